@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- atom-steps/s of the Martini MD inner loop on synthetic water.
 
-    python bench.py --gpus N --steps K --warmup W [--lattice N] [--no-cpu]
+    python bench.py --gpus N --steps K --warmup W [--lattice N] [--dump-outputs DIR] [--full [--no-cpu]]
 
 One "step" is one NGLF velocity-Verlet step of the whole box (half kick, drift,
 image refresh, nonbonded + bonded forces with energy and virial, half kick +
@@ -11,9 +11,14 @@ box (FCC n=102 lattice = 4 244 832 beads >= SURVEY 8d's 4 096 000, even under a 
 state resident in HBM;
 200 untimed steps in front of the warm-up melt the lattice start (50 K) into the
 liquid (~307 K), so the timed steps see production list lengths.
-The timed region is max(--steps, 60) steps rounded up to windows of 20, each window between a
-barrier + stream drain on both sides; `ms_per_step` and `value` come from the MEDIAN window
-(`window_ms` lists them all).  At N=1 the line also carries `also`: the other single-GPU configs of
+The timed region is exactly --steps steps, in windows of 20 (the last one shorter when --steps is not a
+multiple of 20), each window between a barrier + stream drain on both sides; `ms_per_step` and `value`
+come from the MEDIAN window's time per step (`window_ms` lists them all).
+--dump-outputs DIR (N=1): after the timed steps, what the timed path hands its caller -- positions,
+velocities and forces of a fixed, seeded sample of at most 262 144 beads, energy terms, virial and
+kinetic terms -- as float64 .npy files under DIR, so that two builds can be compared output for output.
+A plain run measures the headline and nothing else.  --full adds the side measurements: at N=1 the line
+then also carries `also`: the other single-GPU configs of
 BASELINE.json (1 M-bead water, the 2 M-bead lipid bilayer) and one rank's brick of the 8-GPU runs
 through the RCCL loopback, each timed the same way -- in ONE fresh child process started when the
 headline has finished its GPU work (a fault in a side workload never costs the headline's line),
@@ -23,8 +28,8 @@ ALGORITHMIC bytes of SURVEY 8(d): (36 + 24 + 4*L) B per atom-step, L = stored
 full-list entries per atom, over the HIP-event time of that kernel measured on
 the library's own stream; `roofline.traffic` = that kernel's HBM bytes per launch MEASURED IN THIS RUN (N=1 headline: two short
 child runs under `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE`, see live_traffic; the committed profiles/*traffic.json of the
-same device sources only if the profiler is not there).  `cpu_baseline` times the CPU oracle (a port of the
-reference's serial per-rank path; the reference itself cannot be built) on one
+same device sources only if the profiler is not there; live passes under --full only).  `cpu_baseline` (--full)
+times the CPU oracle (a port of the reference's serial per-rank path; the reference itself cannot be built) on one
 host core on a bounded sample of the same workload.
 """
 import argparse
@@ -41,7 +46,9 @@ HEADLINE_N = 102               # FCC edge of the headline box: 4 n^3 = 4 244 832
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 FP64_VALU_PEAK_TFLOPS = 78.6   # vector FP64: half of the guide's 157.3 TFLOP/s FP32 vector peak (AMD's MI355X figure)
 WINDOW = 20                    # timed steps come in windows of 20: one list rebuild each for water (two for the lipid deck's 10-step period)
-MIN_TIMED_STEPS = 60           # at least three windows whatever --steps says (a 20-step region is one rebuild's luck)
+PMC_TIMED_STEPS = 60           # timed steps of the --pmc child runs: three windows (a 20-step region is one rebuild's luck)
+DUMP_MAX_BEADS = 262144        # --dump-outputs: beads in the sample (r, v, f in float64: 18 MiB)
+DUMP_SEED = 20261016           # ... drawn once from this seed: the same beads in every run of the same arguments
 
 
 def cpu_baseline(n_lattice, seconds_budget=12.0, one_million=True):
@@ -120,10 +127,10 @@ def nonbond_is_fused(kernel_name):
 def live_traffic(extra_args, fused, timeout_s=240.0):
     """HBM bytes per launch of the pair kernel, MEASURED IN THIS RUN and IN THE STATE OF THE TIMED RUN (the passes used to
     sample a lattice start within six steps of a rebuild, where the shell-limited walk reads the fewest list bytes): two child runs of
-    this very bench with the SAME equilibration and warm-up as the timed run and MIN_TIMED_STEPS timed steps, under
+    this very bench with the SAME equilibration and warm-up as the timed run and PMC_TIMED_STEPS timed steps, under
     `rocprofv3 --pmc FETCH_SIZE` and `--pmc WRITE_SIZE` -- separate passes, as MI355X_MICROARCH.md prescribes; counters are KiB;
     FETCH_SIZE reports half the bytes of wide coalesced streaming reads on gfx950 and is doubled.  Only the launches of the child's
-    timed windows are averaged (the last MIN_TIMED_STEPS steps' launches by dispatch order: whole rebuild periods, every age of the
+    timed windows are averaged (the last PMC_TIMED_STEPS steps' launches by dispatch order: whole rebuild periods, every age of the
     list).  Fresh child processes (never an exec of this one); None if the profiler is not there or a pass fails.
     fused: price the launches whose epilogue is the integrator's pass (k_nonbond<..., FUSE, LVL>: the template's last argument but one)."""
     import csv
@@ -140,7 +147,7 @@ def live_traffic(extra_args, fused, timeout_s=240.0):
         for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
             out = os.path.join(d, ctr)
             cmd = [prof, "--pmc", ctr, "--output-format", "csv", "-d", out, "-o", "p", "--", sys.executable, os.path.abspath(__file__),
-                   "--no-cpu", "--no-also", "--no-pmc", "--steps", str(MIN_TIMED_STEPS), "--warmup", "20"] + list(extra_args)
+                   "--no-cpu", "--no-also", "--no-pmc", "--steps", str(PMC_TIMED_STEPS), "--warmup", "20"] + list(extra_args)
             env = dict(os.environ)
             env["TMPDIR"] = "/tmp"
             try:
@@ -155,8 +162,8 @@ def live_traffic(extra_args, fused, timeout_s=240.0):
                     if "k_nonbond" in row["Kernel_Name"] and row["Counter_Name"] == ctr:
                         rows.append((int(row["Dispatch_Id"]), nonbond_is_fused(row["Kernel_Name"]), float(row["Counter_Value"])))
             rows.sort()
-            # the timed windows are the child's last MIN_TIMED_STEPS force evaluations (one pair launch each on a single domain)
-            rows = rows[-MIN_TIMED_STEPS:]
+            # the timed windows are the child's last PMC_TIMED_STEPS force evaluations (one pair launch each on a single domain)
+            rows = rows[-PMC_TIMED_STEPS:]
             acc = [v for _, f, v in rows if f == bool(fused)]
             if not acc:
                 return None
@@ -165,7 +172,7 @@ def live_traffic(extra_args, fused, timeout_s=240.0):
     return {"bytes_per_launch": (2.0 * vals["FETCH_SIZE"] + vals["WRITE_SIZE"]) * 1024.0, "FETCH_SIZE_KiB": vals["FETCH_SIZE"], "WRITE_SIZE_KiB": vals["WRITE_SIZE"],
             "source": "live: rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) over child runs of this bench in the timed run's own state "
                       "(same equilibration and warm-up; the %d %s launches of the child's last %d steps: whole rebuild periods); FETCH_SIZE doubled (gfx950), KiB counters"
-                      % (nlaunch, "fused" if fused else "plain", MIN_TIMED_STEPS)}
+                      % (nlaunch, "fused" if fused else "plain", PMC_TIMED_STEPS)}
 
 
 def runtime_libs():
@@ -223,8 +230,9 @@ def build_setup(workload, n, reps, types=0, cadence="reference"):
     return s, "martini_lipid_bilayer_%dk_beads" % (s.natoms // 1000), "deck tiled %s" % reps, None
 
 
-def run_config(workload, n, reps, steps, warmup, equil, world, rank, local_rank, rdzv, transport, loopback, types=0, cadence="reference"):
-    """one workload on this launch's ranks: equilibration, warm-up, then the timed windows.  Returns the pieces of the JSON line."""
+def run_config(workload, n, reps, steps, warmup, equil, world, rank, local_rank, rdzv, transport, loopback, types=0, cadence="reference", dump_dir=None):
+    """one workload on this launch's ranks: equilibration, warm-up, then the timed windows (and the outputs into dump_dir, N=1).
+    Returns the pieces of the JSON line."""
     import numpy as np
     import ddcmd_amd
     from ddcmd_amd.martini import MartiniHIP, MartiniRank, domain_of
@@ -294,7 +302,8 @@ def run_config(workload, n, reps, steps, warmup, equil, world, rank, local_rank,
         done += k
         if thermostat:
             m.group_temperatures()
-    m.step(warmup)
+    if warmup > 0:
+        m.step(warmup)
     if thermostat:
         m.group_temperatures()
     m.sync()
@@ -304,19 +313,22 @@ def run_config(workload, n, reps, steps, warmup, equil, world, rank, local_rank,
         if rdzv is not None:
             rdzv.barrier()                # ... and so is everybody else's
 
-    nwin = max(1, -(-max(steps, MIN_TIMED_STEPS) // WINDOW))
     m.timing(True)
     reb0 = m.list_stats()["rebuilds"]
-    wins = []
-    for _ in range(nwin):
+    wins, wsteps = [], []
+    left = steps
+    while left > 0:
+        k = min(WINDOW, left)
         barrier()
         t0 = time.perf_counter()
-        m.step(WINDOW)
+        m.step(k)
         barrier()
         el = time.perf_counter() - t0
         if rdzv is not None:
             el = float(rdzv.allreduce([el], "max")[0])       # the slowest rank's time
         wins.append(el)
+        wsteps.append(k)
+        left -= k
     launches, kernel_ms = m.timing_read()
     launches_f, kernel_ms_f = m.timing_fused()
     m.timing(False)
@@ -339,8 +351,10 @@ def run_config(workload, n, reps, steps, warmup, equil, world, rank, local_rank,
         comm.update({"ranks_met": int(rdzv.allreduce([1.0])[0]), "beads_per_rank": [int(x) for x in per_rank[:, 0]],
                      "halo_beads_sent_per_step": [int(x) for x in per_rank[:, 1]], "peers_per_rank": [int(x) for x in per_rank[:, 2]],
                      "halo_bytes_per_step_all_ranks": int(round(tot[3])) * 24})
-    med = sorted(wins)[len(wins) // 2]
-    ms_per_step = med * 1e3 / WINDOW
+    if dump_dir:
+        dump_outputs(dump_dir, m, s, e, vir, rk, tion)
+    med = sorted(w / k for w, k in zip(wins, wsteps))[len(wins) // 2]      # seconds per step of the median window
+    ms_per_step = med * 1e3
     L = st["entries"] / float(max(nlocal, 1))
     # SURVEY 8(d), compulsory bytes per bead and launch.  The plain pair kernel: read r_i 24 + q_i 8 + type_i 4, write f_i 24, list 4 L.
     # Between print steps the pair kernel ends in the integrator's pass (BACK kick, kinetic terms,
@@ -382,9 +396,9 @@ def run_config(workload, n, reps, steps, warmup, equil, world, rank, local_rank,
         traffic = None
     traffic_source = "committed: profiles/*traffic.json of these device sources (tools/profile_r04.sh)" if traffic else None
     res = {
-        "value": s.natoms / (med / WINDOW), "ms_per_step": ms_per_step, "ms_per_step_mean": sum(wins) * 1e3 / (len(wins) * WINDOW),
-        "steps_timed": nwin * WINDOW, "window_steps": WINDOW, "window_ms": [round(w * 1e3, 4) for w in wins],
-        "ns_per_day": (WINDOW / med) * dt_fs * 1e-6 * 86400.0,
+        "value": s.natoms / med, "ms_per_step": ms_per_step, "ms_per_step_mean": sum(wins) * 1e3 / steps,
+        "steps_timed": steps, "window_steps": WINDOW, "window_ms": [round(w * 1e3, 4) for w in wins],
+        "ns_per_day": (1.0 / med) * dt_fs * 1e-6 * 86400.0,
         "config": {"workload": wname, "beads_total": s.natoms, "beads_rank0": nlocal,
                    "lattice": lattice, "lattice_n": lattice_n,
                    "stands_for": ("BASELINE configs[3] '4M-bead Martini water' (SURVEY 8d: 4 096 000 on a simple-cubic start that explodes at 20 fs; "
@@ -411,6 +425,36 @@ def run_config(workload, n, reps, steps, warmup, equil, world, rank, local_rank,
         res["comm"] = comm
     m.close()
     return res
+
+
+def dump_outputs(d, m, s, e, vir, rk, tion):
+    """--dump-outputs: what the timed path hands its caller after its last step, as float64 .npy files under d -- positions, velocities
+    and forces (rows in gid order; a box of more than DUMP_MAX_BEADS beads gives the rows of a fixed sample drawn from DUMP_SEED, whose
+    row numbers are bead_index.npy), the energy terms (martini.E_NAMES), the virial (xx yy zz xy xz yz) and the kinetic terms (rk, then
+    the kinetic tensor).  A single-GPU context: the whole box is this process's."""
+    import numpy as np
+    from ddcmd_amd.martini import E_NAMES
+    if hasattr(m, "download_particles"):          # a loopback rank owns its beads in its own order: gid says which is which
+        st = m.download_particles()
+        gid = st["gid"]
+    else:
+        st = m.download()
+        gid = np.asarray(s.gid, dtype=np.uint64)
+    order = np.argsort(gid, kind="stable")
+    pick = np.arange(order.size)
+    if order.size > DUMP_MAX_BEADS:
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(order.size, DUMP_MAX_BEADS, replace=False))
+        order = order[pick]
+    os.makedirs(d, exist_ok=True)
+    out = {"positions": np.stack([st["r"][c][order] for c in range(3)], axis=1),
+           "velocities": np.stack([st["v"][c][order] for c in range(3)], axis=1),
+           "forces": np.stack([st["f"][c][order] for c in range(3)], axis=1),
+           "bead_index": pick,
+           "energy_terms": np.array([e[k] for k in E_NAMES]),
+           "virial": np.asarray(vir),
+           "kinetic": np.concatenate(([rk], np.asarray(tion)))}
+    for name, a in out.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def spawn_ranks(n):
@@ -487,9 +531,15 @@ def main():
     ap.add_argument("--lattice", dest="n", type=int, default=HEADLINE_N, help="FCC lattice edge: 4*n^3 beads (102 -> 4.24M: the headline; 100 -> 4.0M: rounds 1-4; 64 -> 1.05M, 25 -> 62.5k)")
     ap.add_argument("--cpu-n", type=int, default=26, help="lattice edge of the CPU-baseline sample (26 -> 70 304 beads: BASELINE configs[1] '64k-bead water', the smallest FCC box with at least 64 000)")
     ap.add_argument("--cpu-1m", type=int, default=1, help="1: also time the oracle on the 1.05 M-bead box of configs[2] for one rebuild period (SURVEY 8d: '1 M if time allows', ~20 s); 0: skip")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="N=1: only the headline workload, not the other single-GPU configs")
-    ap.add_argument("--no-pmc", action="store_true", help="N=1 headline: do not measure the pair kernel's HBM bytes live (two short child runs under rocprofv3 --pmc)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements (N=1): the CPU baseline, the other single-GPU configs (`also`) and the live HBM bytes of the pair "
+                         "kernel (rocprofv3 --pmc child runs); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N=1: after the timed steps write what the timed path computed (positions, velocities, forces of a fixed bead sample; "
+                         "energies, virial, kinetic terms) as float64 DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: no CPU baseline")
+    ap.add_argument("--no-also", action="store_true", help="--full, N=1: only the headline workload, not the other single-GPU configs")
+    ap.add_argument("--no-pmc", action="store_true", help="--full, N=1 headline: do not measure the pair kernel's HBM bytes live (two short child runs under rocprofv3 --pmc)")
     ap.add_argument("--workload", choices=("water", "lipid"), default="water",
                     help="water: the headline Martini water box; lipid: tests/golden/lipid_deck (DPPC-style bilayer patch in water, "
                          "all bonded term kinds, charges, Berendsen) tiled --reps times")
@@ -507,6 +557,10 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.gpus != 1:
+        raise SystemExit("bench.py: --dump-outputs is for single-GPU runs (--gpus 1)")
     if "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) != args.gpus:
         # a launcher that started W ranks of a bench asked for N GPUs: a flat scaling curve in the making -- refuse
         sys.stderr.write("bench.py: --gpus %d but WORLD_SIZE=%s: the launcher's world and --gpus must agree\n" % (args.gpus, os.environ["WORLD_SIZE"]))
@@ -585,7 +639,8 @@ def main():
         ctypes.CDLL(None).fflush(None)
         print(json.dumps({"also": rows, "pmc": pmc}), file=real_stdout, flush=True)
         return
-    res = run_config(args.workload, args.n, args.reps, args.steps, args.warmup, args.equil, world, rank, local_rank, rdzv, transport, args.rccl_loopback, args.types, args.cadence)
+    res = run_config(args.workload, args.n, args.reps, args.steps, args.warmup, args.equil, world, rank, local_rank, rdzv, transport, args.rccl_loopback, args.types, args.cadence,
+                     dump_dir=args.dump_outputs)
     out = {
         "metric": "atom_steps_per_sec", "value": res.pop("value"), "unit": "atom-steps/s",
         "n_gpus": world, "steps": res["steps_timed"], "steps_requested": args.steps, "warmup": args.warmup,
@@ -596,7 +651,7 @@ def main():
     out["runtime_libs"] = runtime_libs()
     headline = world == 1 and args.workload == "water" and args.n == HEADLINE_N and not args.rccl_loopback
     pmc_jobs = []      # (row or None for the headline, bench arguments of the PMC child runs, dominant launch fused?)
-    if headline and not args.no_also:
+    if headline and args.full and not args.no_also:
         # The other single-GPU configurations run in ONE fresh child process (this very file with --rows-only), started when this process
         # has finished its own GPU work: a fault in one of them costs the `also` block, never the headline's line.  (Round 6 saw "Memory access
         # fault by GPU node" end one default run in eight; the cause -- the context object registered with hipHostRegister at recycled heap
@@ -618,7 +673,7 @@ def main():
         except Exception as ex:      # the headline stands on its own
             out["also"] = [{"error": "the `also` workloads: %s" % ex}]
     under_profiler = "rocprof" in os.environ.get("LD_PRELOAD", "").lower() or any(k.startswith(("ROCPROF", "ROCP_TOOL")) for k in os.environ)
-    if headline and not args.no_pmc and not under_profiler:      # (a run that is itself being profiled starts no profiler of its own)
+    if headline and args.full and not args.no_pmc and not under_profiler:      # (a run that is itself being profiled starts no profiler of its own)
         # roofline.traffic measured in THIS run: this process and its rows child have finished their GPU work; every pass is a fresh child process
         for row, job, fused in [(None, ["--lattice", str(args.n)], out["roofline"].get("dominant_is_fused", False))] + pmc_jobs:
             lt = live_traffic(job, fused)
@@ -627,7 +682,7 @@ def main():
                 t_k = rf["kernel_ms_avg"] * 1e-3
                 rf.update({"traffic": lt["bytes_per_launch"], "traffic_source": lt["source"], "traffic_FETCH_SIZE_KiB": lt["FETCH_SIZE_KiB"],
                            "traffic_WRITE_SIZE_KiB": lt["WRITE_SIZE_KiB"], "hbm_frac_measured": lt["bytes_per_launch"] / t_k / 1e9 / HBM_PEAK_GBS})
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline(args.cpu_n, one_million=bool(args.cpu_1m) and headline)      # N=1 only (the contract): bounded samples on one host core
     if rdzv is not None:
         rdzv.barrier()

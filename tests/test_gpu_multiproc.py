@@ -222,19 +222,19 @@ def test_bench_world2_as_the_driver_launches_it():
     env.update({"DDCMI_BENCH_SINGLE_DEVICE": "1", "DDCMI_TRANSPORT": "host"})
     env.pop("DDCMI_RDZV_FILE", None); env.pop("DDCMI_RDZV_PORT", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "40", "--warmup", "20", "--lattice", "14"]
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "60", "--warmup", "20", "--lattice", "14"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, "rank 0 prints ONE JSON line"
     out = json.loads(lines[0])
-    # "steps" says what was TIMED (at least MIN_TIMED_STEPS = 60, in windows of 20), "steps_requested" echoes --steps
-    assert out["n_gpus"] == 2 and out["steps"] == 60 and out["steps_requested"] == 40 and out["steps_timed"] == 60 and out["value"] > 0 and out["scaling"] == "strong"
+    # "steps" says what was TIMED (exactly --steps, in windows of 20), "steps_requested" echoes --steps
+    assert out["n_gpus"] == 2 and out["steps"] == 60 and out["steps_requested"] == 60 and out["steps_timed"] == 60 and out["value"] > 0 and out["scaling"] == "strong"
     pf = out["comm"]["preflight_rank0"]
     assert pf["stages_verified"] == 3 and pf["directions"] == 18 and pf["peers"] == [1] and out["comm"]["ranks_met"] == 2
     assert out["comm"]["peers_rank0"][0]["peer"] == 1 and out["comm"]["peers_rank0"][0]["send_bytes_per_step"] > 0
     assert out["config"]["beads_total"] == 4 * 14 ** 3 and 0 < out["config"]["beads_rank0"] < out["config"]["beads_total"]
-    # at least 60 timed steps whatever --steps says, in windows of 20 (one rebuild each); the median window is the figure
+    # 60 timed steps in windows of 20 (one rebuild each); the median window is the figure
     assert out["steps_timed"] == 60 and len(out["window_ms"]) == 3 and out["config"]["rebuilds_in_timed_region"] == 3
     assert abs(out["ms_per_step"] - sorted(out["window_ms"])[1] / 20.0) < 1e-9 * out["ms_per_step"] + 1e-4
     c = out["comm"]
@@ -244,7 +244,7 @@ def test_bench_world2_as_the_driver_launches_it():
     for l in out["runtime_libs"]:
         assert os.path.realpath(l).startswith(os.path.realpath("/opt/rocm") + os.sep), l
     # the same box on one rank gives the same energies (the decomposition changes no physics)
-    p1 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "40", "--warmup", "20", "--lattice", "14", "--no-cpu"],
+    p1 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "60", "--warmup", "20", "--lattice", "14", "--no-cpu"],
                         cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert p1.returncode == 0, p1.stderr[-3000:]
     one = json.loads([l for l in p1.stdout.splitlines() if l.startswith("{")][0])
@@ -267,6 +267,36 @@ def test_bench_gpus2_with_no_launcher_runs_two_ranks():
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["comm"]["ranks_met"] == 2 and sum(out["comm"]["beads_per_rank"]) == 4 * 14 ** 3
     assert "2x1x1" in out["config"]["parallelism"] and out["value"] > 0
+
+
+def test_bench_times_the_steps_asked_and_dumps_what_it_computed(tmp_path):
+    """bench.py --steps K times exactly K steps (windows of 20, the last one shorter) and a plain run carries no side measurement;
+    --dump-outputs writes what the timed path computed as float64 .npy files: the whole box at this size, energies as the line says,
+    and two runs of the same arguments write the same bits (same inputs, and a run repeats bit for bit)"""
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "DDCMI_TRANSPORT", "DDCMI_RCCL_LOOPBACK"):
+        env.pop(k, None)
+    n = 4 * 14 ** 3
+    dumps = []
+    for run in range(2):
+        d = str(tmp_path / ("out%d" % run))
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--lattice", "14", "--steps", "50", "--warmup", "5", "--dump-outputs", d],
+                           cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        out = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+        assert out["steps"] == out["steps_timed"] == out["steps_requested"] == 50 and len(out["window_ms"]) == 3
+        per = sorted(w / k for w, k in zip(out["window_ms"], (20, 20, 10)))
+        assert abs(out["ms_per_step"] - per[1]) < 1e-3 * per[1] + 1e-4      # (window_ms is rounded to 0.1 us)
+        assert "also" not in out and "cpu_baseline" not in out
+        a = {f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)}
+        assert set(a) == {"positions", "velocities", "forces", "bead_index", "energy_terms", "virial", "kinetic"}
+        assert all(v.dtype == np.float64 and np.isfinite(v).all() for v in a.values())
+        assert a["positions"].shape == a["velocities"].shape == a["forces"].shape == (n, 3) and np.array_equal(a["bead_index"], np.arange(n))
+        assert a["energy_terms"][6] == out["check"]["epot"] and a["kinetic"][0] == out["check"]["ekin"] and a["kinetic"].shape == (7,)
+        assert np.abs(a["forces"]).max() > 0 and sum(v.nbytes for v in a.values()) <= 64 << 20
+        dumps.append(a)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
 
 
 def test_nglfconstraint_between_processes():
@@ -307,7 +337,7 @@ def test_bench_world8_on_one_device():
     env.update({"DDCMI_BENCH_SINGLE_DEVICE": "1", "DDCMI_TRANSPORT": "host"})
     env.pop("DDCMI_RDZV_FILE", None); env.pop("DDCMI_RDZV_PORT", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "40", "--warmup", "20", "--lattice", "16"]
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "60", "--warmup", "20", "--lattice", "16"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1200)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -320,7 +350,7 @@ def test_bench_world8_on_one_device():
     assert c["ranks_met"] == 8 and len(c["beads_per_rank"]) == 8 and sum(c["beads_per_rank"]) == 4 * 16 ** 3
     assert c["peers_per_rank"] == [7] * 8 and all(b > 0 for b in c["halo_beads_sent_per_step"])
     assert c["halo_bytes_per_step_all_ranks"] == 24 * sum(c["halo_beads_sent_per_step"]) and c["rccl_version"].count(".") == 2
-    p1 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "40", "--warmup", "20", "--lattice", "16", "--no-cpu"],
+    p1 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "60", "--warmup", "20", "--lattice", "16", "--no-cpu"],
                         cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert p1.returncode == 0, p1.stderr[-3000:]
     one = json.loads([l for l in p1.stdout.splitlines() if l.startswith("{")][0])

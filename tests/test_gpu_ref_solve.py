@@ -1,13 +1,13 @@
 """The device's constraint solve (k_constrain through ddcmi_step_nglf) against the reference's own linear solver: solve.c,
-compiled where it lies into oracle/_ref (make -C oracle ref) and run in a child process (tests/ref_probe.py)."""
-import os
+compiled where it lies into oracle/_ref (make -C oracle ref) and run in a child process (tests/ref_probe.py); without it, its
+answers as recorded in tests/golden/ref_pinned.npz (tests/test_ref_pinned.py, SolveTape)."""
 import numpy as np
 import pytest
 
 import ddcmd_amd
-from test_ref_pinned import REF, make_constraint_system, groups_of, res_move_cons
+from test_ref_pinned import make_constraint_system, groups_of, res_move_cons
 
-pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not os.path.exists(REF), reason="oracle/_ref not built (make -C oracle ref needs /root/reference)")]
+pytestmark = pytest.mark.gpu
 
 
 def constraint_setup(sysd, dt):
@@ -67,13 +67,13 @@ def test_device_constraint_step_against_the_references_linear_solver(seed):
     m.close()
     # the reference's direct form
     g0 = groups_of(sysd, sysd["r"], sysd["v"])
-    assert 2 <= res_move_cons(0, g0, dt) <= 30
+    assert 2 <= res_move_cons(0, g0, dt, "gpu%d_0" % seed) <= 30
     v1 = sysd["v"].copy()
     for g in g0:
         v1[g["idx"]] = g["V"]
     r1 = sysd["r"] + dt * v1
     g1 = groups_of(sysd, r1, v1)
-    assert res_move_cons(1, g1, dt) == 1
+    assert res_move_cons(1, g1, dt, "gpu%d_1" % seed) == 1
     v2 = v1.copy()
     for g in g1:
         v2[g["idx"]] = g["V"]

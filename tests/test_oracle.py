@@ -10,7 +10,7 @@ import ddcmd_amd
 from ddcmd_amd.deck import units_convert, load_deck
 from ddcmd_amd.synth import make_water_setup
 
-REF_DECK = "/root/reference/examples/waterbox/object.data"
+REF_DECK = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_waterbox", "object.data")      # examples/waterbox as shipped
 
 
 def test_units_ddcmd_internal():
@@ -164,7 +164,6 @@ def test_synth_generator_is_deterministic():
     assert int(big.gid[3]) == 3 << 32
 
 
-@pytest.mark.skipif(not os.path.exists(REF_DECK), reason="reference deck only exists in the build container")
 def test_deck_loader_on_reference_waterbox(waterbox):
     """host C loader on the real deck == the committed fixture"""
     s0, g = waterbox

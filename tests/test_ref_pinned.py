@@ -1,7 +1,8 @@
-"""Restatements pinned against the REAL reference where it can be built here: oracle/_ref/libddcmd_ref_small.so is
-compiled by oracle/Makefile from /root/reference/src/{crc32,primes,format}.c where they lie (files that need nothing
-but libc; ddcMD as a whole cannot be built: its util/ recbis/ cub/ submodules are empty).  The product's and the
-oracle's versions of the same functions must agree with it bit for bit."""
+"""Restatements pinned against the REAL reference: oracle/_ref/libddcmd_ref_small.so is compiled by oracle/Makefile from the
+reference's crc32.c, primes.c, format.c and solve.c where they lie (files that need nothing but libc; ddcMD as a whole cannot be
+built: its util/ recbis/ cub/ submodules are empty).  The product's and the oracle's versions of the same functions must agree
+with it bit for bit.  Where the reference sources are not there, the tests take its answers as recorded from that library in
+tests/golden/ref_pinned.npz (tests/golden/make_ref_pinned.py); where they are, the recording is checked against the live answers."""
 import ctypes
 import os
 import numpy as np
@@ -12,10 +13,11 @@ import ddcmd_amd
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = os.path.join(ROOT, "oracle", "_ref", "libddcmd_ref_small.so")
-pytestmark = pytest.mark.skipif(not os.path.exists(REF), reason="oracle/_ref not built (make -C oracle needs /root/reference)")
+RECORDED = os.path.join(ROOT, "tests", "golden", "ref_pinned.npz")
+RECORD = None      # tests/golden/make_ref_pinned.py: a dict that collects the live answers of the solve tapes
 
 
-def _ref(*args):
+def _live(*args):
     """what the reference's own code answers, from a child process (tests/ref_probe.py): the reference library is never
     mapped into this process; every call is a fresh process, so primes.c's file-scope search state starts clean"""
     import json
@@ -24,6 +26,21 @@ def _ref(*args):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "ref_probe.py")] + [str(a) for a in args], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     return json.loads(out.stdout.splitlines()[-1])
+
+
+def _recorded(key):
+    with np.load(RECORDED) as g:
+        return g[key]
+
+
+def _ref(*args):
+    """the reference's answer: live where oracle/_ref is built (and then the recording must say the same), else as recorded"""
+    key = "_".join(str(a) for a in args)
+    want = _recorded(key).tolist()
+    if os.path.exists(REF):
+        live = _live(*args)
+        assert live == want, "tests/golden/ref_pinned.npz[%s] is not what the reference answers: re-record it (tests/golden/make_ref_pinned.py)" % key
+    return want
 
 
 def test_record_checksum_is_the_references_crc32():
@@ -85,6 +102,44 @@ def _ref_solve_batch(systems):
     return [np.array(x) for x in json.loads(out.stdout.splitlines()[-1])]
 
 
+def _digest(M, rhs):
+    """what a recorded system is recognised by: its size, sum |M| and sum |rhs|"""
+    return [float(len(rhs)), float(np.abs(M).sum()), float(np.abs(rhs).sum())]
+
+
+class SolveTape(object):
+    """solve() over the systems one run of res_move_cons meets, in order: live where oracle/_ref is built (checked against the recording
+    of the same tape), else the recorded solutions -- each handed out only for a system with the recorded digest (rtol 1e-9)"""
+
+    def __init__(self, name):
+        self.name, self.k, self.off = name, 0, 0
+        self.rec = RECORD.setdefault(name, ([], [])) if RECORD is not None else None
+        if self.rec is None:
+            self.dig = _recorded("solve_%s_digest" % name)
+            self.x = _recorded("solve_%s_x" % name)
+
+    def __call__(self, systems):
+        live = _ref_solve_batch(systems) if os.path.exists(REF) else None
+        out = []
+        for j, (M, rhs) in enumerate(systems):
+            d = np.array(_digest(M, rhs))
+            n = len(rhs)
+            if self.rec is not None:
+                self.rec[0].append(d)
+                self.rec[1].append(live[j])
+                out.append(live[j])
+                continue
+            assert self.k < len(self.dig), "tape %s: more systems than recorded" % self.name
+            assert np.allclose(d, self.dig[self.k], rtol=1e-9, atol=0), ("tape %s: system %d is not the recorded one" % (self.name, self.k), d, self.dig[self.k])
+            x = self.x[self.off:self.off + n]
+            if live is not None:
+                assert np.allclose(live[j], x, rtol=1e-12, atol=1e-300), "tape %s: the recording is not what solve() answers" % self.name
+            out.append(x.copy())
+            self.k += 1
+            self.off += n
+        return out
+
+
 def constraint_matrix(location, rab, pairs, rmass, dt, dist, V):
     """solveConstraintMatrix's assembly, nglfconstraint.c:139-160, as written there:
     M[ab][uv] = (r_ab . r_uv) (((u==a)-(v==a)) / m_a - ((u==b)-(v==b)) / m_b),  rhs[ab] = -func(dt, d^2, r_ab, V_a - V_b)
@@ -110,13 +165,15 @@ def constraint_apply(lam, rab, pairs, rmass, V):
             V[a] += ((int(u == a) - int(v == a)) * rmass[a] * lam[uv]) * rab[uv]
 
 
-def res_move_cons(location, groups, dt, tol=1.0e-12, maxit=60):
+def res_move_cons(location, groups, dt, tape, tol=1.0e-12, maxit=60):
     """resMoveCons (nglfconstraint.c:266-312) for a list of constraint groups {rab, pairs, rmass, dist, V}: solveConstraintMatrix
-    until err = |lambda| <= tol (BACK: err = 0 after the one linear solve, :172-173), the linear systems by the reference's solve()"""
+    until err = |lambda| <= tol (BACK: err = 0 after the one linear solve, :172-173), the linear systems by the reference's solve()
+    (SolveTape `tape`)"""
     todo = list(range(len(groups)))
+    solve = SolveTape(tape)
     for it in range(maxit):
         sysm = [constraint_matrix(location, g["rab"], g["pairs"], g["rmass"], dt, g["dist"], g["V"]) for g in (groups[k] for k in todo)]
-        lams = _ref_solve_batch(sysm)
+        lams = solve(sysm)
         nxt = []
         for k, lam in zip(todo, lams):
             g = groups[k]
@@ -229,7 +286,7 @@ def test_constraint_solve_against_the_references_linear_solver(seed):
                                            pyoracle._d(v[0]), pyoracle._d(v[1]), pyoracle._d(v[2]), sysd["gid"].ctypes.data_as(pyoracle.up), pyoracle._i(sysd["species"]))
         assert 1 < sweeps < 500
         groups = groups_of(sysd, sysd["r"], sysd["v"])
-        its = res_move_cons(location, groups, dt)
+        its = res_move_cons(location, groups, dt, "cpu%d_%d" % (seed, location))
         assert its == 1 if location == 1 else 2 <= its <= 30
         worst = 0.0
         for g in groups:
