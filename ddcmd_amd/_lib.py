@@ -140,6 +140,12 @@ class CSetup(ctypes.Structure):
         ("random_name", ctypes.c_char_p), ("random_lcg64", ctypes.c_int), ("lcg_from_file", ctypes.c_int),
         ("lcg_state", c_u64_p), ("lcg_multID", ctypes.POINTER(ctypes.c_uint32)), ("lcg_prime", ctypes.POINTER(ctypes.c_uint32)),
         ("group_vcm", c_double_p),
+        ("nanalysis", ctypes.c_int),
+        ("an_name", c_char_pp), ("an_typename", c_char_pp),
+        ("an_type", c_int_p), ("an_eval_rate", c_int_p), ("an_outputrate", c_int_p),
+        ("pc_filename", c_char_pp),
+        ("pc_nbins", c_int_p), ("pc_log", c_int_p), ("pc_method", c_int_p),
+        ("pc_rmin", c_double_p), ("pc_delta_r", c_double_p),
     ]
 
 

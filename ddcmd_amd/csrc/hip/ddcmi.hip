@@ -554,6 +554,7 @@ extern "C" void ddcmi_destroy(ddcmi_ctx *ctx)
    ctx->cg_pa.release(); ctx->cg_pb.release();
    for (auto b : {&ctx->inc_boff, &ctx->inc_aoff, &ctx->inc_toff, &ctx->inc_brow, &ctx->inc_arow, &ctx->inc_trow, &ctx->inc_haoff, &ctx->inc_harow, &ctx->inc_hatoms, &ctx->inc_latoms, &ctx->inc_ldesc, &ctx->inc_hdesc, &ctx->inc_tab, &ctx->inc_htab, &ctx->slot_of_atom, &ctx->hvals}) b->release();
    ctx->tile_nib.release();
+   ctx->pc_rec.release(); ctx->pc_sorted.release(); ctx->pc_cnt.release(); ctx->pc_start.release(); ctx->pc_hist.release(); ctx->pc_send.release(); ctx->pc_recv.release();
    ctx->tile_base.release(); ctx->nbr16.release(); ctx->excl16.release(); ctx->kpartials.release(); ctx->red_tmp.release(); ctx->fb.release(); ctx->tmp32.release();
    for (auto &e : ctx->ev) (void)hipEventDestroy(e);
    if (ctx->ev_drift) (void)hipEventDestroy(ctx->ev_drift);
@@ -1291,3 +1292,4 @@ extern "C" int ddcmi_timing_fused(ddcmi_ctx *ctx, int64_t *launches, double *tot
 }
 
 #include "ddcmi_multigpu.inl"
+#include "ddcmi_analysis.inl"

@@ -335,6 +335,8 @@ struct ddcmi_ctx
    int mig_scnt[27], mig_rcnt[27];
    dbuf<double> sendbuf, hrecv3, hrecv5, mig_out, mig_in;
    dbuf<int> keep, cnt_xchg;
+   /* ANALYSIS PAIRCORRELATION (ddcmi_analysis.inl): its own records, cell sort and histogram; the halo's records travel in pc_send / pc_recv */
+   dbuf<double4> pc_rec, pc_sorted; dbuf<int> pc_cnt, pc_start; dbuf<unsigned long long> pc_hist; dbuf<double> pc_send, pc_recv;
 };
 
 #define SETERR(ctx, code, ...) do { char _b[512]; snprintf(_b, sizeof(_b), __VA_ARGS__); (ctx)->err = _b; return (code); } while (0)

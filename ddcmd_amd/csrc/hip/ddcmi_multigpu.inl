@@ -721,7 +721,7 @@ static void mg_layout_halo(ddcmi_ctx *ctx)
                     ctx->send_off, ctx->recv_off, &ctx->nsend, &ctx->nrecv, ctx->hmsg_s, ctx->hmsg_r);
 }
 /* in-process emulation: same matching rule, direct device copies */
-static int mg_xchg_data_local(ddcmi_group *g, int which /*0 migration, 1 halo5, 2 halo3*/)
+static int mg_xchg_data_local(ddcmi_group *g, int which /*0 migration, 1 halo5, 2 halo3, 3 the pair correlation's records (pc_send -> pc_recv, 4 wide)*/)
 {
    for (ddcmi_ctx *A : g->ranks) HIPCHK(A, hipStreamSynchronize(A->stream));
    for (ddcmi_ctx *A : g->ranks)
@@ -741,9 +741,10 @@ static int mg_xchg_data_local(ddcmi_group *g, int which /*0 migration, 1 halo5, 
          {
             int n = A->hs_cnt[code];
             if (n <= 0) continue;
-            int w = (which == 1) ? 5 : 3;
-            double *dst = (which == 1 ? B->hrecv5.p : B->hrecv3.p) + (size_t)B->recv_off[code] * w;
-            HIPCHK(A, hipMemcpyAsync(dst, A->sendbuf.p + (size_t)A->send_off[code] * w, (size_t)n * w * sizeof(double), hipMemcpyDeviceToDevice, A->stream));
+            int w = (which == 1) ? 5 : (which == 3) ? 4 : 3;
+            double *dst = (which == 1 ? B->hrecv5.p : which == 3 ? B->pc_recv.p : B->hrecv3.p) + (size_t)B->recv_off[code] * w;
+            const double *src = (which == 3 ? A->pc_send.p : A->sendbuf.p) + (size_t)A->send_off[code] * w;
+            HIPCHK(A, hipMemcpyAsync(dst, src, (size_t)n * w * sizeof(double), hipMemcpyDeviceToDevice, A->stream));
          }
       }
    /* a device-to-device hipMemcpy on the null stream is ordered neither with the host nor with the ranks'

@@ -13,6 +13,7 @@ POS, VEL, FORCE = 1, 2, 4
 _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int)
 _up = ctypes.POINTER(ctypes.c_uint64)
+_lp = ctypes.POINTER(ctypes.c_int64)
 _MOLRES = np.uint64(0xFFFFFFFFFFFF0000)
 
 
@@ -99,6 +100,7 @@ def _declare(lib):
     lib.ddcmi_rdzv_exchange.argtypes = [vp, ctypes.c_int, _ip, ctypes.POINTER(vp), ctypes.POINTER(szt), ctypes.c_int, _ip, ctypes.POINTER(vp), ctypes.POINTER(szt)]
     lib.ddcmi_domain_bounds.argtypes = [vp, _dp, _dp]
     lib.ddcmi_download_particles.argtypes = [vp, ctypes.c_int, _ip, _up, _ip] + [_dp] * 9
+    lib.ddcmi_pair_correlation.argtypes = [vp, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int, _lp, _lp]
     lib._ddcmi_declared = True
 
 
@@ -524,6 +526,16 @@ class MartiniHIP(object):
         self._chk(self.lib.ddcmi_group_temperatures(self.ctx, _d(T)))
         return T
 
+    def pair_correlation(self, rmin, delta_r, nbins, log=False):
+        """ANALYSIS PAIRCORRELATION, one evaluation (ddcmi_pair_correlation): (counts[ncombo, nbins], nbeads[nspecies]) of this
+        rank -- ordered pairs (i owned here, species(i) <= species(j)) by comboIndex and bin, and the beads per species"""
+        ns = int(self.s.nspecies)
+        counts = np.zeros((ns * (ns + 1) // 2, int(nbins)), np.int64)
+        nbeads = np.zeros(ns, np.int64)
+        self._chk(self.lib.ddcmi_pair_correlation(self.ctx, float(rmin), float(delta_r), int(nbins), int(bool(log)), ns,
+                                                  counts.ctypes.data_as(_lp), nbeads.ctypes.data_as(_lp)))
+        return counts, nbeads
+
     def download(self, mask=POS | VEL | FORCE):
         n = self.n
         out = [np.zeros(n) for _ in range(9)]
@@ -609,6 +621,7 @@ def _declare_domains(lib):
     lib.ddcmi_group_eval_forces.argtypes = [ctypes.POINTER(vp), ctypes.c_int]
     lib.ddcmi_group_step_nglf.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_double, ctypes.c_int]
     lib.ddcmi_group_temperatures_all.argtypes = [ctypes.POINTER(vp), ctypes.c_int, _dp]
+    lib.ddcmi_group_pair_correlation.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int, _lp, _lp]
     lib._ddcmi_dom_declared = True
 
 
@@ -748,6 +761,17 @@ class MartiniGroup(object):
         T = np.zeros(max(1, self.s.ngroup))
         self._chk(self.lib.ddcmi_group_temperatures_all(self.arr, self.n, _d(T)))
         return T
+
+    def pair_correlation(self, rmin, delta_r, nbins, log=False, per_rank=False):
+        """ddcmi_group_pair_correlation: the domains' (counts, nbeads) summed -- or, per_rank, stacked [rank, ...]"""
+        ns = int(self.s.nspecies)
+        counts = np.zeros((self.n, ns * (ns + 1) // 2, int(nbins)), np.int64)
+        nbeads = np.zeros((self.n, ns), np.int64)
+        self._chk(self.lib.ddcmi_group_pair_correlation(self.arr, self.n, float(rmin), float(delta_r), int(nbins), int(bool(log)), ns,
+                                                        counts.ctypes.data_as(_lp), nbeads.ctypes.data_as(_lp)))
+        if per_rank:
+            return counts, nbeads
+        return counts.sum(axis=0), nbeads.sum(axis=0)
 
     def energies(self):
         """sum over ranks = energyInfo.c allreduce()"""

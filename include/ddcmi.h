@@ -232,6 +232,16 @@ int ddcmi_group_temperatures(ddcmi_ctx *ctx, double *Tgroup);
 int ddcmi_get_clock(const ddcmi_ctx *ctx, int64_t *loop, double *time);
 int ddcmi_sync(ddcmi_ctx *ctx);
 
+/* ---- analysis -------------------------------------------------------------- */
+/* paircorrelation_eval_geom (paircorrelation.c:354-457) on the device: this rank's counts of ordered pairs (i owned here, j any
+ * other bead) with rmin <= r < rmin + nbins*delta_r, species(i) <= species(j), in combo-major order
+ * counts[comboIndex(a,b)*nbins + k] (ncombo = nspecies(nspecies+1)/2), and this rank's beads per species in nbeads[nspecies].
+ * log_scale: ddcMD's rscale = log (rmin > 0).  Sums over ranks are the global histogram exactly.  rmax must not exceed half
+ * the shortest periodic box side, and on a decomposed run the potential's cut-off.  Collective on a decomposed context.  Reads
+ * the current positions (those ddcmi_download_state returns) and changes nothing of the run. [sync] */
+int ddcmi_pair_correlation(ddcmi_ctx *ctx, double rmin, double delta_r, int nbins, int log_scale,
+                           int nspecies, int64_t *counts, int64_t *nbeads);
+
 /* ---- introspection / measurement ------------------------------------------- */
 /* list statistics of the last build: stats[0]=stored full-list entries,
  * [1]=excluded-list entries, [2]=ELL width, [3]=image (halo) atoms, [4]=cells,

@@ -41,6 +41,10 @@ int ddcmi_group_eval_forces(ddcmi_ctx **ctxs, int n);
 int ddcmi_group_step_nglf(ddcmi_ctx **ctxs, int n, double dt, int nsteps);
 /* ddcmi_group_temperatures for an in-process group (sums over its domains) */
 int ddcmi_group_temperatures_all(ddcmi_ctx **ctxs, int n, double *Tgroup);
+/* ddcmi_pair_correlation for an in-process group: every domain's own result, domain after domain -- counts[r*ncombo*nbins ...],
+ * nbeads[r*nspecies ...] for domain r */
+int ddcmi_group_pair_correlation(ddcmi_ctx **ctxs, int n, double rmin, double delta_r, int nbins, int log_scale, int nspecies,
+                                 int64_t *counts, int64_t *nbeads);
 /* the lean step (a single domain of FREE beads without bonded terms: one launch per step, the second stage of its energy / virial /
  * kinetic sums formed for all pending steps at once): the sums of the steps of the last such launch, 32 doubles per step --
  * {lj, ele, virial xx yy zz xy xz yz} as the full list counts them (twice), {rk, tion xx yy zz xy xz yz}, 0, the bonded kernels'

@@ -1,0 +1,134 @@
+"""GPU tests (-m gpu) of ANALYSIS PAIRCORRELATION in the ddcmi_md driver: the deck's analysis list, findEndLoop's stops, the discarded
+startup sample, eval / output after the checkpoint and before the snapshot, snapshot.<loop>/paircorrelation.dat as
+paircorrelation_output writes it -- checked against a numpy recomputation from the atoms files the same run wrote."""
+import glob
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from ddcmd_amd.analysis import PairCorrelation, parse_output
+from ddcmd_amd.deck import load_deck, units_convert
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EXE = os.path.join(ROOT, "ddcmd_amd", "bin", "ddcmi_md")
+RDF = "rdf ANALYSIS { type = PAIRCORRELATION; eval_rate = 10; outputrate = 50; delta_r = 0.1 Angstrom; length = 100; }\n"
+
+
+def _copy(tmp_path, which, name):
+    d = tmp_path / name
+    shutil.copytree(os.path.join(ROOT, "tests", "golden", which), str(d))
+    return d
+
+
+def _np_counts(s, rmin, dr, nbins):
+    """(counts[ncombo, nbins], nbeads) of a loaded state by brute force (minimum image)"""
+    r = np.stack([s.rx, s.ry, s.rz], axis=1)
+    sp = np.asarray(s.species, np.int64)
+    L = s.h[[0, 4, 8]]
+    ns, n = s.nspecies, len(sp)
+    rmax = rmin + nbins * dr
+    counts = np.zeros((ns * (ns + 1) // 2) * nbins, np.int64)
+    for i0 in range(0, n, 512):
+        d = r[None, :, :] - r[i0:i0 + 512, None, :]
+        for a in range(3):
+            if (s.pbc >> a) & 1:
+                d[:, :, a] -= L[a] * np.rint(d[:, :, a] / L[a])
+        rr = np.sqrt((d * d).sum(axis=2))
+        si, sj = sp[i0:i0 + 512][:, None], sp[None, :]
+        ii = np.arange(i0, min(n, i0 + 512))[:, None]
+        keep = (rr >= rmin) & (rr < rmax) & (si <= sj) & (ii != np.arange(n)[None, :])
+        a_, b_ = np.broadcast_to(si, rr.shape)[keep], np.broadcast_to(sj, rr.shape)[keep]
+        k = ((rr[keep] - rmin) / dr).astype(np.int64)
+        ok = (k >= 0) & (k < nbins)
+        combo = (b_ - a_) + ns * a_ - (a_ * (a_ - 1)) // 2
+        counts += np.bincount((combo * nbins + k)[ok], minlength=counts.size)
+    return counts.reshape(-1, nbins), np.bincount(sp, minlength=ns)
+
+
+def _run(cwd, extra, world=1):
+    args = ["-o", "object.data", "-d", "data", "-x", extra]
+    if world == 1:
+        out = subprocess.run([EXE] + args, capture_output=True, text=True, timeout=600, cwd=str(cwd))
+        assert out.returncode == 0, out.stdout + out.stderr
+        return out
+    env = dict(os.environ, WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", DDCMI_TRANSPORT="host", DDCMI_SINGLE_DEVICE="1",
+               DDCMI_RDZV_FILE=os.path.join(str(cwd), "rdzv_port"))
+    procs = [subprocess.Popen([EXE] + args, cwd=str(cwd), env=dict(env, RANK=str(r), LOCAL_RANK=str(r)), stdout=subprocess.PIPE,
+                              stderr=subprocess.PIPE, text=True) for r in range(world)]
+    outs = []
+    for p in procs:
+        try:
+            outs.append(p.communicate(timeout=600))
+        except subprocess.TimeoutExpired:
+            for q in procs:
+                q.kill()
+            raise
+        assert p.returncode == 0, outs[-1]
+    return outs
+
+
+@pytest.mark.parametrize("which", ["water_deck", "lipid_deck"])
+def test_driver_writes_paircorrelation_files(tmp_path, which):
+    sim = "simulate SIMULATE { analysis = rdf; deltaloop = 100; maxloop = 100; printrate = 10; snapshotrate = 10; checkpointrate = 100000; }\n"
+    d = _copy(tmp_path, which, "with")
+    _run(d, sim + RDF)
+    d0 = _copy(tmp_path, which, "without")
+    _run(d0, sim.replace("analysis = rdf; ", ""))
+    assert open(str(d / "data"), "rb").read() == open(str(d0 / "data"), "rb").read()      # the analysis changes nothing of the run
+    s0 = load_deck(str(d / "object.data"))
+    dr = units_convert(0.1, "Angstrom", None)
+    for loop in (50, 100):
+        (path,) = glob.glob(str(d / ("snapshot.*%d" % loop) / "paircorrelation.dat"))
+        txt = open(path).read()
+        fields, nsample, names, r, g = parse_output(txt)
+        assert txt.splitlines()[0] == "# rmin = 0.000000 Ang; delta_r = 0.100000 Ang; length = 100; eval_rate = 10; outputrate = 50;"
+        assert nsample == 5 and len(r) == 100 and abs(r[0] - 0.05) < 1e-9
+        assert len(names) == s0.nspecies * (s0.nspecies + 1) // 2 and names[0] == "%s-%s" % (s0.species_name[0], s0.species_name[0])
+        # numpy: the same samples from the atoms files of loops loop-40 ... loop
+        pc = PairCorrelation(s0.nspecies, 0.0, dr, 100, eval_rate=10, outputrate=50)
+        one = np.zeros_like(pc.g)
+        for L_ in range(loop - 40, loop + 1, 10):
+            snap = glob.glob(str(d / ("snapshot.*%d" % L_)))[0]
+            st = load_deck(str(d / "object.data"), restart_file=os.path.join(snap, "restart"))
+            c, nb = _np_counts(st, 0.0, dr, 100)
+            pc.add(c, nb)
+            vol = float(st.h[0] * st.h[4] * st.h[8])
+        want_txt = pc.output_text(vol, s0.species_name)
+        _, _, names_w, r_w, want = parse_output(want_txt)
+        assert names_w == names and np.allclose(r_w, r)
+        # one count more or less in a bin (a pair at a bin edge, atoms files are rounded): what that count is worth there
+        left = np.arange(100) * dr
+        dv = 4 * np.pi / 3 * ((left + dr) ** 3 - left ** 3)
+        nbs = np.bincount(np.asarray(s0.species), minlength=s0.nspecies).astype(float)
+        from ddcmd_amd.analysis import combo_pairs
+        unit = np.array([[vol / 5 / dv[k] / (nbs[a] * nbs[b]) for k in range(100)] for a, b in combo_pairs(s0.nspecies)])
+        assert np.all(np.abs(g - want) <= 1e-5 * np.abs(want) + 2.01 * unit), np.abs(g - want).max()
+        assert np.abs(g - want).sum() <= 1e-5 * np.abs(want).sum() + 4 * unit.max()
+
+
+def test_driver_two_ranks_write_the_same_files(tmp_path):
+    sim = "simulate SIMULATE { analysis = rdf; deltaloop = 50; maxloop = 50; printrate = 10; snapshotrate = 10; checkpointrate = 100000; }\n"
+    d1 = _copy(tmp_path, "water_deck", "one")
+    _run(d1, sim + RDF)
+    d2 = _copy(tmp_path, "water_deck", "two")
+    _run(d2, sim + RDF, world=2)
+    (a,) = glob.glob(str(d1 / "snapshot.*50" / "paircorrelation.dat"))
+    (b,) = glob.glob(str(d2 / "snapshot.*50" / "paircorrelation.dat"))
+    assert open(a).read() == open(b).read()
+
+
+def test_unsupported_analysis_is_named_once_and_changes_nothing(tmp_path):
+    sim = "simulate SIMULATE { deltaloop = 20; maxloop = 20; printrate = 10; snapshotrate = 100000; checkpointrate = 100000; %s}\n"
+    w = "writeCharmm ANALYSIS { type = subsetWrite; outputrate = 10; }\n"
+    d = _copy(tmp_path, "water_deck", "with")
+    out = _run(d, sim % "analysis = writeCharmm; " + w)
+    d0 = _copy(tmp_path, "water_deck", "without")
+    _run(d0, sim % "")
+    lines = [l for l in out.stderr.splitlines() if "writeCharmm" in l]
+    assert len(lines) == 1 and "subsetWrite" in lines[0] and "not supported" in lines[0]
+    assert open(str(d / "data"), "rb").read() == open(str(d0 / "data"), "rb").read()
+    assert sorted(os.listdir(str(d))) == sorted(os.listdir(str(d0)))      # no file of its own
