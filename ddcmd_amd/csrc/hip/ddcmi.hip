@@ -531,47 +531,7 @@ extern "C" void ddcmi_destroy(ddcmi_ctx *ctx)
    if (ctx->ph_on > 0)
       for (int k = 0; k < 32; k++)
          if (ctx->ph_cnt[k]) fprintf(stderr, "ddcmi phase %2d %-28s %8.1f us x %ld\n", k, ctx->ph_name[k], ctx->ph_sum[k] / ctx->ph_cnt[k], ctx->ph_cnt[k]);
-   ddcmi_comm_destroy(ctx);
-   dbuf<double> *db[] = {&ctx->d_invmass, &ctx->d_mass, &ctx->d_charge_sp, &ctx->bpartials, &ctx->vx, &ctx->vy, &ctx->vz, &ctx->vx2, &ctx->vy2, &ctx->vz2,
-                         &ctx->fx, &ctx->fy, &ctx->fz, &ctx->d_kqtab, &ctx->partials};
-   for (auto b : db) b->release();
-   dbuf<int> *ib[] = {&ctx->d_ljtype_sp, &ctx->d_moltype_sp, &ctx->d_mol_nspecies, &ctx->d_bpair_off, &ctx->d_bpairI, &ctx->d_bpairJ, &ctx->species, &ctx->species2,
-                      &ctx->group, &ctx->group2, &ctx->orig, &ctx->orig2, &ctx->slot_of_orig, &ctx->cid, &ctx->crank, &ctx->order, &ctx->cell_cnt_o, &ctx->cell_start_o,
-                      &ctx->cell_cnt_h, &ctx->cell_start_h, &ctx->cell_start, &ctx->cell_cnt, &ctx->nimg, &ctx->img_off, &ctx->hsrc_t, &ctx->hshift_t, &ctx->hcid, &ctx->hrank,
-                      &ctx->horder, &ctx->halo_src, &ctx->halo_shift, &ctx->scan_tmp, &ctx->nbr_cnt, &ctx->excl, &ctx->excl_cnt,
-                      &ctx->stage_idx, &ctx->tile_nstage, &ctx->tile_width, &ctx->tile_rows, &ctx->tile_work, &ctx->sched, &ctx->tile_perm};
-   for (auto b : ib) b->release();
-   ctx->d_lvltab.release(); ctx->d_lvlidx.release();
-   /* (audit of every dbuf member against this function, round 6: these were never released either) */
-   ctx->hkey.release(); ctx->lcg.release(); ctx->lcg2.release(); ctx->nbr_cum.release(); ctx->cg_atom_gid.release(); ctx->mol_atom_gid.release(); ctx->cg_slot.release(); ctx->mol_slot.release();
-   ctx->mol_mtot.release(); ctx->mol_info.release(); ctx->mol_red.release(); ctx->mol_split.release(); ctx->hs_idx.release(); ctx->dir_cnt.release(); ctx->send_map.release();
-   ctx->sendbuf.release(); ctx->hrecv3.release(); ctx->hrecv5.release(); ctx->mig_out.release(); ctx->mig_in.release(); ctx->keep.release(); ctx->cnt_xchg.release();
-   ctx->lean_part.release(); ctx->lean_kpart.release(); ctx->lean_hist.release(); ctx->lean_tmp.release(); ctx->lean_bpart.release(); ctx->d_vring.release();      /* (~80 MB per context at 1 M beads) */
-   ctx->pos.release(); ctx->pos2.release(); ctx->d_ljtab.release(); ctx->gid.release(); ctx->gid2.release();
-   ctx->d_exmask.release(); ctx->rest_gid.release(); ctx->rest_fc.release(); ctx->rest_slot.release(); ctx->rest_r0.release(); ctx->rest_kb.release(); ctx->pos0.release(); ctx->disp.release(); ctx->atom_gid.release(); ctx->hkeys.release();
-   for (auto b : {&ctx->cg_dist, &ctx->inc_bpar, &ctx->inc_apar, &ctx->inc_tpar}) b->release();
-   for (auto b : {&ctx->cg_atom_off, &ctx->cg_atoms, &ctx->cg_pair_off, &ctx->cons_status, &ctx->mol_off, &ctx->mol_atoms}) b->release();
-   ctx->cg_pa.release(); ctx->cg_pb.release();
-   for (auto b : {&ctx->inc_boff, &ctx->inc_aoff, &ctx->inc_toff, &ctx->inc_brow, &ctx->inc_arow, &ctx->inc_trow, &ctx->inc_haoff, &ctx->inc_harow, &ctx->inc_hatoms, &ctx->inc_latoms, &ctx->inc_ldesc, &ctx->inc_hdesc, &ctx->inc_tab, &ctx->inc_htab, &ctx->slot_of_atom, &ctx->hvals}) b->release();
-   ctx->tile_nib.release();
-   ctx->pc_rec.release(); ctx->pc_sorted.release(); ctx->pc_cnt.release(); ctx->pc_start.release(); ctx->pc_hist.release(); ctx->pc_send.release(); ctx->pc_recv.release();
-   ctx->tile_base.release(); ctx->nbr16.release(); ctx->excl16.release(); ctx->kpartials.release(); ctx->red_tmp.release(); ctx->fb.release(); ctx->tmp32.release();
-   for (auto &e : ctx->ev) (void)hipEventDestroy(e);
-   if (ctx->ev_drift) (void)hipEventDestroy(ctx->ev_drift);
-   if (ctx->ev_halo) (void)hipEventDestroy(ctx->ev_halo);
-   if (ctx->ev_build) (void)hipEventDestroy(ctx->ev_build);
-   if (ctx->ev_sorted) (void)hipEventDestroy(ctx->ev_sorted);
-   if (ctx->ev_interior) (void)hipEventDestroy(ctx->ev_interior);
-   if (ctx->stream2) { (void)hipStreamSynchronize(ctx->stream2); (void)hipStreamDestroy(ctx->stream2); }
-   if (ctx->stream_post) { (void)hipStreamSynchronize(ctx->stream_post); (void)hipStreamDestroy(ctx->stream_post); }
-   if (ctx->d_results) (void)hipFree(ctx->d_results);
-   if (ctx->h_results) (void)hipHostFree(ctx->h_results);
-   if (ctx->d_flags) (void)hipFree(ctx->d_flags);
-   if (ctx->h_flags) (void)hipHostFree(ctx->h_flags);
-   for (int k = 0; k < 3; k++) if (ctx->h_pin[k]) (void)hipHostFree(ctx->h_pin[k]);
-   if (ctx->mbox_h) (void)hipHostFree(ctx->mbox_h);
-   if (ctx->agree_h) (void)hipHostFree(ctx->agree_h);
-   (void)hipStreamDestroy(ctx->stream);
+   ddcmi_comm_destroy(ctx);      /* (before any buffer is freed) */
    delete ctx;
 }
 
@@ -1186,7 +1146,6 @@ extern "C" int ddcmi_kinetic_detail(ddcmi_ctx *ctx, int by_species, int nclass, 
    hipLaunchKernelGGL(k_class_kinetic_sum, dim3(cdiv(nclass * KD_NV, 64)), dim3(64), 0, st, nclass, part.p, res.p);
    HIPCHK(ctx, hipMemcpyAsync(out, res.p, (size_t)nclass * KD_NV * sizeof(double), hipMemcpyDeviceToHost, st));
    HIPCHK(ctx, hipStreamSynchronize(st));
-   part.release(); res.release();
    return DDCMI_OK;
 }
 
@@ -1235,7 +1194,7 @@ extern "C" int ddcmi_get_list(ddcmi_ctx *ctx, int which, int *start, int *j, int
    for (int i = 0; i < n; i++) start[i + 1] = start[i] + c[i];
    if (j && tot > 0)
    {
-      if (d_j.ensure(tot)) { d_start.release(); SETERR(ctx, DDCMI_ENOMEM, "get_list alloc"); }
+      if (d_j.ensure(tot)) SETERR(ctx, DDCMI_ENOMEM, "get_list alloc");
       HIPCHK(ctx, hipMemcpyAsync(d_start.p, start, (n + 1) * sizeof(int), hipMemcpyHostToDevice, st));
       {
          NbTileArgs na;
@@ -1252,7 +1211,6 @@ extern "C" int ddcmi_get_list(ddcmi_ctx *ctx, int which, int *start, int *j, int
       HIPCHK(ctx, hipMemcpyAsync(j, d_j.p, tot * sizeof(int), hipMemcpyDeviceToHost, st));
       HIPCHK(ctx, hipStreamSynchronize(st));
    }
-   d_start.release(); d_j.release();
    return DDCMI_OK;
 }
 

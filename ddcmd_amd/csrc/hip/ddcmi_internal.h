@@ -8,6 +8,7 @@
 #include <time.h>
 #include <string.h>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include "ddcmi.h"
 #include "ddcmi_test.h"      /* the test-only entry points: compiled into the objects, exported by libddcmi_test.so only */
@@ -83,10 +84,17 @@ static inline int ddcmi_debug_guard()
    if (g < 0) { const char *e = getenv("DDCMI_DEBUG_GUARD"); g = e ? atoi(e) : 0; }
    return g;
 }
+/* a device buffer that owns its memory: freed (canary checked) when it goes out of scope; moved, never copied */
 template <class T> struct dbuf
 {
    T *p = nullptr;
    size_t cap = 0;
+   dbuf() = default;
+   dbuf(const dbuf &) = delete;
+   dbuf &operator=(const dbuf &) = delete;
+   dbuf(dbuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+   dbuf &operator=(dbuf &&o) noexcept { if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; } return *this; }
+   ~dbuf() { release(); }
    static size_t guard() { return ddcmi_debug_guard() ? (256 + sizeof(T) - 1) / sizeof(T) : 0; }
    void check() const
    {
@@ -112,6 +120,30 @@ template <class T> struct dbuf
       return 0;
    }
    void release() { if (p) { check(); (void)hipFree(p); } p = nullptr; cap = 0; }
+};
+static_assert(!std::is_copy_constructible<dbuf<int>>::value && std::is_nothrow_move_constructible<dbuf<int>>::value, "dbuf is move-only");
+/* growable mapped pinned host memory of ints that owns its memory: h the host's address, d the device's.  ensure() discards the old
+ * contents: a block that grows holds n + slack ints. */
+struct hbuf
+{
+   int *h = nullptr, *d = nullptr;
+   size_t cap = 0;
+   hbuf() = default;
+   hbuf(const hbuf &) = delete;
+   hbuf &operator=(const hbuf &) = delete;
+   hbuf(hbuf &&o) noexcept : h(o.h), d(o.d), cap(o.cap) { o.h = o.d = nullptr; o.cap = 0; }
+   hbuf &operator=(hbuf &&o) noexcept { if (this != &o) { release(); h = o.h; d = o.d; cap = o.cap; o.h = o.d = nullptr; o.cap = 0; } return *this; }
+   ~hbuf() { release(); }
+   int ensure(size_t n, size_t slack)
+   {
+      if (n <= cap) return 0;
+      release();
+      if (hipHostMalloc((void **)&h, (n + slack) * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) { h = nullptr; return -1; }
+      if (hipHostGetDevicePointer((void **)&d, h, 0) != hipSuccess) { release(); return -1; }
+      cap = n + slack;
+      return 0;
+   }
+   void release() { if (h) (void)hipHostFree(h); h = d = nullptr; cap = 0; }
 };
 
 /* which tiles a k_tile_build launch searches.  mode 0: all (block b = tile b).  mode 1: the box of tile coordinates [lo, lo + n) --
@@ -269,23 +301,14 @@ struct ddcmi_ctx
    double *d_results = nullptr; double *h_results = nullptr;
    int *d_flags = nullptr; int *h_flags = nullptr;      /* d_flags: DDCMI_NFLAGS ints, see the DDCMI_FLAG_* slots */
    /* decomposed runs, RCCL transport: the outcome of a rebuild's local phase (mg_phase4_finish) is agreed on by an all-reduce that
-    * nobody waits for -- its result lands in agree_h (mapped host memory, [0] = sequence word, [1] = worst error code) and is
+    * nobody waits for -- its result lands in agree (mapped host memory, [0] = sequence word, [1] = worst error code) and is
     * looked at in front of the next host wait (ddcmi_agree_poll) */
-   int *agree_h = nullptr, *agree_d = nullptr; int agree_seq = 0; bool agree_pending = false; int64_t agree_loop = 0;
-   /* growable pinned host staging (so that small copies are truly asynchronous): [0] tile work, [1] tile order, [2] count exchange */
+   hbuf agree; int agree_seq = 0; bool agree_pending = false; int64_t agree_loop = 0;
    /* the mailbox (scan.hip: ddcmi_post / ddcmi_post_wait): mapped coherent host memory, [0] = sequence word */
-   int *mbox_h = nullptr, *mbox_d = nullptr; size_t mbox_cap = 0; int mbox_seq = 0;
-   int *h_pin[3] = {nullptr, nullptr, nullptr}; size_t h_pin_cap[3] = {0, 0, 0};
-   int *pinned(int which, size_t n)
-   {
-      if (n <= h_pin_cap[which]) return h_pin[which];
-      if (h_pin[which]) (void)hipHostFree(h_pin[which]);
-      h_pin[which] = nullptr; h_pin_cap[which] = 0;
-      size_t cap = n + n / 4 + 64;
-      if (hipHostMalloc((void **)&h_pin[which], cap * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) return nullptr;
-      h_pin_cap[which] = cap;
-      return h_pin[which];
-   }
+   hbuf mbox; int mbox_seq = 0;
+   /* growable pinned host staging (so that small copies are truly asynchronous): [0] tile work, [1] tile order, [2] count exchange */
+   hbuf h_pin[3];
+   int *pinned(int which, size_t n) { return h_pin[which].ensure(n, n / 4 + 64) ? nullptr : h_pin[which].h; }
    double self_ele = 0.0; std::vector<long> sp_count;      /* sp_count: beads per species of the last ddcmi_upload_state (one domain: the self term follows new charges / constants without the beads) */
    /* what the last rebuild's tail left zeroed for this one (k_rebuild_tail): the cell counters (for this cell count, in these buffers),
     * the flags, the arena counter, the direction counters; a rebuild that cannot rely on it clears them itself */
@@ -337,6 +360,19 @@ struct ddcmi_ctx
    dbuf<int> keep, cnt_xchg;
    /* ANALYSIS PAIRCORRELATION (ddcmi_analysis.inl): its own records, cell sort and histogram; the halo's records travel in pc_send / pc_recv */
    dbuf<double4> pc_rec, pc_sorted; dbuf<int> pc_cnt, pc_start; dbuf<unsigned long long> pc_hist; dbuf<double> pc_send, pc_recv;
+   /* what is not a dbuf or an hbuf; those free themselves after this */
+   ~ddcmi_ctx()
+   {
+      (void)hipSetDevice(device);
+      for (hipStream_t s : {stream, stream2, stream_post}) if (s) (void)hipStreamSynchronize(s);
+      for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+      for (hipEvent_t e : {ev_drift, ev_halo, ev_build, ev_sorted, ev_interior}) if (e) (void)hipEventDestroy(e);
+      for (hipStream_t s : {stream, stream2, stream_post}) if (s) (void)hipStreamDestroy(s);
+      if (d_results) (void)hipFree(d_results);
+      if (h_results) (void)hipHostFree(h_results);
+      if (d_flags) (void)hipFree(d_flags);
+      if (h_flags) (void)hipHostFree(h_flags);
+   }
 };
 
 #define SETERR(ctx, code, ...) do { char _b[512]; snprintf(_b, sizeof(_b), __VA_ARGS__); (ctx)->err = _b; return (code); } while (0)
@@ -355,34 +391,32 @@ struct RoctxRange
 {
    typedef int (*push_fn)(const char *);
    typedef int (*pop_fn)(void);
-   static int state() { static int s = -1; if (s < 0) { const char *e = getenv("DDCMI_ROCTX"); s = (e && atoi(e) != 0) ? 1 : 0; } return s; }
-   static bool bind(push_fn *pu, pop_fn *po)
+   struct Markers { bool on; push_fn push; pop_fn pop; };
+   static Markers load()
    {
-      static push_fn push = nullptr; static pop_fn pop = nullptr; static bool tried = false;
-      if (!tried)
+      Markers m = {false, nullptr, nullptr};
+      const char *e = getenv("DDCMI_ROCTX");
+      if (!e || atoi(e) == 0) return m;
+      m.on = true;
+      for (const char *lib : {"librocprofiler-sdk-roctx.so", "librocprofiler-sdk-roctx.so.1", "libroctx64.so", "libroctx64.so.4"})
       {
-         tried = true;
-         for (const char *lib : {"librocprofiler-sdk-roctx.so", "librocprofiler-sdk-roctx.so.1", "libroctx64.so", "libroctx64.so.4"})
-         {
-            void *h = dlopen(lib, RTLD_NOW | RTLD_GLOBAL);
-            if (!h) continue;
-            push = (push_fn)dlsym(h, "roctxRangePushA"); pop = (pop_fn)dlsym(h, "roctxRangePop");
-            if (push && pop) break;
-            push = nullptr; pop = nullptr;
-         }
+         void *h = dlopen(lib, RTLD_NOW | RTLD_GLOBAL);
+         if (!h) continue;
+         m.push = (push_fn)dlsym(h, "roctxRangePushA"); m.pop = (pop_fn)dlsym(h, "roctxRangePop");
+         if (m.push && m.pop) break;
+         m.push = nullptr; m.pop = nullptr;
       }
-      *pu = push; *po = pop;
-      return push != nullptr;
+      return m;
    }
-   bool on = false;
+   pop_fn pop = nullptr;
    explicit RoctxRange(const char *name)
    {
-      if (!state()) return;
-      push_fn pu; pop_fn po;
+      static const Markers mk = load();      /* (resolved once; the initialisation of a local static is thread-safe) */
+      if (!mk.on) return;
       g_roctx_ranges++;      /* (counted whether or not a marker library is there: tests) */
-      if (bind(&pu, &po)) { pu(name); on = true; }
+      if (mk.push) { mk.push(name); pop = mk.pop; }
    }
-   ~RoctxRange() { if (on) { push_fn pu; pop_fn po; bind(&pu, &po); po(); } }
+   ~RoctxRange() { if (pop) pop(); }
 };
 
 

@@ -462,8 +462,8 @@ static int mg_counts_round(ddcmi_ctx *ctx, int *scnt, int *rcnt, bool *any_over,
       pj.add(ctx->cnt_xchg.p + 32, MG_BLK * (size_t)nr).add(ctx->d_flags, 8);
       int rcp;
       if ((rcp = ddcmi_post(ctx, st, pj)) || (rcp = ddcmi_post_wait(ctx, st))) return rcp;
-      memcpy(all, ctx->mbox_h + pj.off[0], MG_BLK * (size_t)nr * sizeof(int));
-      if (with_flags) memcpy(ctx->h_flags, ctx->mbox_h + pj.off[1], 8 * sizeof(int));
+      memcpy(all, ctx->mbox.h + pj.off[0], MG_BLK * (size_t)nr * sizeof(int));
+      if (with_flags) memcpy(ctx->h_flags, ctx->mbox.h + pj.off[1], 8 * sizeof(int));
    }
    *any_over = false;
    for (int r = 0; r < nr; r++)
@@ -516,7 +516,7 @@ static int mg_agree(ddcmi_ctx *ctx, int local_rc)
       pj.add(ctx->cnt_xchg.p + 1, 1);
       int rcp;
       if ((rcp = ddcmi_post(ctx, st, pj)) || (rcp = ddcmi_post_wait(ctx, st))) return rcp;
-      worst = ctx->mbox_h[pj.off[0]];
+      worst = ctx->mbox.h[pj.off[0]];
    }
    if (local_rc) { ctx->err = local_msg; return local_rc; }
    if (worst) SETERR(ctx, DDCMI_ECOMM, "another rank failed during the list rebuild (error %d): its own message says why", worst);
@@ -543,11 +543,10 @@ __global__ void k_agree_post(const int *src, int *dst, int seq)
 static int mg_agree_async(ddcmi_ctx *ctx, int local_rc, int pretend_peer_code = 0 /* tests: the code a failed peer would have contributed */)
 {
    hipStream_t st = ctx->stream;
-   if (!ctx->agree_h)
+   if (!ctx->agree.h)
    {
-      if (hipHostMalloc((void **)&ctx->agree_h, 16 * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) { ctx->agree_h = nullptr; return mg_agree(ctx, local_rc); }
-      if (hipHostGetDevicePointer((void **)&ctx->agree_d, ctx->agree_h, 0) != hipSuccess) { (void)hipHostFree(ctx->agree_h); ctx->agree_h = nullptr; return mg_agree(ctx, local_rc); }
-      memset(ctx->agree_h, 0, 16 * sizeof(int));
+      if (ctx->agree.ensure(16, 0)) return mg_agree(ctx, local_rc);
+      memset(ctx->agree.h, 0, 16 * sizeof(int));
    }
    { int rcp = ddcmi_agree_poll(ctx); if (rcp && !local_rc) return rcp; }      /* (never two agreements in flight) */
    const std::string local_msg = ctx->err;
@@ -559,7 +558,7 @@ static int mg_agree_async(ddcmi_ctx *ctx, int local_rc, int pretend_peer_code = 
    if (h[0] != 0 || !ctx->list_valid) HIPCHK(ctx, hipMemcpyAsync(d, h, sizeof(int), hipMemcpyHostToDevice, st));
    NCCLCHK2(ctx, ncclAllReduce(d, d + 1, 1, ncclInt, ncclMax, (ncclComm_t)ctx->comm, st));
    ctx->agree_seq++;
-   hipLaunchKernelGGL(k_agree_post, dim3(1), dim3(64), 0, st, d + 1, ctx->agree_d, ctx->agree_seq);
+   hipLaunchKernelGGL(k_agree_post, dim3(1), dim3(64), 0, st, d + 1, ctx->agree.d, ctx->agree_seq);
    ctx->agree_pending = true; ctx->agree_loop = ctx->loop;
    if (local_rc)
    {
@@ -574,7 +573,7 @@ static int mg_agree_async(ddcmi_ctx *ctx, int local_rc, int pretend_peer_code = 
 int ddcmi_agree_poll(ddcmi_ctx *ctx)
 {
    if (!ctx->agree_pending) return DDCMI_OK;
-   volatile int *flag = ctx->agree_h;
+   volatile int *flag = ctx->agree.h;
    struct timespec t0; clock_gettime(CLOCK_MONOTONIC, &t0);
    for (unsigned long spin = 0;; spin++)
    {
@@ -591,7 +590,7 @@ int ddcmi_agree_poll(ddcmi_ctx *ctx)
       }
    }
    ctx->agree_pending = false;
-   const int worst = ctx->agree_h[1];
+   const int worst = ctx->agree.h[1];
    if (worst)
    {
       char b[256];
@@ -1481,6 +1480,7 @@ extern "C" int ddcmi_comm_preflight(ddcmi_ctx *ctx, double timeout_s, int64_t re
    const bool absent = hooks && getenv("DDCMI_DEBUG_PREFLIGHT_ABSENT") && atoi(getenv("DDCMI_DEBUG_PREFLIGHT_ABSENT")) == ctx->rank;      /* tests (host transport): this rank never joins the exchange */
    struct timespec t0; clock_gettime(CLOCK_MONOTONIC, &t0);
    auto elapsed = [&]() { struct timespec t1; clock_gettime(CLOCK_MONOTONIC, &t1); return (t1.tv_sec - t0.tv_sec) + 1e-9 * (t1.tv_nsec - t0.tv_nsec); };
+   /* (freed on return: after mg_fatal on the timeout path, whose ncclCommAbort releases the kernels that still use them) */
    dbuf<double> buf;      /* [0, 27 PF_N) send, [27 PF_N, 54 PF_N) receive, then 24 + 24 doubles of the all-reduce */
    dbuf<int> ibuf;        /* MG_BLK ints in, MG_BLK nr ints out */
    int rc = DDCMI_OK;
@@ -1524,7 +1524,6 @@ extern "C" int ddcmi_comm_preflight(ddcmi_ctx *ctx, double timeout_s, int64_t re
             /* a rank that is stuck: its peers run into the rendezvous' deadline and name it; then it leaves for good */
             struct timespec ts = {(time_t)timeout_s + 1, 0}; nanosleep(&ts, nullptr);
             ctx->err = "preflight: this rank stayed away from the exchange (DDCMI_DEBUG_PREFLIGHT_ABSENT)";
-            buf.release(); ibuf.release();
             return mg_fatal(ctx, DDCMI_ECOMM, nullptr);
          }
          if (hipMemcpyAsync(h.data(), ar, 24 * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { rc = DDCMI_ENODEVICE; msg = "preflight download"; break; }
@@ -1643,7 +1642,6 @@ extern "C" int ddcmi_comm_preflight(ddcmi_ctx *ctx, double timeout_s, int64_t re
    } while (0);
    for (int k = 0; k < 3; k++) if (ev[k]) (void)hipEventDestroy(ev[k]);
    if (side) (void)hipStreamDestroy(side);
-   buf.release(); ibuf.release();
    if (report) { report[6] = stage; report[7] = (int64_t)(elapsed() * 1e6); }
    if (rc) ctx->err = msg;
    /* every rank leaves with the same verdict (a transport error above has usually ended the agreement's transport too: then its own error stands) */

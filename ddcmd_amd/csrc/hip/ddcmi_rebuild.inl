@@ -142,7 +142,7 @@ static int bl_self_images(ddcmi_ctx *ctx)
       PostJobs pj;
       pj.add(ctx->d_flags + 8, 1);
       if ((rc = ddcmi_post(ctx, st, pj)) || (rc = ddcmi_post_wait(ctx, st))) return rc;
-      nh = ctx->mbox_h[pj.off[0]];
+      nh = ctx->mbox.h[pj.off[0]];
    }
    ctx->nhalo = nh;
    if (nh > 0)
@@ -260,7 +260,7 @@ static int schedule_tiles(ddcmi_ctx *ctx, int wg_per_cu)
    /* the tile costs came to the host with the build's flags (ddcmi_bl_finish), in pinned memory; the order
     * and the ranges leave from pinned memory too, so this function costs no host round trip of its own */
    const int ntile = ctx->ntile;
-   const int *work = ctx->h_pin[0], *stage = work ? work + ntile : nullptr;
+   const int *work = ctx->h_pin[0].h, *stage = work ? work + ntile : nullptr;
    const size_t cap_items = (size_t)ntile + 16 * 1024 + 64;      /* every tile once + the parts the tails may add: 8 XCD runs x 2 classes, at most 1024 items each */
    int *perm = ctx->pinned(1, cap_items + 64), *sched = perm ? perm + cap_items : nullptr;
    if (!work || !perm) SETERR(ctx, DDCMI_ENOMEM, "pinned staging for the tile schedule");
@@ -598,7 +598,7 @@ int ddcmi_bl_finish(ddcmi_ctx *ctx)
       HIPCHK(ctx, hipGetLastError());
       ctx->phase(11, "build+transpose launched");
       { int rcp = ddcmi_post_wait(ctx, ctx->stream_post); if (rcp) return rcp; }
-      memcpy(ctx->h_flags, ctx->mbox_h + pj.off[0], 64 * sizeof(int));
+      memcpy(ctx->h_flags, ctx->mbox.h + pj.off[0], 64 * sizeof(int));
       if (ctx->nhalo_dev)
       {
          /* the image count the rebuild was launched without (bl_self_images) */
@@ -612,7 +612,7 @@ int ddcmi_bl_finish(ddcmi_ctx *ctx)
          }
          ctx->nhalo = nh_true;
       }
-      memcpy(h_work, ctx->mbox_h + pj.off[1], 5 * (size_t)ntile * sizeof(int));
+      memcpy(h_work, ctx->mbox.h + pj.off[1], 5 * (size_t)ntile * sizeof(int));
       ctx->phase(12, "wait for the build");
       tot[0] = tot[1] = 0;
       int maxw = 0;

@@ -119,31 +119,26 @@ int ddcmi_post(ddcmi_ctx *ctx, hipStream_t st, PostJobs &j)
 {
    size_t need = 16;
    for (int q = 0; q < j.cnt; q++) { j.off[q] = (int)need; need += (size_t)((j.n[q] + 3) & ~3); }
-   if (need > ctx->mbox_cap)
+   if (need > ctx->mbox.cap)
    {
       /* (every post is waited for before the next one: the old mailbox is idle) */
-      if (ctx->mbox_h) (void)hipHostFree(ctx->mbox_h);
-      ctx->mbox_h = nullptr; ctx->mbox_d = nullptr; ctx->mbox_cap = 0;
-      const size_t cap = need + need / 4 + 1024;
-      if (hipHostMalloc((void **)&ctx->mbox_h, cap * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) SETERR(ctx, DDCMI_ENOMEM, "mapped host memory for the mailbox");
-      if (hipHostGetDevicePointer((void **)&ctx->mbox_d, ctx->mbox_h, 0) != hipSuccess) SETERR(ctx, DDCMI_ENODEVICE, "device address of the mailbox");
-      ctx->mbox_cap = cap;
-      ctx->mbox_h[0] = 0; ctx->mbox_seq = 0;
+      if (ctx->mbox.ensure(need, need / 4 + 1024)) SETERR(ctx, DDCMI_ENOMEM, "mapped host memory for the mailbox");
+      ctx->mbox.h[0] = 0; ctx->mbox_seq = 0;
    }
    ctx->mbox_seq++;
    unsigned *ticket = (unsigned *)(ctx->d_flags + DDCMI_FLAG_TICKET);      /* the mailbox's own zeroed word (left at zero by the last workgroup) */
-   hipLaunchKernelGGL(k_post, dim3((unsigned)std::min<size_t>(16, (need + 16383) / 16384)), dim3(1024), 0, st, j, ctx->mbox_d, ctx->mbox_seq, ticket);
+   hipLaunchKernelGGL(k_post, dim3((unsigned)std::min<size_t>(16, (need + 16383) / 16384)), dim3(1024), 0, st, j, ctx->mbox.d, ctx->mbox_seq, ticket);
    HIPCHK(ctx, hipGetLastError());
    return DDCMI_OK;
 }
-/* wait until the last post has landed; job q's data is at mbox_h + off[q].  The first ~100 us are a hot spin (the single-GPU
+/* wait until the last post has landed; job q's data is at mbox.h + off[q].  The first ~100 us are a hot spin (the single-GPU
  * case the mailbox was built for: the post is a few us away); after that the thread yields between looks -- in a decomposed run
  * the wait covers a collective, i.e. the slowest peer, and this thread may share its cores with the transport's progress thread.
  * A post that never lands is an error after 20 s: with a communicator attached it is reported as such (a peer that is gone),
  * never turned into a blocking hipStreamSynchronize behind a collective that cannot finish. */
 int ddcmi_post_wait(ddcmi_ctx *ctx, hipStream_t st)
 {
-   volatile int *flag = ctx->mbox_h;
+   volatile int *flag = ctx->mbox.h;
    struct timespec t0; clock_gettime(CLOCK_MONOTONIC, &t0);
    bool hot = true;
    for (unsigned long spin = 0;; spin++)

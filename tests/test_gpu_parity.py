@@ -1040,7 +1040,9 @@ def test_create_step_destroy_returns_the_device_memory(kind, monkeypatch):
     """ddcmi_destroy left the lean step's rings (two x (items + 8) x 8 x 32 doubles: ~40 MB per context at 1 M beads), the
     displacement ring and -- found by an audit of every device buffer of the context against ddcmi_destroy -- 22 more (the decomposed
     path's send / receive / migration buffers, LCG64 records, nbr_cum ...) allocated.  Create / 45 steps / destroy in a loop: the free
-    device memory after the sixth context is what it was after the second (the first ones warm the runtime's own pools)."""
+    device memory after the sixth context is what it was after the second (the first ones warm the runtime's own pools).  Every
+    context also runs the entry points with scratch buffers of their own (kinetic detail, the list download, the pair correlation
+    and, through RCCL, the preflight)."""
     import ctypes
     import os
     from ddcmd_amd.martini import MartiniHIP, MartiniRank
@@ -1068,6 +1070,13 @@ def test_create_step_destroy_returns_the_device_memory(kind, monkeypatch):
         m.group_temperatures()
         m.step(45)
         m.energies()
+        m.kinetic_detail(True)
+        m.kinetic_detail(False)
+        m.get_list(0)
+        m.get_list(1)
+        m.pair_correlation(0.0, 0.1, 8)
+        if kind == "lipid_loopback":
+            m.preflight(timeout=30.0)
         m.close()
         free.append(_free_device_bytes())
     assert abs(free[5] - free[1]) < (4 << 20), [f >> 20 for f in free]
