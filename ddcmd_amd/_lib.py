@@ -146,6 +146,7 @@ class CSetup(ctypes.Structure):
         ("pc_filename", c_char_pp),
         ("pc_nbins", c_int_p), ("pc_log", c_int_p), ("pc_method", c_int_p),
         ("pc_rmin", c_double_p), ("pc_delta_r", c_double_p),
+        ("vaf_filename", c_char_pp), ("vaf_length", c_int_p),
     ]
 
 

@@ -1,6 +1,9 @@
-"""ANALYSIS type PAIRCORRELATION on the host side: accumulation of the device's pair counts into g(r) and the output file, as
-paircorrelation_eval_geom / paircorrelation_output (paircorrelation.c) do.  The counting itself is ddcmi_pair_correlation
-(Martini*.pair_correlation); nothing here searches pairs."""
+"""ANALYSIS types PAIRCORRELATION and VELOCITYAUTOCORRELATION on the host side.
+PairCorrelation: accumulation of the device's pair counts into g(r) and the output file, as paircorrelation_eval_geom /
+paircorrelation_output (paircorrelation.c) do.  The counting itself is ddcmi_pair_correlation (Martini*.pair_correlation); nothing
+here searches pairs.
+VelocityAutocorrelation: the windows of velocityAutocorrelation_eval and the file of velocityAutocorrelation_output
+(velocityAutocorrelation.c) over the device's sums (Martini*.vaf_origin / vaf_sample)."""
 import numpy as np
 
 from .deck import units_convert
@@ -96,3 +99,105 @@ def parse_output(text):
     names = lines[2].lstrip("#").split()[1:]
     rows = np.array([[float(x) for x in ln.split()] for ln in lines[3:] if ln.strip()])
     return fields, nsample, names, rows[:, 0], rows[:, 1:].T
+
+
+class VelocityAutocorrelation(object):
+    """one VELOCITYAUTOCORRELATION analysis (velocityAutocorrelation.c:117-327).  eval(sample, origin) is the reference's state
+    machine: sample() returns (vaf, msd) of [1 + ngroup + nspecies] classes summed over the ranks, origin() sets the time origin;
+    add(vaf, msd) stores one sample by hand.  Every class is kept; output_text leaves out the group block of a single group and the
+    species block of a single species, as the reference does."""
+
+    def __init__(self, ngroup, nspecies, length=1, eval_rate=0, outputrate=0, filename="vaf.dat"):
+        if int(length) < 1:
+            raise ValueError("length = %d" % length)
+        self.ng, self.ns, self.length = max(1, int(ngroup)), int(nspecies), int(length)
+        self.eval_rate, self.outputrate, self.filename = int(eval_rate), int(outputrate), filename
+        self.ncl = 1 + self.ng + self.ns
+        self.last = 0
+        self.vaf0, self.msd0 = np.zeros((self.ncl, self.length + 1)), np.zeros((self.ncl, self.length + 1))
+        self.clear()
+
+    def clear(self):
+        """the reset velocityAutocorrelation_output does after writing"""
+        self.vaf_, self.msd_ = np.zeros((self.ncl, self.length + 1)), np.zeros((self.ncl, self.length + 1))
+        self.nsample = 0
+
+    def add(self, vaf, msd, k=None):
+        """sample k (default: the current entry, last) of the current window"""
+        k = self.last if k is None else int(k)
+        self.vaf0[:, k] = np.asarray(vaf, dtype=np.float64)
+        self.msd0[:, k] = np.asarray(msd, dtype=np.float64)
+
+    def accumulate(self):
+        """a full window joins the sums over the windows"""
+        self.nsample += 1
+        self.msd_ += self.msd0
+        self.vaf_ += self.vaf0
+        self.msd0[:] = 0.0
+        self.vaf0[:] = 0.0
+        self.last = 0
+
+    def eval(self, sample, origin):
+        k = self.last
+        if k > 0:
+            self.add(*sample(), k=k)
+        if k == self.length:
+            self.accumulate()
+            k = 0
+        if k == 0:
+            origin()
+            self.add(*sample(), k=0)
+        self.last += 1
+
+    def gate(self):
+        """does output write (and reset)?  nsample * length * eval_rate == outputrate"""
+        return self.nsample * self.length * self.eval_rate == self.outputrate
+
+    def columns(self, group_names, species_names):
+        """(label, class index) of the blocks the file holds"""
+        cols = [("System", 0)]
+        if self.ng > 1:
+            cols += [("Group %s" % group_names[g], 1 + g) for g in range(self.ng)]
+        if self.ns > 1:
+            cols += [("Species %s" % species_names[t], 1 + self.ng + t) for t in range(self.ns)]
+        return cols
+
+    def output_text(self, dt, nglobal, group_counts, species_counts, group_names, species_names):
+        """the file velocityAutocorrelation_output writes, or None when the gate is shut (then nothing is reset).  dt in internal
+        units; the counts are those of the whole system"""
+        if not self.gate():
+            return None
+        tc, v2c, r2c = units_convert(1.0, None, "t"), units_convert(1.0, None, "velocity^2"), units_convert(1.0, None, "l^2")
+        cols = self.columns(group_names, species_names)
+        count = {0: float(nglobal)}
+        count.update({1 + g: float(group_counts[g]) for g in range(len(group_counts))})
+        count.update({1 + self.ng + t: float(species_counts[t]) for t in range(len(species_counts))})
+        head = "%-33s" % "#time (fs)  System vaf MSD"
+        head += "".join("%-26s" % ("  %s vaf MSD" % lab) for lab, _ in cols[1:])
+        lines = [head + " (vaf in Ang^2/fs^2; msd in Ang^2)\n"]
+        for k in range(self.length + 1):
+            row = "%f" % (tc * k * dt * self.eval_rate)
+            for _, c in cols:
+                row += " %e %e" % ((v2c * self.vaf_[c, k] / self.nsample) / count[c], (r2c * self.msd_[c, k] / self.nsample) / count[c])
+            lines.append(row + "\n")
+        self.clear()
+        return "".join(lines)
+
+
+def parse_vaf_output(text):
+    """(block labels, time[length + 1] in fs, vaf[nblock, length + 1], msd[nblock, length + 1]) of a vaf file"""
+    lines = text.splitlines()
+    head = lines[0]
+    body = head[1:head.index("(vaf in")]
+    words = body.split()      # time (fs) System vaf MSD [Group NAME vaf MSD ...] [Species NAME vaf MSD ...]
+    labels, i = [], 2
+    while i < len(words):
+        if words[i] == "System":
+            labels.append("System")
+            i += 3
+        else:
+            labels.append("%s %s" % (words[i], words[i + 1]))
+            i += 4
+    rows = np.array([[float(x) for x in ln.split()] for ln in lines[1:] if ln.strip()])
+    assert rows.shape[1] == 1 + 2 * len(labels)
+    return labels, rows[:, 0], rows[:, 1::2].T, rows[:, 2::2].T

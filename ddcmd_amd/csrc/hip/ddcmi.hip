@@ -292,13 +292,22 @@ __global__ void k_gather_state(int nloc, const int *order,
                                const int *species, const int *group, const uint64_t *gid, const int *orig,
                                double4 *pos2, double *vx2, double *vy2, double *vz2,
                                int *species2, int *group2, uint64_t *gid2, int *orig2, int *slot_of_orig, GridParams gp, int *nimg, int wrap,
-                               const ulonglong2 *lcg, ulonglong2 *lcg2 /* the beads' LCG64 records, nullptr without them */)
+                               const ulonglong2 *lcg, ulonglong2 *lcg2 /* the beads' LCG64 records, nullptr without them */,
+                               const VafRec *vaf = nullptr, VafRec *vaf2 = nullptr /* the beads' reference records (ddcmi_vaf.inl), nullptr without them */)
 {
    int k = blockIdx.x * blockDim.x + threadIdx.x;
    if (k >= nloc) return;
    int i = order[k];
    double4 p = pos[i];
+   const double4 p0 = p;
    if (wrap) back_in_box(gp, p);      /* (k_wrap_cell sorted the beads by their wrapped positions) */
+   if (vaf)
+   {
+      /* the wrap is no displacement: the origin moves by what the wrap moved the bead */
+      VafRec r = vaf[i];
+      r.o[0] += p.x - p0.x; r.o[1] += p.y - p0.y; r.o[2] += p.z - p0.z;
+      vaf2[k] = r;
+   }
    if (nimg)
    {
       int d[3];
@@ -314,6 +323,16 @@ __global__ void k_gather_state(int nloc, const int *order,
    if (lcg) lcg2[k] = lcg[i];
 }
 
+/* in front of a launch that scales the positions by s (the barostat): o' = s p - (p - o), so that d = p - o is what it was */
+__global__ void k_vaf_rescale(int n, double s0, double s1, double s2, const double4 *__restrict__ pos, VafRec *__restrict__ vaf)
+{
+   int i = blockIdx.x * blockDim.x + threadIdx.x;
+   if (i >= n) return;
+   const double4 p = pos[i];
+   VafRec r = vaf[i];
+   r.o[0] = s0 * p.x - (p.x - r.o[0]); r.o[1] = s1 * p.y - (p.y - r.o[1]); r.o[2] = s2 * p.z - (p.z - r.o[2]);
+   vaf[i] = r;
+}
 __global__ void k_slots_from_orig(int nloc, const int *__restrict__ orig, int *slot_of_orig)
 {
    int k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -913,6 +932,7 @@ extern "C" int ddcmi_upload_state(ddcmi_ctx *ctx, int nlocal, const double *rx, 
          if (group[i] < 0 || group[i] >= ctx->ngroup) SETERR(ctx, DDCMI_EINVAL, "particle %d has group %d outside [0,%d)", i, group[i], ctx->ngroup);
    int n = nlocal;
    ctx->lcg_on = false;      /* the streams belong to the beads of the upload they followed: ddcmi_set_random_lcg64 again */
+   ctx->vaf_on = false; ctx->vaf.release(); ctx->vaf2.release();      /* so do the reference records: ddcmi_vaf_origin again */
    ctx->nhalo_hint = 0;      /* (another system: the first rebuild waits for its image count) */
    size_t cap = (size_t)n + n / 4 + 1024;     /* room for image atoms; grown on demand */
    ENSURE(ctx, ctx->pos, cap); ENSURE(ctx, ctx->pos2, cap);
@@ -1251,3 +1271,4 @@ extern "C" int ddcmi_timing_fused(ddcmi_ctx *ctx, int64_t *launches, double *tot
 
 #include "ddcmi_multigpu.inl"
 #include "ddcmi_analysis.inl"
+#include "ddcmi_vaf.inl"

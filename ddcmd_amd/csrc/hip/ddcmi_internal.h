@@ -84,6 +84,10 @@ static inline int ddcmi_debug_guard()
    if (g < 0) { const char *e = getenv("DDCMI_DEBUG_GUARD"); g = e ? atoi(e) : 0; }
    return g;
 }
+/* ANALYSIS VELOCITYAUTOCORRELATION (ddcmi_vaf.inl): a bead's reference record -- its velocity at the time origin and the origin
+ * of its displacement, d = current position - o */
+struct __attribute__((aligned(16))) VafRec { double v0[3], o[3]; };
+
 /* a device buffer that owns its memory: freed (canary checked) when it goes out of scope; moved, never copied */
 template <class T> struct dbuf
 {
@@ -360,6 +364,9 @@ struct ddcmi_ctx
    dbuf<int> keep, cnt_xchg;
    /* ANALYSIS PAIRCORRELATION (ddcmi_analysis.inl): its own records, cell sort and histogram; the halo's records travel in pc_send / pc_recv */
    dbuf<double4> pc_rec, pc_sorted; dbuf<int> pc_cnt, pc_start; dbuf<unsigned long long> pc_hist; dbuf<double> pc_send, pc_recv;
+   /* ANALYSIS VELOCITYAUTOCORRELATION (ddcmi_vaf.inl): the owned beads' reference records in slot order, moved with the beads like lcg
+    * (k_gather_state, the migration records); vaf_part: the sample's per-workgroup sums and, behind them, its result */
+   dbuf<VafRec> vaf, vaf2; bool vaf_on = false; dbuf<double> vaf_part;
    /* what is not a dbuf or an hbuf; those free themselves after this */
    ~ddcmi_ctx()
    {

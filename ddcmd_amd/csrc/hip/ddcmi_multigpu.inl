@@ -77,11 +77,15 @@ __global__ void k_iota(int n, int *a)
 }
 
 struct MigGeom { double L[3], W[3]; int P[3], pc[3], pbc; };
+/* doubles of a migration record: ten, and the six of the bead's reference record behind them while ANALYSIS VELOCITYAUTOCORRELATION
+ * tracks (every rank of a run tracks or none does: ddcmi_vaf_origin is called on all of them) */
+static inline int mig_width(const ddcmi_ctx *ctx) { return ctx->vaf_on ? 16 : 10; }
 
 /* ownership (voronoiCalcParticleDestinations for a cubic lattice of centres =
  * brick index) + packing of the beads that leave: record = x y z tag vx vy vz gid {group, LCG64 multID, prime} {LCG64 state} */
 __global__ void k_mig_classify(MigGeom mg, int nloc, int mig_cap, double4 *pos, const double *vx, const double *vy, const double *vz,
-                               const uint64_t *gid, const int *group, int *keep, int *dir_cnt, double *mig_out, int *flags, const ulonglong2 *lcg, int *orig)
+                               const uint64_t *gid, const int *group, int *keep, int *dir_cnt, double *mig_out, int *flags, const ulonglong2 *lcg, int *orig,
+                               VafRec *vaf = nullptr /* the reference records: width 16, [10..16) = the record; nullptr: width 10 */)
 {
    int i = blockIdx.x * blockDim.x + threadIdx.x;
    if (i == 0) dir_cnt[27] = mig_cap;      /* travels with the counts: every rank sees whether any rank's segments overflowed */
@@ -91,7 +95,17 @@ __global__ void k_mig_classify(MigGeom mg, int nloc, int mig_cap, double4 *pos, 
    if (mg.pbc & 1) { if (p.x > 0.5 * mg.L[0]) p.x -= mg.L[0]; if (p.x < -0.5 * mg.L[0]) p.x += mg.L[0]; }
    if (mg.pbc & 2) { if (p.y > 0.5 * mg.L[1]) p.y -= mg.L[1]; if (p.y < -0.5 * mg.L[1]) p.y += mg.L[1]; }
    if (mg.pbc & 4) { if (p.z > 0.5 * mg.L[2]) p.z -= mg.L[2]; if (p.z < -0.5 * mg.L[2]) p.z += mg.L[2]; }
+   VafRec vr;
+   if (vaf)
+   {
+      /* (the wrap is no displacement, as in k_gather_state; a repeated round finds the bead wrapped and adds zero) */
+      const double4 p0 = pos[i];
+      vr = vaf[i];
+      vr.o[0] += p.x - p0.x; vr.o[1] += p.y - p0.y; vr.o[2] += p.z - p0.z;
+      vaf[i] = vr;
+   }
    pos[i] = p;
+   const int mw = vaf ? 16 : 10;
    double r[3] = {p.x, p.y, p.z};
    int d[3];
 #pragma unroll
@@ -112,7 +126,7 @@ __global__ void k_mig_classify(MigGeom mg, int nloc, int mig_cap, double4 *pos, 
       int slot = atomicAdd(&dir_cnt[code], 1);
       if (slot < mig_cap)
       {
-         double *rec = mig_out + ((size_t)code * mig_cap + slot) * 10;
+         double *rec = mig_out + ((size_t)code * mig_cap + slot) * mw;
          rec[0] = p.x; rec[1] = p.y; rec[2] = p.z; rec[3] = p.w;
          rec[4] = vx[i]; rec[5] = vy[i]; rec[6] = vz[i];
          rec[7] = __longlong_as_double((long long)gid[i]);
@@ -120,6 +134,7 @@ __global__ void k_mig_classify(MigGeom mg, int nloc, int mig_cap, double4 *pos, 
          const ulonglong2 q = lcg ? lcg[i] : make_ulonglong2(0ull, 0ull);
          rec[8] = __longlong_as_double((long long)((unsigned long long)(group[i] & 0xff) | (q.y & 3ull) << 8 | (q.y >> 32) << 32));
          rec[9] = __longlong_as_double((long long)q.x);
+         if (vaf) { for (int k = 0; k < 3; k++) { rec[10 + k] = vr.v0[k]; rec[13 + k] = vr.o[k]; } }
       }
    }
 }
@@ -129,11 +144,11 @@ __global__ void k_compact_order(int n, const int *keep, const int *scan, int *or
    if (i < n && keep[i]) order[scan[i]] = i;
 }
 __global__ void k_unpack_mig(int narr, int nkeep, const double *mig_in, double4 *pos, double *vx, double *vy, double *vz,
-                             uint64_t *gid, int *species, int *group, int *orig, ulonglong2 *lcg)
+                             uint64_t *gid, int *species, int *group, int *orig, ulonglong2 *lcg, VafRec *vaf = nullptr)
 {
    int k = blockIdx.x * blockDim.x + threadIdx.x;
    if (k >= narr) return;
-   const double *rec = mig_in + (size_t)k * 10;
+   const double *rec = mig_in + (size_t)k * (vaf ? 16 : 10);
    int i = nkeep + k;
    pos[i] = make_double4(rec[0], rec[1], rec[2], rec[3]);
    vx[i] = rec[4]; vy[i] = rec[5]; vz[i] = rec[6];
@@ -143,6 +158,7 @@ __global__ void k_unpack_mig(int narr, int nkeep, const double *mig_in, double4 
    group[i] = (int)(w & 0xffull);
    if (lcg) lcg[i] = make_ulonglong2((unsigned long long)__double_as_longlong(rec[9]), (w >> 8 & 3ull) | (w >> 32) << 32);
    orig[i] = i;
+   if (vaf) { VafRec vr; for (int q = 0; q < 3; q++) { vr.v0[q] = rec[10 + q]; vr.o[q] = rec[13 + q]; } vaf[i] = vr; }
 }
 
 /* which owned beads does each neighbour direction need?  (ddcSendRecvTables:
@@ -313,12 +329,14 @@ static int mg_ensure_owned(ddcmi_ctx *ctx, size_t need)
    hipStream_t st = ctx->stream;
    size_t want = need + need / 4 + 4096;
    const bool lcg_fits = !ctx->lcg_on || (ctx->lcg.cap >= need + 1 && ctx->lcg2.cap >= need + 1);
-   if (ctx->vx.cap >= need && ctx->species.cap >= need + 1 && ctx->pos.cap >= need && lcg_fits) return DDCMI_OK;
+   const bool vaf_fits = !ctx->vaf_on || (ctx->vaf.cap >= need + 1 && ctx->vaf2.cap >= need + 1);
+   if (ctx->vx.cap >= need && ctx->species.cap >= need + 1 && ctx->pos.cap >= need && lcg_fits && vaf_fits) return DDCMI_OK;
    dbuf<double> *d3[] = {&ctx->vx, &ctx->vy, &ctx->vz, &ctx->fx, &ctx->fy, &ctx->fz};
    for (auto b : d3) if (b->ensure(want, true, st)) SETERR(ctx, DDCMI_ENOMEM, "growing bead arrays to %zu failed", want);
    dbuf<double> *d3b[] = {&ctx->vx2, &ctx->vy2, &ctx->vz2};
    for (auto b : d3b) if (b->ensure(want)) SETERR(ctx, DDCMI_ENOMEM, "growing bead arrays to %zu failed", want);
    if (ctx->lcg_on && (ctx->lcg.ensure(want + 1, true, st) || ctx->lcg2.ensure(want + 1))) SETERR(ctx, DDCMI_ENOMEM, "growing the LCG64 records to %zu failed", want);
+   if (ctx->vaf_on && (ctx->vaf.ensure(want + 1, true, st) || ctx->vaf2.ensure(want + 1))) SETERR(ctx, DDCMI_ENOMEM, "growing the reference records to %zu failed", want);
    dbuf<int> *i1[] = {&ctx->species, &ctx->group, &ctx->orig};
    for (auto b : i1) if (b->ensure(want + 1, true, st)) SETERR(ctx, DDCMI_ENOMEM, "growing bead arrays to %zu failed", want);
    dbuf<int> *i2[] = {&ctx->species2, &ctx->group2, &ctx->orig2, &ctx->slot_of_orig, &ctx->cid, &ctx->crank, &ctx->order, &ctx->nimg, &ctx->img_off};
@@ -734,7 +752,8 @@ static int mg_xchg_data_local(ddcmi_group *g, int which /*0 migration, 1 halo5, 
             if (n <= 0) continue;
             int roff = 0;
             for (int c = 0; c < code; c++) roff += B->mig_rcnt[c];
-            HIPCHK(A, hipMemcpyAsync(B->mig_in.p + (size_t)roff * 10, A->mig_out.p + (size_t)code * A->mig_cap * 10, (size_t)n * 10 * sizeof(double), hipMemcpyDeviceToDevice, A->stream));
+            const size_t mw = (size_t)mig_width(A);
+            HIPCHK(A, hipMemcpyAsync(B->mig_in.p + (size_t)roff * mw, A->mig_out.p + (size_t)code * A->mig_cap * mw, (size_t)n * mw * sizeof(double), hipMemcpyDeviceToDevice, A->stream));
          }
          else
          {
@@ -763,7 +782,7 @@ static int mg_phase1_launch(ddcmi_ctx *ctx)
       SETERR(ctx, DDCMI_EUNSUPPORTED, "with domain decomposition bonded terms must be given by gid (ddcmi_set_bonded_gid): caller-order indices do not survive migration");
    if ((rc = mg_ensure_owned(ctx, (size_t)n + 1))) return rc;
    if (ctx->mig_cap == 0) ctx->mig_cap = std::max(1024, n / 16);
-   ENSURE(ctx, ctx->mig_out, (size_t)27 * ctx->mig_cap * 10);
+   ENSURE(ctx, ctx->mig_out, (size_t)27 * ctx->mig_cap * mig_width(ctx));
    ENSURE(ctx, ctx->dir_cnt, 32);
    ENSURE(ctx, ctx->keep, (size_t)n + 1);
    if (!ctx->dircnt_clean) ddcmi_zero_ints(ctx, st, ZeroJobs().add(ctx->dir_cnt.p, 32).add(ctx->d_flags, 8));      /* (else: the last rebuild's tail launch left them zeroed) */
@@ -774,7 +793,8 @@ static int mg_phase1_launch(ddcmi_ctx *ctx)
    if (n > 0)
    {
       hipLaunchKernelGGL(k_mig_classify, dim3(cdiv(n, 256)), dim3(256), 0, st, mg, n, ctx->mig_cap, ctx->pos.p, ctx->vx.p, ctx->vy.p, ctx->vz.p,
-                         ctx->gid.p, ctx->group.p, ctx->keep.p, ctx->dir_cnt.p, ctx->mig_out.p, ctx->d_flags, ctx->lcg_on ? ctx->lcg.p : (const ulonglong2 *)nullptr, ctx->orig.p);
+                         ctx->gid.p, ctx->group.p, ctx->keep.p, ctx->dir_cnt.p, ctx->mig_out.p, ctx->d_flags, ctx->lcg_on ? ctx->lcg.p : (const ulonglong2 *)nullptr, ctx->orig.p,
+                         ctx->vaf_on ? ctx->vaf.p : (VafRec *)nullptr);
    }
    return DDCMI_OK;
 }
@@ -819,15 +839,17 @@ static int mg_phase2_migrate_in(ddcmi_ctx *ctx)
          hipLaunchKernelGGL(k_gather_state, dim3(cdiv(nkeep, 256)), dim3(256), 0, st, nkeep, ctx->order.p, ctx->pos.p, ctx->vx.p, ctx->vy.p, ctx->vz.p,
                             ctx->species.p, ctx->group.p, ctx->gid.p, ctx->orig.p,
                             ctx->pos2.p, ctx->vx2.p, ctx->vy2.p, ctx->vz2.p, ctx->species2.p, ctx->group2.p, ctx->gid2.p, ctx->orig2.p, ctx->slot_of_orig.p, ctx->gp, (int *)nullptr, 0,
-                            ctx->lcg_on ? ctx->lcg.p : (const ulonglong2 *)nullptr, ctx->lcg2.p);
+                            ctx->lcg_on ? ctx->lcg.p : (const ulonglong2 *)nullptr, ctx->lcg2.p, ctx->vaf_on ? ctx->vaf.p : (const VafRec *)nullptr, ctx->vaf2.p);
       }
       if (ctx->lcg_on) std::swap(ctx->lcg, ctx->lcg2);
+      if (ctx->vaf_on) std::swap(ctx->vaf, ctx->vaf2);
       std::swap(ctx->pos, ctx->pos2); std::swap(ctx->vx, ctx->vx2); std::swap(ctx->vy, ctx->vy2); std::swap(ctx->vz, ctx->vz2);
       std::swap(ctx->species, ctx->species2); std::swap(ctx->group, ctx->group2); std::swap(ctx->gid, ctx->gid2); std::swap(ctx->orig, ctx->orig2);
    }
    if (narr > 0)
       hipLaunchKernelGGL(k_unpack_mig, dim3(cdiv(narr, 256)), dim3(256), 0, st, narr, nkeep, ctx->mig_in.p, ctx->pos.p, ctx->vx.p, ctx->vy.p, ctx->vz.p,
-                         ctx->gid.p, ctx->species.p, ctx->group.p, ctx->orig.p, ctx->lcg_on ? ctx->lcg.p : (ulonglong2 *)nullptr);
+                         ctx->gid.p, ctx->species.p, ctx->group.p, ctx->orig.p, ctx->lcg_on ? ctx->lcg.p : (ulonglong2 *)nullptr,
+                         ctx->vaf_on ? ctx->vaf.p : (VafRec *)nullptr);
    ctx->nloc = nkeep + narr;
    n = ctx->nloc;
    ctx->sort_renumbers = true;      /* (the sort's first kernel numbers the beads: was a launch of its own) */
@@ -963,8 +985,8 @@ int ddcmi_mg_rebuild(ddcmi_ctx *ctx)
       int roff[27], acc = 0;
       for (int c = 0; c < 27; c++) { roff[c] = acc; acc += ctx->mig_rcnt[c]; }
       /* (between a count round and its data exchange only an allocation of a few MB can fail: that rank leaves the job, mg_fatal) */
-      if (ctx->mig_in.ensure((size_t)acc * 10 + 16)) return mg_fatal(ctx, DDCMI_ENOMEM, "device allocation for the arriving beads failed");
-      if ((rc = mg_xchg_data(ctx, ctx->mig_out.p, nullptr, ctx->mig_scnt, ctx->mig_cap, ctx->mig_in.p, roff, ctx->mig_rcnt, 10))) return rc;
+      if (ctx->mig_in.ensure((size_t)acc * mig_width(ctx) + 16)) return mg_fatal(ctx, DDCMI_ENOMEM, "device allocation for the arriving beads failed");
+      if ((rc = mg_xchg_data(ctx, ctx->mig_out.p, nullptr, ctx->mig_scnt, ctx->mig_cap, ctx->mig_in.p, roff, ctx->mig_rcnt, mig_width(ctx)))) return rc;
    }
    ctx->phase(2, "mg migration exchange");
    lrc = mg_phase2_migrate_in(ctx);
@@ -1145,7 +1167,7 @@ static int group_rebuild(ddcmi_group *g)
          B->mig_rcnt[code] = mg_remote(B, mg_opp(code)) ? g->ranks[B->dir_dest[mg_opp(code)]]->mig_scnt[code] : 0;
          acc += B->mig_rcnt[code];
       }
-      if (B->mig_in.ensure((size_t)acc * 10 + 16)) SETERR(B, DDCMI_ENOMEM, "migration buffer");
+      if (B->mig_in.ensure((size_t)acc * mig_width(B) + 16)) SETERR(B, DDCMI_ENOMEM, "migration buffer");
    }
    if ((rc = mg_xchg_data_local(g, 0))) return rc;
    for (ddcmi_ctx *c : g->ranks) if ((rc = mg_phase2_migrate_in(c))) return rc;

@@ -84,14 +84,16 @@ int ddcmi_bl_sort_owned(ddcmi_ctx *ctx)
          hipLaunchKernelGGL(k_sort_cells, dim3(ncb), dim3(256), 0, st, ncell, ctx->cell_start_o.p, ctx->cell_cnt_o.p, ctx->order.p);
       /* caller index -> slot: a scattered store per bead, kept up only where something reads it every step */
       if (ctx->lcg_on) ENSURE(ctx, ctx->lcg2, (size_t)n + 1);
+      if (ctx->vaf_on) ENSURE(ctx, ctx->vaf2, (size_t)n + 1);
       const bool slots = (!ctx->bonded_gid && ctx->inc_nrow > 0) || (!ctx->cons_gid && ctx->ncgroup > 0) || (!ctx->mol_gid && ctx->nmol_multi > 0);
       hipLaunchKernelGGL(k_gather_state, dim3(nb), dim3(256), 0, st, n, ctx->order.p, ctx->pos.p, ctx->vx.p, ctx->vy.p, ctx->vz.p,
                          ctx->species.p, ctx->group.p, ctx->gid.p, ctx->orig.p,
                          ctx->pos2.p, ctx->vx2.p, ctx->vy2.p, ctx->vz2.p, ctx->species2.p, ctx->group2.p, ctx->gid2.p, ctx->orig2.p,
                          slots ? ctx->slot_of_orig.p : (int *)nullptr,
                          gp, (ctx->nranks == 1 && !ctx->loopback && !ctx->group_) ? ctx->nimg.p : (int *)nullptr, 1,
-                         ctx->lcg_on ? ctx->lcg.p : (const ulonglong2 *)nullptr, ctx->lcg2.p);
+                         ctx->lcg_on ? ctx->lcg.p : (const ulonglong2 *)nullptr, ctx->lcg2.p, ctx->vaf_on ? ctx->vaf.p : (const VafRec *)nullptr, ctx->vaf2.p);
       if (ctx->lcg_on) std::swap(ctx->lcg, ctx->lcg2);
+      if (ctx->vaf_on) std::swap(ctx->vaf, ctx->vaf2);
       ctx->slot_valid = slots;
       std::swap(ctx->pos, ctx->pos2); std::swap(ctx->vx, ctx->vx2); std::swap(ctx->vy, ctx->vy2); std::swap(ctx->vz, ctx->vz2);
       std::swap(ctx->species, ctx->species2); std::swap(ctx->group, ctx->group2); std::swap(ctx->gid, ctx->gid2); std::swap(ctx->orig, ctx->orig2);

@@ -482,6 +482,9 @@ static int step_pre_b(ddcmi_ctx *ctx, double dt)
          ctx->gp.L[a] = ctx->h[4 * a];
       }
    }
+   if (ctx->vaf_on && n > 0 && (lam.scale[0] != 1.0 || lam.scale[1] != 1.0 || lam.scale[2] != 1.0))
+      /* the scaling is no displacement (scalePositionsByBoxChange leaves v0[].r alone): the origins move by what it moves the beads */
+      hipLaunchKernelGGL(k_vaf_rescale, dim3(nb), dim3(256), 0, ctx->stream, n, lam.scale[0], lam.scale[1], lam.scale[2], ctx->pos.p, ctx->vaf.p);
    if (ctx->ncgroup > 0 && ctx->nhalo > 0 && (lam.scale[0] != 1.0 || lam.scale[1] != 1.0 || lam.scale[2] != 1.0))
       /* the FRONT solve reads the (scaled) positions of partners that are image / halo beads: adjustPosn for them too (an image
        * r + L goes to lambda r + lambda L, its place in the scaled box); the position halo after the drift replaces them */

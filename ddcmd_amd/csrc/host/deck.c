@@ -548,6 +548,7 @@ ddcmi_setup *ddcmi_deck_load_with(const char *object_file, const char *restart_f
          s->an_type = calloc(na, sizeof(int)); s->an_eval_rate = calloc(na, sizeof(int)); s->an_outputrate = calloc(na, sizeof(int));
          s->pc_nbins = calloc(na, sizeof(int)); s->pc_log = calloc(na, sizeof(int)); s->pc_method = calloc(na, sizeof(int));
          s->pc_rmin = calloc(na, sizeof(double)); s->pc_delta_r = calloc(na, sizeof(double));
+         s->vaf_filename = calloc(na, sizeof(char *)); s->vaf_length = calloc(na, sizeof(int));
          int bad = 0;
          char msg[512] = "";
          for (int a = 0; a < na; a++)
@@ -558,6 +559,15 @@ ddcmi_setup *ddcmi_deck_load_with(const char *object_file, const char *restart_f
             s->an_typename[a] = get_string(ao, "type", "NONE");
             object_get(ao, "eval_rate", &s->an_eval_rate[a], INT, 1, "0");
             object_get(ao, "outputrate", &s->an_outputrate[a], INT, 1, "0");
+            if (strncasecmp(s->an_typename[a], "VELOCITYAUTOCORRELATION", strlen("VELOCITYAUTOCORRELATION")) == 0)
+            {
+               /* velocityAutocorrelation_parms (velocityAutocorrelation.c:59-60), the prefix match of analysis.c:178 */
+               s->an_type[a] = 2;
+               s->vaf_filename[a] = get_string(ao, "filename", "vaf.dat");
+               object_get(ao, "length", &s->vaf_length[a], INT, 1, "1");
+               if (s->vaf_length[a] < 1) { snprintf(msg, sizeof(msg), "ANALYSIS %s: length = %d", s->an_name[a], s->vaf_length[a]); bad = 1; }
+               continue;
+            }
             if (strncasecmp(s->an_typename[a], "PAIRCORRELATION", strlen("PAIRCORRELATION")) != 0) continue;
             s->an_type[a] = 1;
             s->pc_filename[a] = get_string(ao, "filename", "paircorrelation.dat");
@@ -1097,9 +1107,10 @@ void ddcmi_setup_free(ddcmi_setup *s)
    free(s->integrator_type); free(s->accelerator_type);
    free(s->u_energyflux);
    free(s->random_name); free(s->lcg_state); free(s->lcg_multID); free(s->lcg_prime);
-   for (int a = 0; a < s->nanalysis; a++) { free(s->an_name[a]); free(s->an_typename[a]); free(s->pc_filename[a]); }
+   for (int a = 0; a < s->nanalysis; a++) { free(s->an_name[a]); free(s->an_typename[a]); free(s->pc_filename[a]); free(s->vaf_filename[a]); }
    free(s->an_name); free(s->an_typename); free(s->pc_filename); free(s->an_type); free(s->an_eval_rate); free(s->an_outputrate);
    free(s->pc_nbins); free(s->pc_log); free(s->pc_method); free(s->pc_rmin); free(s->pc_delta_r);
+   free(s->vaf_filename); free(s->vaf_length);
    free(s->u_pressure); free(s->u_volume); free(s->u_temperature); free(s->u_energy); free(s->u_time); free(s->u_length);
    free(s);
 }

@@ -104,13 +104,16 @@ typedef struct ddcmi_setup
    uint32_t *lcg_multID, *lcg_prime;
    double *group_vcm;      /* [3 ngroup] LANGEVIN groups: `vcm` (langevin.c:167), internal units; zero otherwise */
    /* SIMULATE analysis = name ... (analysis.c:120-160): every ANALYSIS object in the list, in list order.  an_type: 1 PAIRCORRELATION
-    * (paircorrelation.c:68-135; the pc_* fields), 0 any other type (not supported: the driver names it once on stderr) */
+    * (paircorrelation.c:68-135; the pc_* fields), 2 VELOCITYAUTOCORRELATION (velocityAutocorrelation.c:59-60; the vaf_* fields),
+    * 0 any other type (not supported: the driver names it once on stderr) */
    int nanalysis;
    char **an_name, **an_typename;
    int *an_type, *an_eval_rate, *an_outputrate;
    char **pc_filename;
    int *pc_nbins, *pc_log, *pc_method;        /* pc_method: 0 geom, 1 grid, 2 neighborList (all evaluated the same way: exactly) */
    double *pc_rmin, *pc_delta_r;              /* internal length units */
+   char **vaf_filename;
+   int *vaf_length;                           /* samples per window behind the origin (>= 1) */
 } ddcmi_setup;
 
 /* lcg64_default over n particles in order (lcg64.c:98-110, primes.c:35-63 with prime_init(30000, task, ntasks), ddcMD.c:70) */

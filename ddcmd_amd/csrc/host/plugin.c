@@ -1126,6 +1126,7 @@ static void analysis_init_all(SIMULATE *simulate)
    const int np = s->nspecies * (s->nspecies + 1) / 2;
    for (int a = 0; a < s->nanalysis; a++)
    {
+      if (s->an_type[a] == 2) continue;      /* VELOCITYAUTOCORRELATION: vaf_init_all */
       if (s->an_type[a] != 1)
       {
          if (par.rank == 0) fprintf(stderr, "ddcmi_md: ANALYSIS %s of type %s is not supported and is ignored\n", s->an_name[a], s->an_typename[a] ? s->an_typename[a] : "?");
@@ -1225,6 +1226,111 @@ static void analysis_free_all(void)
    free(pc_states); pc_states = NULL; pc_n = 0;
 }
 
+/* ANALYSIS type VELOCITYAUTOCORRELATION (velocityAutocorrelation.c: eval :117-229, output :230-327): the state machine of the
+ * reference -- last, nsample, vaf0 / msd0 of the current window, vaf_ / msd_ accumulated over the windows -- over the device's sums
+ * (ddcmi_vaf_origin / ddcmi_vaf_sample).  Every class is kept ([1 + ngroup + nspecies] blocks of length + 1); the output leaves out
+ * the group block of a single group and the species block of a single species, as the reference does.  The sums over the ranks go
+ * by ddcmi_rdzv_allreduce_f64, in rank order.  A restart begins with a fresh origin (last = 0). */
+typedef struct { int a, last, nsample, ncl, len; double *vaf0, *msd0, *vaf_, *msd_, *buf; } VAFSTATE;
+static VAFSTATE *vaf_states = NULL;
+static int vaf_n = 0;
+static void vaf_init_all(SIMULATE *simulate)
+{
+   const ddcmi_setup *s = simulate->setup;
+   vaf_n = 0;
+   vaf_states = s->nanalysis > 0 ? calloc(s->nanalysis, sizeof(VAFSTATE)) : NULL;
+   for (int a = 0; a < s->nanalysis; a++)
+   {
+      if (s->an_type[a] != 2) continue;
+      VAFSTATE *p = &vaf_states[vaf_n++];
+      p->a = a; p->len = s->vaf_length[a]; p->ncl = 1 + (s->ngroup > 0 ? s->ngroup : 1) + s->nspecies;
+      const size_t tot = (size_t)p->ncl * (p->len + 1);
+      p->vaf0 = calloc(tot, sizeof(double)); p->msd0 = calloc(tot, sizeof(double));
+      p->vaf_ = calloc(tot, sizeof(double)); p->msd_ = calloc(tot, sizeof(double)); p->buf = calloc(2 * (size_t)p->ncl, sizeof(double));
+      if (!p->vaf0 || !p->msd0 || !p->vaf_ || !p->msd_ || !p->buf) die("analysis", "out of memory");
+   }
+}
+/* sample k of the current window: the global sums of every class */
+static void vaf_take(SIMULATE *simulate, VAFSTATE *p, int k)
+{
+   const ddcmi_setup *s = simulate->setup;
+   ddcmi_ctx *ctx = simulate->accelerator->parms;
+   if (ddcmi_vaf_sample(ctx, s->ngroup > 0 ? s->ngroup : 1, s->nspecies, p->buf, p->buf + p->ncl) != DDCMI_OK) die("velocityAutocorrelation_eval", ddcmi_last_error(ctx));
+   if (par.world > 1 && ddcmi_rdzv_allreduce_f64(par.rdzv, p->buf, 2 * p->ncl, 0) != DDCMI_OK) die("velocityAutocorrelation_eval", ddcmi_rdzv_last_error(par.rdzv));
+   for (int c = 0; c < p->ncl; c++) { p->vaf0[k + c * (p->len + 1)] = p->buf[c]; p->msd0[k + c * (p->len + 1)] = p->buf[p->ncl + c]; }
+}
+static void vaf_eval(SIMULATE *simulate, VAFSTATE *p)
+{
+   ddcmi_ctx *ctx = simulate->accelerator->parms;
+   const size_t tot = (size_t)p->ncl * (p->len + 1);
+   int k = p->last;
+   if (k > 0) vaf_take(simulate, p, k);
+   if (k == p->len)
+   {
+      p->nsample++;
+      for (size_t l = 0; l < tot; l++) { p->msd_[l] += p->msd0[l]; p->vaf_[l] += p->vaf0[l]; p->msd0[l] = 0.0; p->vaf0[l] = 0.0; }
+      k = p->last = 0;
+   }
+   if (k == 0)
+   {
+      if (ddcmi_vaf_origin(ctx) != DDCMI_OK) die("velocityAutocorrelation_eval", ddcmi_last_error(ctx));
+      vaf_take(simulate, p, 0);      /* sum v.v, and zero */
+   }
+   p->last++;
+}
+static void vaf_output(SIMULATE *simulate, VAFSTATE *p)
+{
+   const ddcmi_setup *s = simulate->setup;
+   const int a = p->a, len = p->len, eval_rate = s->an_eval_rate[a], outputrate = s->an_outputrate[a];
+   if ((long long)p->nsample * len * eval_rate != outputrate) return;      /* (no file, no reset) */
+   const int ng = s->ngroup > 0 ? s->ngroup : 1, ngroups = ng == 1 ? 0 : ng, nspecies = s->nspecies == 1 ? 0 : s->nspecies;
+   if (par.rank == 0)
+   {
+      char dir[512], path[1100];
+      snprintf(dir, sizeof(dir), "snapshot.%012" PRId64, simulate->loop);
+      if (mkdir(dir, 0777) != 0 && errno != EEXIST) die("velocityAutocorrelation_output", "cannot create the snapshot directory");
+      snprintf(path, sizeof(path), "%s/%s", dir, s->vaf_filename[a]);
+      FILE *f = fopen(path, "w");
+      if (!f) die("velocityAutocorrelation_output", "cannot open the output file");
+      /* member counts of the whole system (sys->group[ii]->nMember, species likewise) */
+      double *ngm = calloc(ng, sizeof(double)), *nsm = calloc(s->nspecies, sizeof(double));
+      for (int i = 0; i < s->natoms; i++) { ngm[s->group ? s->group[i] : 0] += 1.0; nsm[s->species[i]] += 1.0; }
+      const double nglobal = (double)simulate->system->nglobal;
+      const double time_convert = units_convert(1.0, NULL, "t"), v2_convert = units_convert(1.0, NULL, "velocity^2"), r2_convert = units_convert(1.0, NULL, "l^2");
+      fprintf(f, "%-33s", "#time (fs)  System vaf MSD");
+      for (int ii = 0; ii < ngroups; ii++) { char temp[300]; snprintf(temp, sizeof(temp), "  Group %s vaf MSD", s->group_name[ii]); fprintf(f, "%-26s", temp); }
+      for (int ii = 0; ii < nspecies; ii++) { char temp[300]; snprintf(temp, sizeof(temp), "  Species %s vaf MSD", s->species_name[ii]); fprintf(f, "%-26s", temp); }
+      fprintf(f, " (vaf in Ang^2/fs^2; msd in Ang^2)\n");
+      for (int k = 0; k <= len; k++)
+      {
+         const double time = time_convert * k * simulate->dt * eval_rate;
+         fprintf(f, "%f", time);
+         fprintf(f, " %e %e", (v2_convert * p->vaf_[k] / p->nsample) / nglobal, (r2_convert * p->msd_[k] / p->nsample) / nglobal);
+         for (int ii = 0; ii < ngroups; ii++)
+         {
+            const int off = (1 + ii) * (len + 1);
+            fprintf(f, " %e %e", (v2_convert * p->vaf_[k + off] / p->nsample) / ngm[ii], (r2_convert * p->msd_[k + off] / p->nsample) / ngm[ii]);
+         }
+         for (int ii = 0; ii < nspecies; ii++)
+         {
+            const int off = (1 + ng + ii) * (len + 1);
+            fprintf(f, " %e %e", (v2_convert * p->vaf_[k + off] / p->nsample) / nsm[ii], (r2_convert * p->msd_[k + off] / p->nsample) / nsm[ii]);
+         }
+         fprintf(f, "\n");
+      }
+      fclose(f);
+      free(ngm); free(nsm);
+   }
+   memset(p->vaf_, 0, sizeof(double) * (size_t)p->ncl * (len + 1));
+   memset(p->msd_, 0, sizeof(double) * (size_t)p->ncl * (len + 1));
+   p->nsample = 0;
+}
+static void vaf_free_all(void)
+{
+   for (int k = 0; k < vaf_n; k++) { free(vaf_states[k].vaf0); free(vaf_states[k].msd0); free(vaf_states[k].vaf_); free(vaf_states[k].msd_); free(vaf_states[k].buf); }
+   free(vaf_states); vaf_states = NULL; vaf_n = 0;
+}
+
 /* simulateMaster, masters.c:369-559: firstEnergyCall, then batches of steps up to
  * the next print step (findEndLoop :263-281), energies after each batch */
 int simulateMaster(SIMULATE *simulate, const char *datafile_path)
@@ -1252,6 +1358,9 @@ int simulateMaster(SIMULATE *simulate, const char *datafile_path)
       if (pc_due(simulate->setup->an_eval_rate[pc_states[k].a], simulate->loop)) pc_eval(simulate, &pc_states[k]);
       pc_clear(simulate->setup, &pc_states[k]);
    }
+   vaf_init_all(simulate);
+   for (int k = 0; k < vaf_n; k++)                                /* its clear is analysis_NULL: the startup evaluation stays and sets the first origin */
+      if (pc_due(simulate->setup->an_eval_rate[vaf_states[k].a], simulate->loop)) vaf_eval(simulate, &vaf_states[k]);
    while (simulate->loop < simulate->maxloop)
    {
       int64_t endLoop = (simulate->loop / simulate->printrate + 1) * simulate->printrate;
@@ -1268,6 +1377,12 @@ int simulateMaster(SIMULATE *simulate, const char *datafile_path)
       for (int k = 0; k < pc_n; k++)                              /* findEndLoop, masters.c:277-282: the analyses' eval and output rates */
       {
          const int r[2] = {simulate->setup->an_eval_rate[pc_states[k].a], simulate->setup->an_outputrate[pc_states[k].a]};
+         for (int q = 0; q < 2; q++)
+            if (r[q] > 0) { int64_t nx = (simulate->loop / r[q] + 1) * r[q]; if (nx < endLoop) endLoop = nx; }
+      }
+      for (int k = 0; k < vaf_n; k++)
+      {
+         const int r[2] = {simulate->setup->an_eval_rate[vaf_states[k].a], simulate->setup->an_outputrate[vaf_states[k].a]};
          for (int q = 0; q < 2; q++)
             if (r[q] > 0) { int64_t nx = (simulate->loop / r[q] + 1) * r[q]; if (nx < endLoop) endLoop = nx; }
       }
@@ -1309,10 +1424,17 @@ int simulateMaster(SIMULATE *simulate, const char *datafile_path)
          if (pc_due(simulate->setup->an_eval_rate[a], simulate->loop)) pc_eval(simulate, &pc_states[k]);
          if (pc_due(simulate->setup->an_outputrate[a], simulate->loop)) pc_output(simulate, &pc_states[k]);
       }
+      for (int k = 0; k < vaf_n; k++)
+      {
+         const int a = vaf_states[k].a;
+         if (pc_due(simulate->setup->an_eval_rate[a], simulate->loop)) vaf_eval(simulate, &vaf_states[k]);
+         if (pc_due(simulate->setup->an_outputrate[a], simulate->loop)) vaf_output(simulate, &vaf_states[k]);
+      }
       if (!ck && simulate->snapshotrate > 0 && simulate->loop % simulate->snapshotrate == 0)    /* doSnapshot, masters.c:340-352: the particle files, no ./restart */
       { if (writeRestart(simulate, NULL, 0) != 0) die("simulateMaster", "snapshot write failed"); }
    }
    analysis_free_all();
+   vaf_free_all();
    sendHostState(sys);
    if (simulate->datafile) fclose(simulate->datafile);
    simulate->datafile = NULL;

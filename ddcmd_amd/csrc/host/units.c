@@ -85,6 +85,8 @@ static int eval_expr(const char *s, double *factor, int dim[NDIM])
          static const char *dimnames[NDIM] = {"l", "m", "t", "i", "T"};
          for (int d = 0; d < NDIM; d++)
             if (strcmp(sym, dimnames[d]) == 0) { f = external_si[d]; dm[d] = 1; found = 1; }
+         if (!found && strcmp(sym, "velocity") == 0)      /* the external velocity, l/t (velocityAutocorrelation.c:258 asks for velocity^2) */
+         { f = external_si[0] / external_si[2]; dm[0] = 1; dm[2] = -1; found = 1; }
          if (!found)
             for (const unit_symbol *u = table; u->name; u++)
                if (strcmp(sym, u->name) == 0) { f = u->si; memcpy(dm, u->dim, sizeof(dm)); found = 1; break; }

@@ -101,6 +101,9 @@ def _declare(lib):
     lib.ddcmi_domain_bounds.argtypes = [vp, _dp, _dp]
     lib.ddcmi_download_particles.argtypes = [vp, ctypes.c_int, _ip, _up, _ip] + [_dp] * 9
     lib.ddcmi_pair_correlation.argtypes = [vp, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int, _lp, _lp]
+    lib.ddcmi_vaf_origin.argtypes = [vp]
+    lib.ddcmi_vaf_sample.argtypes = [vp, ctypes.c_int, ctypes.c_int, _dp, _dp]
+    lib.ddcmi_vaf_clear.argtypes = [vp]
     lib._ddcmi_declared = True
 
 
@@ -536,6 +539,22 @@ class MartiniHIP(object):
                                                   counts.ctypes.data_as(_lp), nbeads.ctypes.data_as(_lp)))
         return counts, nbeads
 
+    def vaf_origin(self):
+        """ANALYSIS VELOCITYAUTOCORRELATION: the current state becomes the time origin of every owned bead (ddcmi_vaf_origin)"""
+        self._chk(self.lib.ddcmi_vaf_origin(self.ctx))
+
+    def vaf_sample(self):
+        """(vaf[nclass], msd[nclass]) of this rank: sum v0.v and sum d.d in internal units for the system, every group, every
+        species -- class 0, 1 + g, 1 + ngroup + s (ddcmi_vaf_sample)"""
+        ng, ns = max(1, int(self.s.ngroup)), int(self.s.nspecies)
+        vaf, msd = np.zeros(1 + ng + ns), np.zeros(1 + ng + ns)
+        self._chk(self.lib.ddcmi_vaf_sample(self.ctx, ng, ns, _d(vaf), _d(msd)))
+        return vaf, msd
+
+    def vaf_clear(self):
+        """tracking off, the reference records released (ddcmi_vaf_clear)"""
+        self._chk(self.lib.ddcmi_vaf_clear(self.ctx))
+
     def download(self, mask=POS | VEL | FORCE):
         n = self.n
         out = [np.zeros(n) for _ in range(9)]
@@ -622,6 +641,9 @@ def _declare_domains(lib):
     lib.ddcmi_group_step_nglf.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_double, ctypes.c_int]
     lib.ddcmi_group_temperatures_all.argtypes = [ctypes.POINTER(vp), ctypes.c_int, _dp]
     lib.ddcmi_group_pair_correlation.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int, _lp, _lp]
+    lib.ddcmi_group_vaf_origin.argtypes = [ctypes.POINTER(vp), ctypes.c_int]
+    lib.ddcmi_group_vaf_clear.argtypes = [ctypes.POINTER(vp), ctypes.c_int]
+    lib.ddcmi_group_vaf_sample.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp]
     lib._ddcmi_dom_declared = True
 
 
@@ -772,6 +794,27 @@ class MartiniGroup(object):
         if per_rank:
             return counts, nbeads
         return counts.sum(axis=0), nbeads.sum(axis=0)
+
+    def vaf_origin(self):
+        """ddcmi_group_vaf_origin: the time origin of every domain's beads"""
+        self._chk(self.lib.ddcmi_group_vaf_origin(self.arr, self.n))
+
+    def vaf_clear(self):
+        """ddcmi_group_vaf_clear: tracking off on every domain"""
+        self._chk(self.lib.ddcmi_group_vaf_clear(self.arr, self.n))
+
+    def vaf_sample(self, per_rank=False):
+        """ddcmi_group_vaf_sample: the domains' (vaf, msd) summed in rank order -- or, per_rank, stacked [rank, class]"""
+        ng, ns = max(1, int(self.s.ngroup)), int(self.s.nspecies)
+        vaf, msd = np.zeros((self.n, 1 + ng + ns)), np.zeros((self.n, 1 + ng + ns))
+        self._chk(self.lib.ddcmi_group_vaf_sample(self.arr, self.n, ng, ns, _d(vaf), _d(msd)))
+        if per_rank:
+            return vaf, msd
+        tv, tm = vaf[0].copy(), msd[0].copy()
+        for r in range(1, self.n):
+            tv += vaf[r]
+            tm += msd[r]
+        return tv, tm
 
     def energies(self):
         """sum over ranks = energyInfo.c allreduce()"""

@@ -241,6 +241,24 @@ int ddcmi_sync(ddcmi_ctx *ctx);
  * the current positions (those ddcmi_download_state returns) and changes nothing of the run. [sync] */
 int ddcmi_pair_correlation(ddcmi_ctx *ctx, double rmin, double delta_r, int nbins, int log_scale,
                            int nspecies, int64_t *counts, int64_t *nbeads);
+/* ANALYSIS VELOCITYAUTOCORRELATION (velocityAutocorrelation.c) on the device.  Every owned bead carries a reference record -- its
+ * velocity at the time origin and its displacement since, the sum of the drift moves dt*v (the reference's REF {r, v},
+ * velocityAutocorrelation.c:30, kept up in nglf.c:79-86): wraps into the box and the barostat's scaling do not count, and the
+ * record follows its bead through rebuilds and migration between ranks.  Off until the first origin; with it off nothing of a
+ * run differs.  ddcmi_upload_state drops the records.
+ * ddcmi_vaf_origin (velocityAutocorrelation.c:193-199): the current state becomes the time origin of every owned bead, v0 = v,
+ * d = 0; switches tracking on.  On a decomposed run every rank calls it at the same point of the run. */
+int ddcmi_vaf_origin(ddcmi_ctx *ctx);
+/* velocityAutocorrelation_eval's sums (velocityAutocorrelation.c:152-179) over this rank's beads, in internal units:
+ * vaf[c] = sum v0.v, msd[c] = sum d.d for class c = 0 the system, 1 + g group g, 1 + ngroup + s species s ([1 + ngroup + nspecies]
+ * each; the reference's "a single group / species has no block" rule is the output's).  ngroup and nspecies must be the
+ * context's.  Sums over ranks are the global sums; no communication.  Right after an origin: sum v.v and exactly 0.  Refused
+ * without an origin.  Two identical runs give identical bits.  Changes nothing of the run. [sync] */
+int ddcmi_vaf_sample(ddcmi_ctx *ctx, int ngroup, int nspecies, double *vaf, double *msd);
+/* tracking off, the records released (the reference has no counterpart: its v0 lives as long as the analysis).  On a decomposed
+ * run every rank calls it at the same point of the run, as with the origin: the migration records carry the reference record
+ * while tracking is on, and sender and receiver must agree on that. */
+int ddcmi_vaf_clear(ddcmi_ctx *ctx);
 
 /* ---- introspection / measurement ------------------------------------------- */
 /* list statistics of the last build: stats[0]=stored full-list entries,

@@ -45,6 +45,11 @@ int ddcmi_group_temperatures_all(ddcmi_ctx **ctxs, int n, double *Tgroup);
  * nbeads[r*nspecies ...] for domain r */
 int ddcmi_group_pair_correlation(ddcmi_ctx **ctxs, int n, double rmin, double delta_r, int nbins, int log_scale, int nspecies,
                                  int64_t *counts, int64_t *nbeads);
+/* ddcmi_vaf_origin / ddcmi_vaf_sample / ddcmi_vaf_clear for an in-process group: the origin (the clear) on every domain; every
+ * domain's own sums, domain after domain -- vaf[r*nclass ...], msd[r*nclass ...] for domain r, nclass = 1 + ngroup + nspecies */
+int ddcmi_group_vaf_origin(ddcmi_ctx **ctxs, int n);
+int ddcmi_group_vaf_clear(ddcmi_ctx **ctxs, int n);
+int ddcmi_group_vaf_sample(ddcmi_ctx **ctxs, int n, int ngroup, int nspecies, double *vaf, double *msd);
 /* the lean step (a single domain of FREE beads without bonded terms: one launch per step, the second stage of its energy / virial /
  * kinetic sums formed for all pending steps at once): the sums of the steps of the last such launch, 32 doubles per step --
  * {lj, ele, virial xx yy zz xy xz yz} as the full list counts them (twice), {rk, tion xx yy zz xy xz yz}, 0, the bonded kernels'

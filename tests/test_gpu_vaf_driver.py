@@ -1,0 +1,121 @@
+"""GPU tests (-m gpu) of ANALYSIS VELOCITYAUTOCORRELATION in the ddcmi_md driver: the startup evaluation sets the first origin, a
+sample at every eval, accumulate / re-origin / sample 0 on reaching length, snapshot.<loop>/vaf.dat as velocityAutocorrelation_output
+writes it (gate, header, the one-group / one-species rule, units, member counts) -- held against analysis.VelocityAutocorrelation fed
+by a Python run of the same deck."""
+import glob
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from ddcmd_amd.analysis import VelocityAutocorrelation, parse_vaf_output
+from ddcmd_amd.deck import load_deck, units_convert
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EXE = os.path.join(ROOT, "ddcmd_amd", "bin", "ddcmi_md")
+VAF = "vaf ANALYSIS { type = VELOCITYAUTOCORRELATION; eval_rate = 5; length = 4; outputrate = %d; }\n"
+SIM = "simulate SIMULATE { %sdeltaloop = 80; maxloop = 80; printrate = 5; snapshotrate = 100000; checkpointrate = 100000; }\n"
+
+
+def _copy(tmp_path, which, name):
+    d = tmp_path / name
+    shutil.copytree(os.path.join(ROOT, "tests", "golden", which), str(d))
+    return d
+
+
+def _run(cwd, extra, world=1):
+    args = ["-o", "object.data", "-d", "data", "-x", extra]
+    if world == 1:
+        out = subprocess.run([EXE] + args, capture_output=True, text=True, timeout=600, cwd=str(cwd))
+        assert out.returncode == 0, out.stdout + out.stderr
+        return out
+    env = dict(os.environ, WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", DDCMI_TRANSPORT="host", DDCMI_SINGLE_DEVICE="1",
+               DDCMI_RDZV_FILE=os.path.join(str(cwd), "rdzv_port"))
+    procs = [subprocess.Popen([EXE] + args, cwd=str(cwd), env=dict(env, RANK=str(r), LOCAL_RANK=str(r)), stdout=subprocess.PIPE,
+                              stderr=subprocess.PIPE, text=True) for r in range(world)]
+    outs = []
+    for p in procs:
+        try:
+            outs.append(p.communicate(timeout=600))
+        except subprocess.TimeoutExpired:
+            for q in procs:
+                q.kill()
+            raise
+        assert p.returncode == 0, outs[-1]
+    return outs
+
+
+def _python_files(deck, loops):
+    """the same run through the Python layer, in the driver's batches of five steps: {loop: text}"""
+    from ddcmd_amd.martini import MartiniHIP
+    s = load_deck(deck)
+    m = MartiniHIP(s, constraints=s.integrator_type.upper().startswith("NGLFCONSTRAINT") and s.nresicons > 0)
+    m.eval_forces()
+    m.group_temperatures()
+    an = VelocityAutocorrelation(s.ngroup, s.nspecies, length=4, eval_rate=5, outputrate=40)
+    gc, sc = np.bincount(s.group, minlength=max(1, s.ngroup)), np.bincount(s.species, minlength=s.nspecies)
+    an.eval(m.vaf_sample, m.vaf_origin)
+    out = {}
+    for loop in range(5, max(loops) + 1, 5):
+        m.step(5)
+        m.energies()
+        m.group_temperatures()
+        an.eval(m.vaf_sample, m.vaf_origin)
+        if loop % 40 == 0:
+            out[loop] = an.output_text(s.dt, s.natoms, gc, sc, s.group_name, s.species_name)
+    m.close()
+    return s, out
+
+
+@pytest.mark.parametrize("which", ["water_deck", "lipid_deck"])
+def test_driver_writes_vaf_files(tmp_path, which):
+    d = _copy(tmp_path, which, "with")
+    _run(d, SIM % "analysis = vaf; " + VAF % 40)
+    d0 = _copy(tmp_path, which, "without")
+    _run(d0, SIM % "")
+    assert open(str(d / "data"), "rb").read() == open(str(d0 / "data"), "rb").read()      # the analysis changes nothing of the run
+    s, want = _python_files(str(d / "object.data"), (40, 80))
+    nblock = 1 + (s.ngroup if s.ngroup > 1 else 0) + (s.nspecies if s.nspecies > 1 else 0)
+    dt_fs = units_convert(s.dt, None, "fs")
+    for loop in (40, 80):
+        (path,) = glob.glob(str(d / ("snapshot.*%d" % loop) / "vaf.dat"))
+        txt = open(path).read()
+        labels, t, vaf, msd = parse_vaf_output(txt)
+        assert len(labels) == nblock and vaf.shape == (nblock, 5)
+        assert txt.splitlines()[0].startswith("%-33s" % "#time (fs)  System vaf MSD") and txt.splitlines()[0].endswith(" (vaf in Ang^2/fs^2; msd in Ang^2)")
+        if which == "water_deck":      # two groups, two species: a block each
+            assert labels == ["System"] + ["Group %s" % n for n in s.group_name] + ["Species %s" % n for n in s.species_name] and len(labels) == 5
+        else:                          # one group: no group columns, the species follow the system
+            assert s.ngroup == 1 and labels[1] == "Species %s" % s.species_name[0] and len(labels) == 1 + s.nspecies
+        assert np.allclose(t, np.arange(5) * dt_fs * 5, rtol=0, atol=1e-6)
+        assert np.all(msd[:, 0] == 0.0) and np.all(msd[0, 1:] > 0) and np.all(vaf[0, 0] > 0)
+        assert want[loop] is not None
+        lw, tw, vw, mw = parse_vaf_output(want[loop])
+        assert lw == labels
+        print(which, loop, np.abs(vaf - vw).max() / np.abs(vw).max(), np.abs(msd - mw).max() / np.abs(mw).max())
+        assert np.allclose(vaf, vw, rtol=2e-6, atol=2e-6 * np.abs(vw).max()) and np.allclose(msd, mw, rtol=2e-6, atol=0)
+
+
+def test_gate_shut_writes_no_file(tmp_path):
+    d = _copy(tmp_path, "water_deck", "gate")
+    _run(d, SIM % "analysis = vaf; " + VAF % 30)      # nsample * 4 * 5 is 20 at loop 30, 60 at loop 60: never the outputrate
+    assert glob.glob(str(d / "snapshot.*" / "vaf.dat")) == []
+
+
+def test_driver_two_ranks_write_the_same_file(tmp_path):
+    d1 = _copy(tmp_path, "water_deck", "one")
+    _run(d1, SIM % "analysis = vaf; " + VAF % 40)
+    d2 = _copy(tmp_path, "water_deck", "two")
+    _run(d2, SIM % "analysis = vaf; " + VAF % 40, world=2)
+    for loop in (40, 80):
+        (a,) = glob.glob(str(d1 / ("snapshot.*%d" % loop) / "vaf.dat"))
+        (b,) = glob.glob(str(d2 / ("snapshot.*%d" % loop) / "vaf.dat"))
+        ta, tb = open(a).read(), open(b).read()
+        la, t1, v1, m1 = parse_vaf_output(ta)
+        lb, t2, v2, m2 = parse_vaf_output(tb)
+        assert la == lb and np.array_equal(t1, t2)
+        # the ranks' sums are added in rank order: the digits %e prints agree unless a value sits on a rounding edge of its last digit
+        assert np.allclose(v1, v2, rtol=2e-6, atol=2e-6 * np.abs(v1).max()) and np.allclose(m1, m2, rtol=2e-6, atol=0)
