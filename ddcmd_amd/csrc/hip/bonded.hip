@@ -563,6 +563,7 @@ static int build_rows(ddcmi_ctx *ctx, int nbond, const int *bond_ij, const doubl
 {
    int rc;
    ctx->inc_nrow = 0; ctx->inc_light = 0; ctx->inc_lanes = 0; ctx->inc_hlanes = 0; ctx->inc_heavy = 0;
+   memset(ctx->inc_census, 0, sizeof(ctx->inc_census)); ctx->inc_tabl[0] = ctx->inc_tabl[1] = -1;
    ctx->nbond = nbond; ctx->nangle = nangle; ctx->ntors = ntors;
    if (nbond + nangle + ntors > 0)
    {
@@ -660,7 +661,7 @@ static int build_rows(ddcmi_ctx *ctx, int nbond, const int *bond_ij, const doubl
       for (int t = 0; t < ntors; t++) for (int r = 1; r < 4; r++) join(tors_ijkl[4 * t], tors_ijkl[4 * t + r]);
       /* the lanes and row patterns of one launch (PatSet): an atom's rows with the partners as differences of atom numbers.  Rows of kind A are
        * wA ints wide with relA atom numbers in front, rows of kind B four ints with relB */
-      struct HostPat { std::vector<int> desc, hdr, rowA, rowB; int nlanes = 0; };
+      struct HostPat { std::vector<int> desc, hdr, rowA, rowB; int nlanes = 0, npat = 0, nfill = 0, nnear = 0, wall = 0, wmixed = 0, wfar = 0; };
       auto make_patterns = [&](const std::vector<int> &atoms, const std::vector<int> &offA, const std::vector<int> &rowsA, int wA, int relA,
                                const std::vector<int> &offB, const std::vector<int> &rowsB, int relB)
       {
@@ -714,6 +715,21 @@ static int build_rows(ddcmi_ctx *ctx, int nbond, const int *bond_ij, const doubl
                if (near) hp.desc[2 * (size_t)l + 1] |= 1 << 30;
             }
          }
+         /* the census of these decisions (ddcmi_debug_bonded_layout): a wave is all near as the kernel sees it -- fillers carry the bit -- */
+         hp.npat = (int)seen.size();
+         for (int w0 = 0; w0 < hp.nlanes; w0 += 64)
+         {
+            int real = 0, nr = 0, all = 1;
+            for (int l = w0; l < std::min(w0 + 64, hp.nlanes); l++)
+            {
+               const bool nb = (hp.desc[2 * (size_t)l + 1] >> 30) & 1;
+               all &= nb;
+               if (hp.desc[2 * (size_t)l] >= nrow) { hp.nfill++; continue; }
+               real++; nr += nb;
+            }
+            hp.nnear += nr;
+            if (real > 0) { if (all) hp.wall++; else if (nr > 0) hp.wmixed++; else hp.wfar++; }
+         }
          hp.desc.push_back(nrow); hp.desc.push_back(1 << 30);
          hp.hdr.resize(hp.hdr.size() + 4, 0); hp.rowA.resize(hp.rowA.size() + 4, 0); hp.rowB.resize(hp.rowB.size() + 4, 0);      /* (the rows' read-ahead) */
          return hp;
@@ -753,6 +769,8 @@ static int build_rows(ddcmi_ctx *ctx, int nbond, const int *bond_ij, const doubl
          off[2] = put(par[q ? 1 : 0].data(), par[q ? 1 : 0].size() * sizeof(double));
          off[3] = put(par[q ? 2 : 1].data(), par[q ? 2 : 1].size() * sizeof(double));
          ctx->inc_tab_pieces[q] = (int)(tb.size() / 4);
+         const int cen[10] = {hp.nlanes, hp.nfill, hp.npat, ctx->inc_tab_pieces[q], (int)ids[q ? 1 : 0].size(), (int)ids[q ? 2 : 1].size(), hp.nnear, hp.wall, hp.wmixed, hp.wfar};
+         memcpy(ctx->inc_census[q], cen, sizeof(cen));
       }
       if ((rc = up(ctx, ctx->inc_boff, boff.data(), boff.size())) || (rc = up(ctx, ctx->inc_aoff, aoff.data(), aoff.size())) || (rc = up(ctx, ctx->inc_toff, toff.data(), toff.size())) ||
           (rc = up(ctx, ctx->inc_hatoms, hatoms.data(), hatoms.size())) || (rc = up(ctx, ctx->inc_latoms, latoms.data(), latoms.size())) || (rc = up(ctx, ctx->inc_haoff, haoff.data(), haoff.size())) || (rc = up(ctx, ctx->inc_harow, harow.data(), harow.size())) ||
@@ -882,6 +900,18 @@ extern "C" int ddcmi_set_restraints(ddcmi_ctx *ctx, int n, const uint64_t *gid, 
    return DDCMI_OK;
 }
 
+/* test aid (include/ddcmi_test.h): the layout build_rows() decided and the instantiations the last launch took */
+extern "C" int ddcmi_debug_bonded_layout(ddcmi_ctx *ctx, int out[2][12])
+{
+   if (!ctx || !out) return DDCMI_EINVAL;
+   for (int q = 0; q < 2; q++)
+   {
+      for (int k = 0; k < 10; k++) out[q][k] = ctx->inc_census[q][k];
+      out[q][10] = ctx->inc_tabl[q]; out[q][11] = 0;
+   }
+   return DDCMI_OK;
+}
+
 static GatherRows gather_rows(const ddcmi_ctx *ctx)
 {
    GatherRows gr = {ctx->inc_nrow, ctx->inc_boff.p, ctx->inc_aoff.p, ctx->inc_haoff.p, ctx->inc_toff.p, (const int2 *)ctx->inc_brow.p, (const int4 *)ctx->inc_arow.p,
@@ -965,14 +995,16 @@ int ddcmi_launch_bonded(ddcmi_ctx *ctx, double4 *fb, int lean_slot)
    }
    double *p2 = p1 + nblk;      /* the heavy launch's workgroups follow the light one's in every row */
    const double *hrecv = ctx->halo_in_recv ? ctx->hrecv3.p : nullptr;      /* (received beads: their current positions are in the receive buffer) */
-   static const bool no_lds_tab = getenv("DDCMI_NO_BONDED_LDS_TABLES") != nullptr;
+   const bool tabl_l = gr.lp.pieces <= GB_TAB_PIECES && !ctx->no_bonded_lds, tabl_h = gr.hp.pieces <= GB_TAB_PIECES && !ctx->no_bonded_lds;
    if (nblk > 0)
    {
-      auto kl = (gr.lp.pieces <= GB_TAB_PIECES && !no_lds_tab) ? k_bonded_gather<false, true> : k_bonded_gather<false, false>;
+      auto kl = tabl_l ? k_bonded_gather<false, true> : k_bonded_gather<false, false>;
+      ctx->inc_tabl[0] = tabl_l;
       hipLaunchKernelGGL(kl, dim3(nblk), dim3(256), 0, st, gr, slot, ctx->nloc, ctx->nloc + ctx->nhalo, box, ctx->excludePotentialTerm,
                          ctx->pos.p, ctx->fx.p, ctx->fy.p, ctx->fz.p, fb, p1, pstride, hrecv, ctx->halo_src.p);
    }
-   auto kh = (gr.hp.pieces <= GB_TAB_PIECES && !no_lds_tab) ? k_bonded_gather<true, true> : k_bonded_gather<true, false>;
+   auto kh = tabl_h ? k_bonded_gather<true, true> : k_bonded_gather<true, false>;
+   if (nblk2 > 0) ctx->inc_tabl[1] = tabl_h;
    if (nblk2 > 0)
       hipLaunchKernelGGL(kh, dim3(nblk2), dim3(256), 0, st, gr, slot, ctx->nloc, ctx->nloc + ctx->nhalo, box, ctx->excludePotentialTerm,
                          ctx->pos.p, ctx->fx.p, ctx->fy.p, ctx->fz.p, fb, p2, pstride, hrecv, ctx->halo_src.p);

@@ -511,6 +511,7 @@ extern "C" int ddcmi_create(ddcmi_ctx **out, int device)
    ctx->no_self_img = getenv("DDCMI_NO_SELF_IMAGES") != nullptr;
    ctx->no_direct_halo = getenv("DDCMI_NO_DIRECT_HALO") != nullptr;
    ctx->force_lvl = getenv("DDCMI_FORCE_LEVEL_TABLE") != nullptr;
+   ctx->no_bonded_lds = getenv("DDCMI_NO_BONDED_LDS_TABLES") != nullptr;
    /* test hook, armed only together with DDCMI_DEBUG_HOOKS=1 (a stray value alone does nothing; read per context: a test sets it between two of them) */
    ctx->debug_image_bound = (getenv("DDCMI_DEBUG_HOOKS") && getenv("DDCMI_DEBUG_IMAGE_BOUND")) ? atoi(getenv("DDCMI_DEBUG_IMAGE_BOUND")) : 0;
    /* (Rounds 3-5 registered the context itself with hipHostRegister, so that the two small count arrays inside it -- mig_scnt, hs_cnt: host

@@ -296,6 +296,10 @@ struct ddcmi_ctx
    /* rows of the bead-parallel bonded kernel (atom -> its terms), built once in ddcmi_set_bonded[_gid] */
    int idx_amax_cons = -1, idx_amax_mol = -1;      /* largest caller index the index-named constraint groups / molecule lists use: checked against the bead count at the rebuild */
    int inc_nrow = 0, inc_heavy = 0, inc_light = 0, inc_lanes = 0, inc_hlanes = 0; dbuf<int> inc_boff, inc_aoff, inc_haoff, inc_toff, inc_brow, inc_arow, inc_harow, inc_trow, inc_hatoms, inc_latoms, inc_ldesc, inc_hdesc, inc_tab, inc_htab; int inc_tab_pieces[2] = {0, 0}, inc_tab_off[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}; dbuf<double> inc_bpar, inc_apar, inc_tpar;
+   /* what build_rows() decided, per launch (light, heavy), for ddcmi_debug_bonded_layout (include/ddcmi_test.h): {lanes, filler lanes, patterns, table pieces, parameter
+    * sets of the A rows, of the B rows, real lanes with the near bit, waves all near, waves with near and far real lanes, waves with real lanes of which none is near};
+    * inc_tabl: the last launch took the instantiation with the tables in LDS (-1: not launched yet).  DDCMI_NO_BONDED_LDS_TABLES=1, read in ddcmi_create: never. */
+   int inc_census[2][10] = {{0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}}, inc_tabl[2] = {-1, -1}; bool no_bonded_lds = false;
    bool bonded_gid = false;
    int natom_g = 0; dbuf<uint64_t> atom_gid;      /* sorted gids of the atoms that occur in terms: an atom's number is its place here */
    dbuf<int> slot_of_atom;                         /* [natom_g] lowest slot holding that gid on this rank, INT_MAX if absent (refilled at rebuilds) */

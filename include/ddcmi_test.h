@@ -4,7 +4,8 @@
  * tests/ and tools/ load:
  *   ddcmi_group_*              in-process emulation of a px*py*pz decomposition on ONE GPU (the multi-domain path without RCCL)
  *   ddcmi_plan_*               the host logic of the halo exchange / domain directions, callable without a GPU (world-2 CPU tests)
- *   ddcmi_debug_branch_census  which rarely taken dihedral branches a test's geometry drives */
+ *   ddcmi_debug_branch_census  which rarely taken dihedral branches a test's geometry drives
+ *   ddcmi_debug_bonded_layout  what the bonded kernels' lane layout decided for a test's term lists */
 #ifndef DDCMI_TEST_H
 #define DDCMI_TEST_H
 #include "ddcmi.h"
@@ -16,6 +17,14 @@ extern "C" {
  * [4] improper series; [5] improper difference wrapped by 2 pi; [6] cos phi clamped.  Counted per evaluation (a term is
  * evaluated once per atom it has).  Test aid: shows that a test's geometry really drives those branches. [sync] */
 int ddcmi_debug_branch_census(unsigned long long out[8], int reset);
+/* census of the lane layout ddcmi_set_bonded / ddcmi_set_bonded_gid made of the term lists, out[0] the light launch (bonds, func 2/10 angles), out[1] the
+ * heavy one (func-1 angles, dihedrals): [0] lanes, [1] of these filler lanes (in front of a molecule's run that would straddle two workgroups), [2] row
+ * patterns, [3] 16-byte pieces of the launch's table (at most 384: copied to LDS), [4] [5] distinct parameter sets of its two term kinds, [6] atoms'
+ * lanes with the near bit (every partner a lane of the same workgroup at the distance of the atom numbers), waves of 64 lanes that hold an atom's
+ * lane and [7] are all near (the wave reads its partners' records unasked) / [8] hold near and far atoms' lanes / [9] hold no near one, [10] whether
+ * the context's last launch took the instantiation with the table in LDS (-1: none launched yet; DDCMI_NO_BONDED_LDS_TABLES=1 at ddcmi_create: never),
+ * [11] 0.  Host numbers, kept where the tables are made: no device counter.  Test aid: shows that a test's molecules really drive each path. */
+int ddcmi_debug_bonded_layout(ddcmi_ctx *ctx, int out[2][12]);
 /* Host logic of the halo exchange (ddcSendRecvTables, ddcSendRecv.c:126-225), callable without a GPU.
  * ddcmi_plan_recv_counts: from the all-gathered per-direction send counts all_counts[nranks][27], what
  * this rank receives: recv_cnt[c] = what the rank in my direction opp(c) sends along ITS direction c.
