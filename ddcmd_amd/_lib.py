@@ -82,6 +82,16 @@ c_u64_p = ctypes.POINTER(ctypes.c_uint64)
 c_char_pp = ctypes.POINTER(ctypes.c_char_p)
 
 
+AN_NONE, AN_PAIRCORRELATION, AN_VAF = range(3)      # enum ddcmi_analysis_kind
+
+
+class CAnalysis(ctypes.Structure):
+    """Mirror of struct ddcmi_analysis (ddcmd_amd/csrc/host/deck.h)."""
+    _fields_ = [("name", ctypes.c_char_p), ("type_name", ctypes.c_char_p), ("type", ctypes.c_int), ("eval_rate", ctypes.c_int), ("outputrate", ctypes.c_int),
+                ("filename", ctypes.c_char_p), ("length", ctypes.c_int),
+                ("rscale_log", ctypes.c_int), ("method", ctypes.c_int), ("rmin", ctypes.c_double), ("delta_r", ctypes.c_double)]
+
+
 class CSetup(ctypes.Structure):
     """Mirror of struct ddcmi_setup (ddcmd_amd/csrc/host/deck.h)."""
     _fields_ = [
@@ -140,13 +150,7 @@ class CSetup(ctypes.Structure):
         ("random_name", ctypes.c_char_p), ("random_lcg64", ctypes.c_int), ("lcg_from_file", ctypes.c_int),
         ("lcg_state", c_u64_p), ("lcg_multID", ctypes.POINTER(ctypes.c_uint32)), ("lcg_prime", ctypes.POINTER(ctypes.c_uint32)),
         ("group_vcm", c_double_p),
-        ("nanalysis", ctypes.c_int),
-        ("an_name", c_char_pp), ("an_typename", c_char_pp),
-        ("an_type", c_int_p), ("an_eval_rate", c_int_p), ("an_outputrate", c_int_p),
-        ("pc_filename", c_char_pp),
-        ("pc_nbins", c_int_p), ("pc_log", c_int_p), ("pc_method", c_int_p),
-        ("pc_rmin", c_double_p), ("pc_delta_r", c_double_p),
-        ("vaf_filename", c_char_pp), ("vaf_length", c_int_p),
+        ("nanalysis", ctypes.c_int), ("analysis", ctypes.POINTER(CAnalysis)),
     ]
 
 

@@ -1,0 +1,293 @@
+/* analysis.c -- see analysis.h: the supported ANALYSIS types, one row of `types` each, and the driver's walks over a deck's list. */
+#include "analysis.h"
+#include "units.h"
+#include <errno.h>
+#include <stdlib.h>
+#include <string.h>
+#include <strings.h>
+#include <math.h>
+#include <inttypes.h>
+#include <sys/stat.h>
+
+static int analysis_due(int rate, int64_t loop) { return rate > 0 && loop % rate == 0; }      /* TEST0 */
+/* snapshot.<loop>/<filename>, opened for writing (rank 0) */
+static FILE *snapshot_fopen(const SIMULATE *simulate, const char *filename, const char *where)
+{
+   char dir[512], path[1100];
+   snprintf(dir, sizeof(dir), "snapshot.%012" PRId64, simulate->loop);      /* CreateSnapshotdir: the directory writeRestart uses */
+   if (mkdir(dir, 0777) != 0 && errno != EEXIST) die(where, "cannot create the snapshot directory");
+   snprintf(path, sizeof(path), "%s/%s", dir, filename);
+   FILE *f = fopen(path, "w");
+   if (!f) die(where, "cannot open the output file");
+   return f;
+}
+static void sum_over_ranks(double *buf, int n, const char *where)      /* in rank order, the sum on every rank */
+{ if (par.world > 1 && ddcmi_rdzv_allreduce_f64(par.rdzv, buf, n, 0) != DDCMI_OK) die(where, ddcmi_rdzv_last_error(par.rdzv)); }
+static void *zalloc(size_t n, size_t size) { void *p = calloc(n, size); if (!p) die("analysis", "out of memory"); return p; }
+static void refuse_length(const ddcmi_analysis *an, char *msg, int msglen) { snprintf(msg, msglen, "ANALYSIS %s: length = %d", an->name, an->length); }
+
+/* ------------------------------------------------------------------------- */
+/* ANALYSIS type PAIRCORRELATION (paircorrelation.c: parms :68-135, eval_geom :354-457, output :460-520; analysis.c:133-153): the counts
+ * come from the device (ddcmi_pair_correlation), are summed over the ranks (integers below 2^53: the double sum is exact, so every rank
+ * count gives the same file) and accumulated on the host in the reference's order; rank 0 writes the file. */
+typedef struct { int nsample; double *g, *buf; int64_t *cnt, *nb; } PCSTATE;
+static void pc_parms(const OBJECT *obj, ddcmi_analysis *an, char *msg, int msglen)
+{
+   int bad = msg[0] != 0;      /* the two range checks at the end speak only in a list without a refusal so far */
+   char *m = NULL, *rs = NULL;
+   object_get(obj, "delta_r", &an->delta_r, WITH_UNITS, 1, "1", "l", NULL);
+   object_get(obj, "rmin", &an->rmin, WITH_UNITS, 1, "0", "l", NULL);
+   object_get(obj, "method", &m, STRING, 1, "geom");
+   object_get(obj, "rscale", &rs, STRING, 1, "normal");
+   const char *method = m ? m : "", *rscale = rs ? rs : "";      /* "key = ;": present and empty */
+   if (strcasecmp(method, "geom") == 0) an->method = 0;
+   else if (strcasecmp(method, "grid") == 0) an->method = 1;
+   else if (strcasecmp(method, "neighborList") == 0) an->method = 2;
+   else { snprintf(msg, msglen, "ANALYSIS %s: unrecognized method \"%s\"", an->name, method); bad = 1; }
+   if (strcasecmp(rscale, "normal") == 0) an->rscale_log = 0;
+   else if (strcasecmp(rscale, "log") == 0) an->rscale_log = 1;
+   else { snprintf(msg, msglen, "ANALYSIS %s: unrecognized rscale \"%s\"", an->name, rscale); bad = 1; }
+   if (!bad && an->rscale_log && !(an->rmin > 0.0)) { snprintf(msg, msglen, "ANALYSIS %s: rscale = log needs rmin > 0", an->name); bad = 1; }
+   if (!bad && an->length <= 0) refuse_length(an, msg, msglen);
+   free(m); free(rs);
+}
+static void *pc_init(SIMULATE *simulate, const ddcmi_analysis *an)
+{
+   const ddcmi_setup *s = simulate->setup;
+   const size_t nh = (size_t)(s->nspecies * (s->nspecies + 1) / 2) * an->length;
+   PCSTATE *p = zalloc(1, sizeof(PCSTATE));
+   p->g = zalloc(nh, sizeof(double)); p->buf = zalloc(nh + s->nspecies, sizeof(double));
+   p->cnt = zalloc(nh, sizeof(int64_t)); p->nb = zalloc(s->nspecies, sizeof(int64_t));
+   return p;
+}
+static void pc_clear(SIMULATE *simulate, const ddcmi_analysis *an, void *state)
+{
+   const ddcmi_setup *s = simulate->setup;
+   PCSTATE *p = state;
+   memset(p->g, 0, sizeof(double) * (size_t)(s->nspecies * (s->nspecies + 1) / 2) * an->length);
+   p->nsample = 0;
+}
+static int pc_combo(int i, int j, int ns) { int lo = i < j ? i : j, hi = i < j ? j : i; return (hi - lo) + ns * lo - (lo * (lo - 1)) / 2; }
+static void pc_eval(SIMULATE *simulate, const ddcmi_analysis *an, void *state)
+{
+   const ddcmi_setup *s = simulate->setup;
+   PCSTATE *p = state;
+   ddcmi_ctx *ctx = simulate->accelerator->parms;
+   const int ns = s->nspecies, nbins = an->length;
+   const size_t nh = (size_t)(ns * (ns + 1) / 2) * nbins;
+   if (ddcmi_pair_correlation(ctx, an->rmin, an->delta_r, nbins, an->rscale_log, ns, p->cnt, p->nb) != DDCMI_OK)
+      die("paircorrelation_eval", ddcmi_last_error(ctx));
+   for (size_t k = 0; k < nh; k++) p->buf[k] = (double)p->cnt[k];
+   for (int t = 0; t < ns; t++) p->buf[nh + t] = (double)p->nb[t];
+   sum_over_ranks(p->buf, (int)(nh + ns), "paircorrelation_eval");
+   p->nsample += 1;
+   for (int i = 0; i < ns; i++)
+      for (int j = i; j < ns; j++)
+      {
+         const int l = pc_combo(i, j, ns);
+         const double recipNiNj = 1.0 / (p->buf[nh + i] * p->buf[nh + j]);
+         for (int k = 0; k < nbins; k++) { double nBonds = p->buf[(size_t)l * nbins + k]; nBonds *= recipNiNj; p->g[(size_t)l * nbins + k] += nBonds; }
+      }
+}
+static void pc_output(SIMULATE *simulate, const ddcmi_analysis *an, void *state)
+{
+   const ddcmi_setup *s = simulate->setup;
+   PCSTATE *p = state;
+   ddcmi_ctx *ctx = simulate->accelerator->parms;
+   const int ns = s->nspecies, np = ns * (ns + 1) / 2, nbins = an->length;
+   if (p->nsample == 0) { pc_clear(simulate, an, p); return; }
+   if (par.rank == 0)
+   {
+      FILE *f = snapshot_fopen(simulate, an->filename, "paircorrelation_output");
+      double h[9];
+      if (ddcmi_get_box(ctx, h) != DDCMI_OK) die("paircorrelation_output", ddcmi_last_error(ctx));
+      const double volume = h[0] * h[4] * h[8], sc = volume / p->nsample;
+      const double rmin = an->rmin, dr = an->delta_r, rmax = rmin + nbins * dr;
+      const double logDelta = an->rscale_log ? (log10(rmax) - log10(rmin)) / (nbins * 1.0) : 0.0;
+      double *left = malloc(sizeof(double) * nbins), *right = malloc(sizeof(double) * nbins);
+      for (int k = 0; k < nbins; k++)
+      {
+         if (an->rscale_log) left[k] = pow(10, log10(rmin) + k * logDelta);
+         else { left[k] = rmin + k * dr; right[k] = rmin + (k + 1) * dr; }
+      }
+      if (an->rscale_log) { for (int k = 0; k + 1 < nbins; k++) right[k] = left[k + 1]; right[nbins - 1] = rmax; }
+      for (int k = 0; k < nbins; k++)
+      {
+         const double dv = 4.0 * M_PI / 3.0 * (right[k] * right[k] * right[k] - left[k] * left[k] * left[k]);
+         for (int l = 0; l < np; l++) p->g[k + (size_t)nbins * l] *= sc / dv;
+      }
+      fprintf(f, "# rmin = %f Ang; delta_r = %f Ang; length = %d; eval_rate = %d; outputrate = %d;\n", units_convert(rmin, NULL, "Angstrom"),
+              units_convert(dr, NULL, "Angstrom"), nbins, an->eval_rate, an->outputrate);
+      fprintf(f, "# nsample = %d;\n", p->nsample);
+      fprintf(f, "# r(Ang) ");
+      for (int l = 0; l < np; l++)
+      {
+         int ti = -1, tj = -1;
+         for (int i = 0; i < ns && ti < 0; i++) for (int j = i; j < ns; j++) if (pc_combo(i, j, ns) == l) { ti = i; tj = j; break; }      /* comboReverseIndex */
+         fprintf(f, "%s-%s ", s->species_name[ti], s->species_name[tj]);
+      }
+      fprintf(f, "\n");
+      for (int k = 0; k < nbins; k++)
+      {
+         fprintf(f, "%f ", units_convert(0.5 * (left[k] + right[k]), NULL, "Angstrom"));
+         for (int l = 0; l < np; l++) fprintf(f, "%e ", p->g[k + (size_t)nbins * l]);
+         fprintf(f, "\n");
+      }
+      fclose(f);
+      free(left); free(right);
+   }
+   pc_clear(simulate, an, p);
+}
+static void pc_free(void *state) { PCSTATE *p = state; free(p->g); free(p->buf); free(p->cnt); free(p->nb); free(p); }
+
+/* ANALYSIS type VELOCITYAUTOCORRELATION (velocityAutocorrelation.c: parms :59-60, eval :117-229, output :230-327): the state machine of
+ * the reference -- last, nsample, vaf0 / msd0 of the current window, vaf_ / msd_ accumulated over the windows -- over the device's sums
+ * (ddcmi_vaf_origin / ddcmi_vaf_sample).  Every class is kept ([1 + ngroup + nspecies] blocks of length + 1); the output leaves out
+ * the group block of a single group and the species block of a single species, as the reference does.  The sums over the ranks go
+ * by ddcmi_rdzv_allreduce_f64, in rank order.  A restart begins with a fresh origin (last = 0).  There is no clear: the startup
+ * evaluation stays and sets the first origin. */
+typedef struct { int last, nsample, ncl, len; double *vaf0, *msd0, *vaf_, *msd_, *buf; } VAFSTATE;
+static void vaf_parms(const OBJECT *obj, ddcmi_analysis *an, char *msg, int msglen) { (void)obj; if (an->length < 1) refuse_length(an, msg, msglen); }
+static void *vaf_init(SIMULATE *simulate, const ddcmi_analysis *an)
+{
+   const ddcmi_setup *s = simulate->setup;
+   VAFSTATE *p = zalloc(1, sizeof(VAFSTATE));
+   p->len = an->length; p->ncl = 1 + (s->ngroup > 0 ? s->ngroup : 1) + s->nspecies;
+   const size_t tot = (size_t)p->ncl * (p->len + 1);
+   p->vaf0 = zalloc(tot, sizeof(double)); p->msd0 = zalloc(tot, sizeof(double));
+   p->vaf_ = zalloc(tot, sizeof(double)); p->msd_ = zalloc(tot, sizeof(double)); p->buf = zalloc(2 * (size_t)p->ncl, sizeof(double));
+   return p;
+}
+/* sample k of the current window: the global sums of every class */
+static void vaf_take(SIMULATE *simulate, VAFSTATE *p, int k)
+{
+   const ddcmi_setup *s = simulate->setup;
+   ddcmi_ctx *ctx = simulate->accelerator->parms;
+   if (ddcmi_vaf_sample(ctx, s->ngroup > 0 ? s->ngroup : 1, s->nspecies, p->buf, p->buf + p->ncl) != DDCMI_OK) die("velocityAutocorrelation_eval", ddcmi_last_error(ctx));
+   sum_over_ranks(p->buf, 2 * p->ncl, "velocityAutocorrelation_eval");
+   for (int c = 0; c < p->ncl; c++) { p->vaf0[k + c * (p->len + 1)] = p->buf[c]; p->msd0[k + c * (p->len + 1)] = p->buf[p->ncl + c]; }
+}
+static void vaf_eval(SIMULATE *simulate, const ddcmi_analysis *an, void *state)
+{
+   (void)an;
+   VAFSTATE *p = state;
+   ddcmi_ctx *ctx = simulate->accelerator->parms;
+   const size_t tot = (size_t)p->ncl * (p->len + 1);
+   int k = p->last;
+   if (k > 0) vaf_take(simulate, p, k);
+   if (k == p->len)
+   {
+      p->nsample++;
+      for (size_t l = 0; l < tot; l++) { p->msd_[l] += p->msd0[l]; p->vaf_[l] += p->vaf0[l]; p->msd0[l] = 0.0; p->vaf0[l] = 0.0; }
+      k = p->last = 0;
+   }
+   if (k == 0)
+   {
+      if (ddcmi_vaf_origin(ctx) != DDCMI_OK) die("velocityAutocorrelation_eval", ddcmi_last_error(ctx));
+      vaf_take(simulate, p, 0);      /* sum v.v, and zero */
+   }
+   p->last++;
+}
+static void vaf_output(SIMULATE *simulate, const ddcmi_analysis *an, void *state)
+{
+   const ddcmi_setup *s = simulate->setup;
+   VAFSTATE *p = state;
+   const int len = p->len, eval_rate = an->eval_rate, outputrate = an->outputrate;
+   if ((long long)p->nsample * len * eval_rate != outputrate) return;      /* (no file, no reset) */
+   const int ng = s->ngroup > 0 ? s->ngroup : 1, ngroups = ng == 1 ? 0 : ng, nspecies = s->nspecies == 1 ? 0 : s->nspecies;
+   if (par.rank == 0)
+   {
+      FILE *f = snapshot_fopen(simulate, an->filename, "velocityAutocorrelation_output");
+      /* member counts of the whole system (sys->group[ii]->nMember, species likewise) */
+      double *ngm = calloc(ng, sizeof(double)), *nsm = calloc(s->nspecies, sizeof(double));
+      for (int i = 0; i < s->natoms; i++) { ngm[s->group ? s->group[i] : 0] += 1.0; nsm[s->species[i]] += 1.0; }
+      const double nglobal = (double)simulate->system->nglobal;
+      const double time_convert = units_convert(1.0, NULL, "t"), v2_convert = units_convert(1.0, NULL, "velocity^2"), r2_convert = units_convert(1.0, NULL, "l^2");
+      fprintf(f, "%-33s", "#time (fs)  System vaf MSD");
+      for (int ii = 0; ii < ngroups; ii++) { char temp[300]; snprintf(temp, sizeof(temp), "  Group %s vaf MSD", s->group_name[ii]); fprintf(f, "%-26s", temp); }
+      for (int ii = 0; ii < nspecies; ii++) { char temp[300]; snprintf(temp, sizeof(temp), "  Species %s vaf MSD", s->species_name[ii]); fprintf(f, "%-26s", temp); }
+      fprintf(f, " (vaf in Ang^2/fs^2; msd in Ang^2)\n");
+      for (int k = 0; k <= len; k++)
+      {
+         const double time = time_convert * k * simulate->dt * eval_rate;
+         fprintf(f, "%f", time);
+         fprintf(f, " %e %e", (v2_convert * p->vaf_[k] / p->nsample) / nglobal, (r2_convert * p->msd_[k] / p->nsample) / nglobal);
+         for (int ii = 0; ii < ngroups; ii++)
+         {
+            const int off = (1 + ii) * (len + 1);
+            fprintf(f, " %e %e", (v2_convert * p->vaf_[k + off] / p->nsample) / ngm[ii], (r2_convert * p->msd_[k + off] / p->nsample) / ngm[ii]);
+         }
+         for (int ii = 0; ii < nspecies; ii++)
+         {
+            const int off = (1 + ng + ii) * (len + 1);
+            fprintf(f, " %e %e", (v2_convert * p->vaf_[k + off] / p->nsample) / nsm[ii], (r2_convert * p->msd_[k + off] / p->nsample) / nsm[ii]);
+         }
+         fprintf(f, "\n");
+      }
+      fclose(f);
+      free(ngm); free(nsm);
+   }
+   memset(p->vaf_, 0, sizeof(double) * (size_t)p->ncl * (len + 1));
+   memset(p->msd_, 0, sizeof(double) * (size_t)p->ncl * (len + 1));
+   p->nsample = 0;
+}
+static void vaf_free(void *state) { VAFSTATE *p = state; free(p->vaf0); free(p->msd0); free(p->vaf_); free(p->msd_); free(p->buf); free(p); }
+
+/* ------------------------------------------------------------------------- */
+static const ANALYSIS_TYPE types[] = {      /* indexed by enum ddcmi_analysis_kind; DDCMI_AN_NONE has no row */
+   [DDCMI_AN_PAIRCORRELATION] = {"PAIRCORRELATION", DDCMI_AN_PAIRCORRELATION, "paircorrelation.dat", pc_parms, pc_init, pc_eval, pc_output, pc_clear, pc_free},
+   [DDCMI_AN_VAF] = {"VELOCITYAUTOCORRELATION", DDCMI_AN_VAF, "vaf.dat", vaf_parms, vaf_init, vaf_eval, vaf_output, NULL, vaf_free},
+};
+const ANALYSIS_TYPE *analysis_type_find(const char *type_name)
+{
+   for (size_t t = 1; t < sizeof(types) / sizeof(types[0]); t++) if (strncasecmp(type_name, types[t].prefix, strlen(types[t].prefix)) == 0) return &types[t];
+   return NULL;
+}
+
+/* the supported analyses of the running deck, in list order */
+typedef struct { const ddcmi_analysis *an; const ANALYSIS_TYPE *row; void *state; } ANALYSIS;
+static ANALYSIS *analyses = NULL;
+static int nanalyses = 0;
+void analysis_init_all(SIMULATE *simulate)
+{
+   const ddcmi_setup *s = simulate->setup;
+   nanalyses = 0;
+   analyses = zalloc(s->nanalysis + 1, sizeof(ANALYSIS));
+   for (int a = 0; a < s->nanalysis; a++)
+   {
+      const ddcmi_analysis *an = &s->analysis[a];
+      if (an->type != DDCMI_AN_NONE) analyses[nanalyses++] = (ANALYSIS){an, &types[an->type], types[an->type].init(simulate, an)};
+      else if (par.rank == 0) fprintf(stderr, "ddcmi_md: ANALYSIS %s of type %s is not supported and is ignored\n", an->name, an->type_name ? an->type_name : "?");
+   }
+}
+void analysis_startup_all(SIMULATE *simulate)
+{
+   for (ANALYSIS *A = analyses; A < analyses + nanalyses; A++)
+   {
+      if (analysis_due(A->an->eval_rate, simulate->loop)) A->row->eval(simulate, A->an, A->state);
+      if (A->row->clear) A->row->clear(simulate, A->an, A->state);      /* PAIRCORRELATION discards that sample */
+   }
+}
+int64_t analysis_next_stop(const SIMULATE *simulate, int64_t endLoop)
+{
+   for (const ANALYSIS *A = analyses; A < analyses + nanalyses; A++)
+   {
+      const int r[2] = {A->an->eval_rate, A->an->outputrate};
+      for (int q = 0; q < 2; q++)
+         if (r[q] > 0) { int64_t nx = (simulate->loop / r[q] + 1) * r[q]; if (nx < endLoop) endLoop = nx; }
+   }
+   return endLoop;
+}
+void analysis_do_all(SIMULATE *simulate)
+{
+   for (ANALYSIS *A = analyses; A < analyses + nanalyses; A++)
+   {
+      if (analysis_due(A->an->eval_rate, simulate->loop)) A->row->eval(simulate, A->an, A->state);
+      if (analysis_due(A->an->outputrate, simulate->loop)) A->row->output(simulate, A->an, A->state);
+   }
+}
+void analysis_free_all(void)
+{
+   for (ANALYSIS *A = analyses; A < analyses + nanalyses; A++) A->row->free(A->state);
+   free(analyses); analyses = NULL; nanalyses = 0;
+}

@@ -1,5 +1,6 @@
 /* deck.c -- see deck.h. */
 #include "deck.h"
+#include "analysis.h"
 #include "object.h"
 #include "units.h"
 #include <stdio.h>
@@ -537,57 +538,33 @@ ddcmi_setup *ddcmi_deck_load_with(const char *object_file, const char *restart_f
       object_get(sim, "time", &s->time, WITH_UNITS, 1, "0.0", "t", NULL);
       object_get(sim, "dt", &s->dt, WITH_UNITS, 1, "1.0", "t", NULL);
    }
-   /* ANALYSIS objects (analysis_init, analysis.c:120-160; paircorrelation_parms, paircorrelation.c:68-135) */
+   /* ANALYSIS objects (analysis_init, analysis.c:120-160): the keys of every type here, the type's own through its row of analysis.c's table */
    {
-      char **an = NULL;
-      int na = object_getv(sim, "analysis", (void **)&an, STRING, IGNORE_IF_NOT_FOUND);
+      char **names = NULL;
+      int na = object_getv(sim, "analysis", (void **)&names, STRING, IGNORE_IF_NOT_FOUND);
       if (na > 0)
       {
          s->nanalysis = na;
-         s->an_name = calloc(na, sizeof(char *)); s->an_typename = calloc(na, sizeof(char *)); s->pc_filename = calloc(na, sizeof(char *));
-         s->an_type = calloc(na, sizeof(int)); s->an_eval_rate = calloc(na, sizeof(int)); s->an_outputrate = calloc(na, sizeof(int));
-         s->pc_nbins = calloc(na, sizeof(int)); s->pc_log = calloc(na, sizeof(int)); s->pc_method = calloc(na, sizeof(int));
-         s->pc_rmin = calloc(na, sizeof(double)); s->pc_delta_r = calloc(na, sizeof(double));
-         s->vaf_filename = calloc(na, sizeof(char *)); s->vaf_length = calloc(na, sizeof(int));
-         int bad = 0;
-         char msg[512] = "";
+         s->analysis = calloc(na, sizeof(ddcmi_analysis));
+         char msg[512] = "";      /* the latest refusal of the list: the last one wins */
          for (int a = 0; a < na; a++)
          {
-            s->an_name[a] = an[a]; an[a] = NULL;
-            OBJECT *ao = object_find(s->an_name[a], "ANALYSIS");
-            if (!ao) { snprintf(msg, sizeof(msg), "ANALYSIS %s not found", s->an_name[a]); bad = 1; continue; }
-            s->an_typename[a] = get_string(ao, "type", "NONE");
-            object_get(ao, "eval_rate", &s->an_eval_rate[a], INT, 1, "0");
-            object_get(ao, "outputrate", &s->an_outputrate[a], INT, 1, "0");
-            if (strncasecmp(s->an_typename[a], "VELOCITYAUTOCORRELATION", strlen("VELOCITYAUTOCORRELATION")) == 0)
-            {
-               /* velocityAutocorrelation_parms (velocityAutocorrelation.c:59-60), the prefix match of analysis.c:178 */
-               s->an_type[a] = 2;
-               s->vaf_filename[a] = get_string(ao, "filename", "vaf.dat");
-               object_get(ao, "length", &s->vaf_length[a], INT, 1, "1");
-               if (s->vaf_length[a] < 1) { snprintf(msg, sizeof(msg), "ANALYSIS %s: length = %d", s->an_name[a], s->vaf_length[a]); bad = 1; }
-               continue;
-            }
-            if (strncasecmp(s->an_typename[a], "PAIRCORRELATION", strlen("PAIRCORRELATION")) != 0) continue;
-            s->an_type[a] = 1;
-            s->pc_filename[a] = get_string(ao, "filename", "paircorrelation.dat");
-            object_get(ao, "length", &s->pc_nbins[a], INT, 1, "1");
-            object_get(ao, "delta_r", &s->pc_delta_r[a], WITH_UNITS, 1, "1", "l", NULL);
-            object_get(ao, "rmin", &s->pc_rmin[a], WITH_UNITS, 1, "0", "l", NULL);
-            char *m = get_string(ao, "method", "geom"), *rs = get_string(ao, "rscale", "normal");
-            if (strcasecmp(m, "geom") == 0) s->pc_method[a] = 0;
-            else if (strcasecmp(m, "grid") == 0) s->pc_method[a] = 1;
-            else if (strcasecmp(m, "neighborList") == 0) s->pc_method[a] = 2;
-            else { snprintf(msg, sizeof(msg), "ANALYSIS %s: unrecognized method \"%s\"", s->an_name[a], m); bad = 1; }
-            if (strcasecmp(rs, "normal") == 0) s->pc_log[a] = 0;
-            else if (strcasecmp(rs, "log") == 0) s->pc_log[a] = 1;
-            else { snprintf(msg, sizeof(msg), "ANALYSIS %s: unrecognized rscale \"%s\"", s->an_name[a], rs); bad = 1; }
-            if (!bad && s->pc_log[a] && !(s->pc_rmin[a] > 0.0)) { snprintf(msg, sizeof(msg), "ANALYSIS %s: rscale = log needs rmin > 0", s->an_name[a]); bad = 1; }
-            if (!bad && s->pc_nbins[a] <= 0) { snprintf(msg, sizeof(msg), "ANALYSIS %s: length = %d", s->an_name[a], s->pc_nbins[a]); bad = 1; }
-            free(m); free(rs);
+            ddcmi_analysis *an = &s->analysis[a];
+            an->name = names[a]; names[a] = NULL;
+            OBJECT *ao = object_find(an->name, "ANALYSIS");
+            if (!ao) { snprintf(msg, sizeof(msg), "ANALYSIS %s not found", an->name); continue; }
+            an->type_name = get_string(ao, "type", "NONE");
+            object_get(ao, "eval_rate", &an->eval_rate, INT, 1, "0");
+            object_get(ao, "outputrate", &an->outputrate, INT, 1, "0");
+            const ANALYSIS_TYPE *row = analysis_type_find(an->type_name);
+            if (!row) continue;
+            an->type = row->type;
+            an->filename = get_string(ao, "filename", row->filename);
+            object_get(ao, "length", &an->length, INT, 1, "1");
+            row->parms(ao, an, msg, sizeof(msg));
          }
-         free(an);
-         if (bad) FAIL("%s", msg);
+         free(names);
+         if (msg[0]) FAIL("%s", msg);
       }
    }
    char *sysname = get_string(sim, "system", NULL);
@@ -1107,10 +1084,8 @@ void ddcmi_setup_free(ddcmi_setup *s)
    free(s->integrator_type); free(s->accelerator_type);
    free(s->u_energyflux);
    free(s->random_name); free(s->lcg_state); free(s->lcg_multID); free(s->lcg_prime);
-   for (int a = 0; a < s->nanalysis; a++) { free(s->an_name[a]); free(s->an_typename[a]); free(s->pc_filename[a]); free(s->vaf_filename[a]); }
-   free(s->an_name); free(s->an_typename); free(s->pc_filename); free(s->an_type); free(s->an_eval_rate); free(s->an_outputrate);
-   free(s->pc_nbins); free(s->pc_log); free(s->pc_method); free(s->pc_rmin); free(s->pc_delta_r);
-   free(s->vaf_filename); free(s->vaf_length);
+   for (int a = 0; a < s->nanalysis; a++) { free(s->analysis[a].name); free(s->analysis[a].type_name); free(s->analysis[a].filename); }
+   free(s->analysis);
    free(s->u_pressure); free(s->u_volume); free(s->u_temperature); free(s->u_energy); free(s->u_time); free(s->u_length);
    free(s);
 }

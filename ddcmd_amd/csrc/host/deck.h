@@ -17,6 +17,20 @@ extern "C" {
 
 enum { DDCMI_GROUP_FREE = 0, DDCMI_GROUP_BERENDSEN = 1, DDCMI_GROUP_LANGEVIN = 2, DDCMI_GROUP_OTHER = 3 };
 
+/* one ANALYSIS object (analysis_init, analysis.c:120-160).  type: the row of host/analysis.c's table that evaluates it; DDCMI_AN_NONE is any
+ * other type (not supported: the driver names it once on stderr) */
+enum ddcmi_analysis_kind { DDCMI_AN_NONE = 0, DDCMI_AN_PAIRCORRELATION, DDCMI_AN_VAF };
+typedef struct ddcmi_analysis
+{
+   char *name, *type_name;
+   enum ddcmi_analysis_kind type;
+   int eval_rate, outputrate;
+   char *filename;
+   int length;                  /* PAIRCORRELATION (paircorrelation.c:68-135): bins; VELOCITYAUTOCORRELATION (velocityAutocorrelation.c:59-60): samples per window behind the origin (>= 1) */
+   int rscale_log, method;      /* from here on PAIRCORRELATION only, zero otherwise.  method: 0 geom, 1 grid, 2 neighborList (all evaluated the same way: exactly) */
+   double rmin, delta_r;        /* internal length units */
+} ddcmi_analysis;
+
 typedef struct ddcmi_setup
 {
    /* SIMULATE (simulate.c:141-169,239-244) */
@@ -103,17 +117,9 @@ typedef struct ddcmi_setup
    uint64_t *lcg_state;
    uint32_t *lcg_multID, *lcg_prime;
    double *group_vcm;      /* [3 ngroup] LANGEVIN groups: `vcm` (langevin.c:167), internal units; zero otherwise */
-   /* SIMULATE analysis = name ... (analysis.c:120-160): every ANALYSIS object in the list, in list order.  an_type: 1 PAIRCORRELATION
-    * (paircorrelation.c:68-135; the pc_* fields), 2 VELOCITYAUTOCORRELATION (velocityAutocorrelation.c:59-60; the vaf_* fields),
-    * 0 any other type (not supported: the driver names it once on stderr) */
+   /* SIMULATE analysis = name ... (analysis.c:120-160): every ANALYSIS object in the list, in list order */
    int nanalysis;
-   char **an_name, **an_typename;
-   int *an_type, *an_eval_rate, *an_outputrate;
-   char **pc_filename;
-   int *pc_nbins, *pc_log, *pc_method;        /* pc_method: 0 geom, 1 grid, 2 neighborList (all evaluated the same way: exactly) */
-   double *pc_rmin, *pc_delta_r;              /* internal length units */
-   char **vaf_filename;
-   int *vaf_length;                           /* samples per window behind the origin (>= 1) */
+   ddcmi_analysis *analysis;
 } ddcmi_setup;
 
 /* lcg64_default over n particles in order (lcg64.c:98-110, primes.c:35-63 with prime_init(30000, task, ntasks), ddcMD.c:70) */

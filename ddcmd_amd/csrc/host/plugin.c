@@ -1,6 +1,7 @@
 /* plugin.c -- see plugin.h: ddcMD's plugin surface for the Martini path, in C, on
  * top of the C-ABI.  Reference lines are cited per function. */
 #include "plugin.h"
+#include "analysis.h"
 #include <errno.h>
 #include "object.h"
 #include "units.h"
@@ -14,7 +15,7 @@
 
 static ACCELERATOR *the_accelerator = NULL;
 
-static void die(const char *where, const char *msg)
+void die(const char *where, const char *msg)
 {
    /* error_action(msg, ERROR_IN(where, ABORT)) in the reference: print and exit */
    fprintf(stderr, "%s: %s\n", where, msg);
@@ -28,8 +29,7 @@ static void die(const char *where, const char *msg)
  * halos over RCCL (one GPU per rank) or, with DDCMI_TRANSPORT=host, over the rendezvous' streams (ranks that
  * share a GPU).  Rank 0 owns stdout, the data file and the restart files; STATE on rank 0 is the gathered
  * global state at print / checkpoint steps, exactly what it is on one rank. */
-typedef struct { int rank, world, local_rank, grid[3], host_transport; ddcmi_rdzv *rdzv; } PARENV;
-static PARENV par = {0, 1, 0, {1, 1, 1}, 0, NULL};
+PARENV par = {0, 1, 0, {1, 1, 1}, 0, NULL};
 static int env_int(const char *name, int dflt) { const char *v = getenv(name); return (v && *v) ? atoi(v) : dflt; }
 /* the process grid: the deck's ddc DDC { lx ly lz } when it multiplies to the number of ranks; otherwise WORLD_SIZE factored
  * over the axes, smallest prime factors first, each onto the axis whose bricks are widest at that point (2 -> 2x1x1,
@@ -1111,226 +1111,6 @@ void printinfo(SIMULATE *simulate, ETYPE *e_in, int header)
    }
 }
 
-/* ------------------------------------------------------------------------- */
-/* ANALYSIS type PAIRCORRELATION (paircorrelation.c: eval_geom :354-457, output :460-520; analysis.c:133-153): the counts come from
- * the device (ddcmi_pair_correlation), are summed over the ranks (integers below 2^53: the double sum is exact, so every rank count
- * gives the same file) and accumulated on the host in the reference's order; rank 0 writes the file.  Other types: one line. */
-typedef struct { int a; int nsample; double *g, *buf; int64_t *cnt, *nb; } PCSTATE;
-static PCSTATE *pc_states = NULL;
-static int pc_n = 0;
-static void analysis_init_all(SIMULATE *simulate)
-{
-   const ddcmi_setup *s = simulate->setup;
-   pc_n = 0;
-   pc_states = s->nanalysis > 0 ? calloc(s->nanalysis, sizeof(PCSTATE)) : NULL;
-   const int np = s->nspecies * (s->nspecies + 1) / 2;
-   for (int a = 0; a < s->nanalysis; a++)
-   {
-      if (s->an_type[a] == 2) continue;      /* VELOCITYAUTOCORRELATION: vaf_init_all */
-      if (s->an_type[a] != 1)
-      {
-         if (par.rank == 0) fprintf(stderr, "ddcmi_md: ANALYSIS %s of type %s is not supported and is ignored\n", s->an_name[a], s->an_typename[a] ? s->an_typename[a] : "?");
-         continue;
-      }
-      PCSTATE *p = &pc_states[pc_n++];
-      const size_t nh = (size_t)np * s->pc_nbins[a];
-      p->a = a;
-      p->g = calloc(nh, sizeof(double)); p->buf = calloc(nh + s->nspecies, sizeof(double));
-      p->cnt = calloc(nh, sizeof(int64_t)); p->nb = calloc(s->nspecies, sizeof(int64_t));
-      if (!p->g || !p->buf || !p->cnt || !p->nb) die("analysis", "out of memory");
-   }
-}
-static void pc_clear(const ddcmi_setup *s, PCSTATE *p)
-{
-   memset(p->g, 0, sizeof(double) * (size_t)(s->nspecies * (s->nspecies + 1) / 2) * s->pc_nbins[p->a]);
-   p->nsample = 0;
-}
-static int pc_combo(int i, int j, int ns) { int lo = i < j ? i : j, hi = i < j ? j : i; return (hi - lo) + ns * lo - (lo * (lo - 1)) / 2; }
-static void pc_eval(SIMULATE *simulate, PCSTATE *p)
-{
-   const ddcmi_setup *s = simulate->setup;
-   ddcmi_ctx *ctx = simulate->accelerator->parms;
-   const int a = p->a, ns = s->nspecies, nbins = s->pc_nbins[a];
-   const size_t nh = (size_t)(ns * (ns + 1) / 2) * nbins;
-   if (ddcmi_pair_correlation(ctx, s->pc_rmin[a], s->pc_delta_r[a], nbins, s->pc_log[a], ns, p->cnt, p->nb) != DDCMI_OK)
-      die("paircorrelation_eval", ddcmi_last_error(ctx));
-   for (size_t k = 0; k < nh; k++) p->buf[k] = (double)p->cnt[k];
-   for (int t = 0; t < ns; t++) p->buf[nh + t] = (double)p->nb[t];
-   if (par.world > 1 && ddcmi_rdzv_allreduce_f64(par.rdzv, p->buf, (int)(nh + ns), 0) != DDCMI_OK) die("paircorrelation_eval", ddcmi_rdzv_last_error(par.rdzv));
-   p->nsample += 1;
-   for (int i = 0; i < ns; i++)
-      for (int j = i; j < ns; j++)
-      {
-         const int l = pc_combo(i, j, ns);
-         const double recipNiNj = 1.0 / (p->buf[nh + i] * p->buf[nh + j]);
-         for (int k = 0; k < nbins; k++) { double nBonds = p->buf[(size_t)l * nbins + k]; nBonds *= recipNiNj; p->g[(size_t)l * nbins + k] += nBonds; }
-      }
-}
-static void pc_output(SIMULATE *simulate, PCSTATE *p)
-{
-   const ddcmi_setup *s = simulate->setup;
-   ddcmi_ctx *ctx = simulate->accelerator->parms;
-   const int a = p->a, ns = s->nspecies, np = ns * (ns + 1) / 2, nbins = s->pc_nbins[a];
-   if (p->nsample == 0) { pc_clear(s, p); return; }
-   if (par.rank == 0)
-   {
-      char dir[512], path[1100];
-      snprintf(dir, sizeof(dir), "snapshot.%012" PRId64, simulate->loop);      /* CreateSnapshotdir: the directory writeRestart uses */
-      if (mkdir(dir, 0777) != 0 && errno != EEXIST) die("paircorrelation_output", "cannot create the snapshot directory");
-      snprintf(path, sizeof(path), "%s/%s", dir, s->pc_filename[a]);
-      FILE *f = fopen(path, "w");
-      if (!f) die("paircorrelation_output", "cannot open the output file");
-      double h[9];
-      if (ddcmi_get_box(ctx, h) != DDCMI_OK) die("paircorrelation_output", ddcmi_last_error(ctx));
-      const double volume = h[0] * h[4] * h[8], sc = volume / p->nsample;
-      const double rmin = s->pc_rmin[a], dr = s->pc_delta_r[a], rmax = rmin + nbins * dr;
-      const double logDelta = s->pc_log[a] ? (log10(rmax) - log10(rmin)) / (nbins * 1.0) : 0.0;
-      double *left = malloc(sizeof(double) * nbins), *right = malloc(sizeof(double) * nbins);
-      for (int k = 0; k < nbins; k++)
-      {
-         if (s->pc_log[a]) left[k] = pow(10, log10(rmin) + k * logDelta);
-         else { left[k] = rmin + k * dr; right[k] = rmin + (k + 1) * dr; }
-      }
-      if (s->pc_log[a]) { for (int k = 0; k + 1 < nbins; k++) right[k] = left[k + 1]; right[nbins - 1] = rmax; }
-      for (int k = 0; k < nbins; k++)
-      {
-         const double dv = 4.0 * M_PI / 3.0 * (right[k] * right[k] * right[k] - left[k] * left[k] * left[k]);
-         for (int l = 0; l < np; l++) p->g[k + (size_t)nbins * l] *= sc / dv;
-      }
-      fprintf(f, "# rmin = %f Ang; delta_r = %f Ang; length = %d; eval_rate = %d; outputrate = %d;\n", units_convert(rmin, NULL, "Angstrom"),
-              units_convert(dr, NULL, "Angstrom"), nbins, s->an_eval_rate[a], s->an_outputrate[a]);
-      fprintf(f, "# nsample = %d;\n", p->nsample);
-      fprintf(f, "# r(Ang) ");
-      for (int l = 0; l < np; l++)
-      {
-         int ti = -1, tj = -1;
-         for (int i = 0; i < ns && ti < 0; i++) for (int j = i; j < ns; j++) if (pc_combo(i, j, ns) == l) { ti = i; tj = j; break; }      /* comboReverseIndex */
-         fprintf(f, "%s-%s ", s->species_name[ti], s->species_name[tj]);
-      }
-      fprintf(f, "\n");
-      for (int k = 0; k < nbins; k++)
-      {
-         fprintf(f, "%f ", units_convert(0.5 * (left[k] + right[k]), NULL, "Angstrom"));
-         for (int l = 0; l < np; l++) fprintf(f, "%e ", p->g[k + (size_t)nbins * l]);
-         fprintf(f, "\n");
-      }
-      fclose(f);
-      free(left); free(right);
-   }
-   pc_clear(s, p);
-}
-static int pc_due(int rate, int64_t loop) { return rate > 0 && loop % rate == 0; }      /* TEST0 */
-static void analysis_free_all(void)
-{
-   for (int k = 0; k < pc_n; k++) { free(pc_states[k].g); free(pc_states[k].buf); free(pc_states[k].cnt); free(pc_states[k].nb); }
-   free(pc_states); pc_states = NULL; pc_n = 0;
-}
-
-/* ANALYSIS type VELOCITYAUTOCORRELATION (velocityAutocorrelation.c: eval :117-229, output :230-327): the state machine of the
- * reference -- last, nsample, vaf0 / msd0 of the current window, vaf_ / msd_ accumulated over the windows -- over the device's sums
- * (ddcmi_vaf_origin / ddcmi_vaf_sample).  Every class is kept ([1 + ngroup + nspecies] blocks of length + 1); the output leaves out
- * the group block of a single group and the species block of a single species, as the reference does.  The sums over the ranks go
- * by ddcmi_rdzv_allreduce_f64, in rank order.  A restart begins with a fresh origin (last = 0). */
-typedef struct { int a, last, nsample, ncl, len; double *vaf0, *msd0, *vaf_, *msd_, *buf; } VAFSTATE;
-static VAFSTATE *vaf_states = NULL;
-static int vaf_n = 0;
-static void vaf_init_all(SIMULATE *simulate)
-{
-   const ddcmi_setup *s = simulate->setup;
-   vaf_n = 0;
-   vaf_states = s->nanalysis > 0 ? calloc(s->nanalysis, sizeof(VAFSTATE)) : NULL;
-   for (int a = 0; a < s->nanalysis; a++)
-   {
-      if (s->an_type[a] != 2) continue;
-      VAFSTATE *p = &vaf_states[vaf_n++];
-      p->a = a; p->len = s->vaf_length[a]; p->ncl = 1 + (s->ngroup > 0 ? s->ngroup : 1) + s->nspecies;
-      const size_t tot = (size_t)p->ncl * (p->len + 1);
-      p->vaf0 = calloc(tot, sizeof(double)); p->msd0 = calloc(tot, sizeof(double));
-      p->vaf_ = calloc(tot, sizeof(double)); p->msd_ = calloc(tot, sizeof(double)); p->buf = calloc(2 * (size_t)p->ncl, sizeof(double));
-      if (!p->vaf0 || !p->msd0 || !p->vaf_ || !p->msd_ || !p->buf) die("analysis", "out of memory");
-   }
-}
-/* sample k of the current window: the global sums of every class */
-static void vaf_take(SIMULATE *simulate, VAFSTATE *p, int k)
-{
-   const ddcmi_setup *s = simulate->setup;
-   ddcmi_ctx *ctx = simulate->accelerator->parms;
-   if (ddcmi_vaf_sample(ctx, s->ngroup > 0 ? s->ngroup : 1, s->nspecies, p->buf, p->buf + p->ncl) != DDCMI_OK) die("velocityAutocorrelation_eval", ddcmi_last_error(ctx));
-   if (par.world > 1 && ddcmi_rdzv_allreduce_f64(par.rdzv, p->buf, 2 * p->ncl, 0) != DDCMI_OK) die("velocityAutocorrelation_eval", ddcmi_rdzv_last_error(par.rdzv));
-   for (int c = 0; c < p->ncl; c++) { p->vaf0[k + c * (p->len + 1)] = p->buf[c]; p->msd0[k + c * (p->len + 1)] = p->buf[p->ncl + c]; }
-}
-static void vaf_eval(SIMULATE *simulate, VAFSTATE *p)
-{
-   ddcmi_ctx *ctx = simulate->accelerator->parms;
-   const size_t tot = (size_t)p->ncl * (p->len + 1);
-   int k = p->last;
-   if (k > 0) vaf_take(simulate, p, k);
-   if (k == p->len)
-   {
-      p->nsample++;
-      for (size_t l = 0; l < tot; l++) { p->msd_[l] += p->msd0[l]; p->vaf_[l] += p->vaf0[l]; p->msd0[l] = 0.0; p->vaf0[l] = 0.0; }
-      k = p->last = 0;
-   }
-   if (k == 0)
-   {
-      if (ddcmi_vaf_origin(ctx) != DDCMI_OK) die("velocityAutocorrelation_eval", ddcmi_last_error(ctx));
-      vaf_take(simulate, p, 0);      /* sum v.v, and zero */
-   }
-   p->last++;
-}
-static void vaf_output(SIMULATE *simulate, VAFSTATE *p)
-{
-   const ddcmi_setup *s = simulate->setup;
-   const int a = p->a, len = p->len, eval_rate = s->an_eval_rate[a], outputrate = s->an_outputrate[a];
-   if ((long long)p->nsample * len * eval_rate != outputrate) return;      /* (no file, no reset) */
-   const int ng = s->ngroup > 0 ? s->ngroup : 1, ngroups = ng == 1 ? 0 : ng, nspecies = s->nspecies == 1 ? 0 : s->nspecies;
-   if (par.rank == 0)
-   {
-      char dir[512], path[1100];
-      snprintf(dir, sizeof(dir), "snapshot.%012" PRId64, simulate->loop);
-      if (mkdir(dir, 0777) != 0 && errno != EEXIST) die("velocityAutocorrelation_output", "cannot create the snapshot directory");
-      snprintf(path, sizeof(path), "%s/%s", dir, s->vaf_filename[a]);
-      FILE *f = fopen(path, "w");
-      if (!f) die("velocityAutocorrelation_output", "cannot open the output file");
-      /* member counts of the whole system (sys->group[ii]->nMember, species likewise) */
-      double *ngm = calloc(ng, sizeof(double)), *nsm = calloc(s->nspecies, sizeof(double));
-      for (int i = 0; i < s->natoms; i++) { ngm[s->group ? s->group[i] : 0] += 1.0; nsm[s->species[i]] += 1.0; }
-      const double nglobal = (double)simulate->system->nglobal;
-      const double time_convert = units_convert(1.0, NULL, "t"), v2_convert = units_convert(1.0, NULL, "velocity^2"), r2_convert = units_convert(1.0, NULL, "l^2");
-      fprintf(f, "%-33s", "#time (fs)  System vaf MSD");
-      for (int ii = 0; ii < ngroups; ii++) { char temp[300]; snprintf(temp, sizeof(temp), "  Group %s vaf MSD", s->group_name[ii]); fprintf(f, "%-26s", temp); }
-      for (int ii = 0; ii < nspecies; ii++) { char temp[300]; snprintf(temp, sizeof(temp), "  Species %s vaf MSD", s->species_name[ii]); fprintf(f, "%-26s", temp); }
-      fprintf(f, " (vaf in Ang^2/fs^2; msd in Ang^2)\n");
-      for (int k = 0; k <= len; k++)
-      {
-         const double time = time_convert * k * simulate->dt * eval_rate;
-         fprintf(f, "%f", time);
-         fprintf(f, " %e %e", (v2_convert * p->vaf_[k] / p->nsample) / nglobal, (r2_convert * p->msd_[k] / p->nsample) / nglobal);
-         for (int ii = 0; ii < ngroups; ii++)
-         {
-            const int off = (1 + ii) * (len + 1);
-            fprintf(f, " %e %e", (v2_convert * p->vaf_[k + off] / p->nsample) / ngm[ii], (r2_convert * p->msd_[k + off] / p->nsample) / ngm[ii]);
-         }
-         for (int ii = 0; ii < nspecies; ii++)
-         {
-            const int off = (1 + ng + ii) * (len + 1);
-            fprintf(f, " %e %e", (v2_convert * p->vaf_[k + off] / p->nsample) / nsm[ii], (r2_convert * p->msd_[k + off] / p->nsample) / nsm[ii]);
-         }
-         fprintf(f, "\n");
-      }
-      fclose(f);
-      free(ngm); free(nsm);
-   }
-   memset(p->vaf_, 0, sizeof(double) * (size_t)p->ncl * (len + 1));
-   memset(p->msd_, 0, sizeof(double) * (size_t)p->ncl * (len + 1));
-   p->nsample = 0;
-}
-static void vaf_free_all(void)
-{
-   for (int k = 0; k < vaf_n; k++) { free(vaf_states[k].vaf0); free(vaf_states[k].msd0); free(vaf_states[k].vaf_); free(vaf_states[k].msd_); free(vaf_states[k].buf); }
-   free(vaf_states); vaf_states = NULL; vaf_n = 0;
-}
-
 /* simulateMaster, masters.c:369-559: firstEnergyCall, then batches of steps up to
  * the next print step (findEndLoop :263-281), energies after each batch */
 int simulateMaster(SIMULATE *simulate, const char *datafile_path)
@@ -1353,14 +1133,7 @@ int simulateMaster(SIMULATE *simulate, const char *datafile_path)
    ddcenergy(simulate->ddc, sys, 1);
    printinfo(simulate, &sys->energyInfo, 1);
    analysis_init_all(simulate);
-   for (int k = 0; k < pc_n; k++)                                 /* analysis_startup, analysis.c:133-138: that sample is discarded */
-   {
-      if (pc_due(simulate->setup->an_eval_rate[pc_states[k].a], simulate->loop)) pc_eval(simulate, &pc_states[k]);
-      pc_clear(simulate->setup, &pc_states[k]);
-   }
-   vaf_init_all(simulate);
-   for (int k = 0; k < vaf_n; k++)                                /* its clear is analysis_NULL: the startup evaluation stays and sets the first origin */
-      if (pc_due(simulate->setup->an_eval_rate[vaf_states[k].a], simulate->loop)) vaf_eval(simulate, &vaf_states[k]);
+   analysis_startup_all(simulate);
    while (simulate->loop < simulate->maxloop)
    {
       int64_t endLoop = (simulate->loop / simulate->printrate + 1) * simulate->printrate;
@@ -1374,18 +1147,7 @@ int simulateMaster(SIMULATE *simulate, const char *datafile_path)
          int64_t nextSn = (simulate->loop / simulate->snapshotrate + 1) * simulate->snapshotrate;          /* masters.c:275 */
          if (nextSn < endLoop) endLoop = nextSn;
       }
-      for (int k = 0; k < pc_n; k++)                              /* findEndLoop, masters.c:277-282: the analyses' eval and output rates */
-      {
-         const int r[2] = {simulate->setup->an_eval_rate[pc_states[k].a], simulate->setup->an_outputrate[pc_states[k].a]};
-         for (int q = 0; q < 2; q++)
-            if (r[q] > 0) { int64_t nx = (simulate->loop / r[q] + 1) * r[q]; if (nx < endLoop) endLoop = nx; }
-      }
-      for (int k = 0; k < vaf_n; k++)
-      {
-         const int r[2] = {simulate->setup->an_eval_rate[vaf_states[k].a], simulate->setup->an_outputrate[vaf_states[k].a]};
-         for (int q = 0; q < 2; q++)
-            if (r[q] > 0) { int64_t nx = (simulate->loop / r[q] + 1) * r[q]; if (nx < endLoop) endLoop = nx; }
-      }
+      endLoop = analysis_next_stop(simulate, endLoop);            /* findEndLoop, masters.c:277-282: the analyses' eval and output rates */
       if (endLoop > simulate->maxloop) endLoop = simulate->maxloop;
       if (simulate->integrator->eval_integrator == (void (*)(void *, void *, void *))nglfHIP)
       {
@@ -1418,23 +1180,11 @@ int simulateMaster(SIMULATE *simulate, const char *datafile_path)
       const int ck = simulate->checkpointrate > 0 && simulate->loop % simulate->checkpointrate == 0;
       if (ck)                                                                                   /* masters.c:318-322 */
       { if (writeRestart(simulate, NULL, 1) != 0) die("simulateMaster", "writeRestart failed"); }
-      for (int k = 0; k < pc_n; k++)                              /* doAnalysis (masters.c:503-505): after the checkpoint, before the snapshot */
-      {
-         const int a = pc_states[k].a;
-         if (pc_due(simulate->setup->an_eval_rate[a], simulate->loop)) pc_eval(simulate, &pc_states[k]);
-         if (pc_due(simulate->setup->an_outputrate[a], simulate->loop)) pc_output(simulate, &pc_states[k]);
-      }
-      for (int k = 0; k < vaf_n; k++)
-      {
-         const int a = vaf_states[k].a;
-         if (pc_due(simulate->setup->an_eval_rate[a], simulate->loop)) vaf_eval(simulate, &vaf_states[k]);
-         if (pc_due(simulate->setup->an_outputrate[a], simulate->loop)) vaf_output(simulate, &vaf_states[k]);
-      }
+      analysis_do_all(simulate);                                  /* doAnalysis (masters.c:503-505): after the checkpoint, before the snapshot */
       if (!ck && simulate->snapshotrate > 0 && simulate->loop % simulate->snapshotrate == 0)    /* doSnapshot, masters.c:340-352: the particle files, no ./restart */
       { if (writeRestart(simulate, NULL, 0) != 0) die("simulateMaster", "snapshot write failed"); }
    }
    analysis_free_all();
-   vaf_free_all();
    sendHostState(sys);
    if (simulate->datafile) fclose(simulate->datafile);
    simulate->datafile = NULL;

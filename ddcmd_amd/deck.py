@@ -183,14 +183,14 @@ def load_deck(object_file, restart_file=None, extra_objects=None):
         s.units = {k: getattr(c, "u_" + k).decode() for k in ("pressure", "volume", "temperature", "energy", "time", "length")}
         # SIMULATE analysis = ...: one dict per ANALYSIS object, in list order (types PAIRCORRELATION and VELOCITYAUTOCORRELATION with their parameters, internal units)
         s.analysis = []
-        for a in range(int(c.nanalysis)):
-            d = {"name": c.an_name[a].decode(), "type": (c.an_typename[a] or b"").decode(), "eval_rate": int(c.an_eval_rate[a]),
-                 "outputrate": int(c.an_outputrate[a]), "supported": bool(c.an_type[a] != 0)}
-            if c.an_type[a] == 2:      # VELOCITYAUTOCORRELATION
-                d.update(filename=c.vaf_filename[a].decode(), length=int(c.vaf_length[a]))
-            elif d["supported"]:
-                d.update(filename=c.pc_filename[a].decode(), length=int(c.pc_nbins[a]), delta_r=float(c.pc_delta_r[a]), rmin=float(c.pc_rmin[a]),
-                         rscale="log" if c.pc_log[a] else "normal", method=("geom", "grid", "neighborList")[int(c.pc_method[a])])
+        for a in (c.analysis[i] for i in range(int(c.nanalysis))):
+            d = {"name": a.name.decode(), "type": (a.type_name or b"").decode(), "eval_rate": int(a.eval_rate), "outputrate": int(a.outputrate),
+                 "supported": a.type != _lib.AN_NONE}
+            if d["supported"]:
+                d.update(filename=a.filename.decode(), length=int(a.length))
+            if a.type == _lib.AN_PAIRCORRELATION:
+                d.update(delta_r=float(a.delta_r), rmin=float(a.rmin), rscale="log" if a.rscale_log else "normal",
+                         method=("geom", "grid", "neighborList")[a.method])
             s.analysis.append(d)
     finally:
         lib.ddcmi_setup_free(p)

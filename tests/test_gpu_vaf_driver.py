@@ -119,3 +119,35 @@ def test_driver_two_ranks_write_the_same_file(tmp_path):
         assert la == lb and np.array_equal(t1, t2)
         # the ranks' sums are added in rank order: the digits %e prints agree unless a value sits on a rounding edge of its last digit
         assert np.allclose(v1, v2, rtol=2e-6, atol=2e-6 * np.abs(v1).max()) and np.allclose(m1, m2, rtol=2e-6, atol=0)
+
+
+def _files(d):
+    """every file under d, as paths relative to it"""
+    return sorted(os.path.relpath(os.path.join(p, f), str(d)) for p, _, fs in os.walk(str(d)) for f in fs)
+
+
+def test_driver_mixed_list_matches_single_analysis_runs(tmp_path):
+    """a list of three types -- VELOCITYAUTOCORRELATION, an unsupported one, PAIRCORRELATION -- against the runs of its two supported
+    members alone: the run itself, the g(r) files and the vaf files are the same bytes, the unsupported one is named once and writes
+    nothing.  Bytes, not a tolerance: the pair counts are integers, the vaf kernels reduce without atomics, and the analyses of one
+    list share no state, so the order in which the driver walks them shows in no file."""
+    sim = "simulate SIMULATE { %sdeltaloop = 100; maxloop = 100; printrate = 5; snapshotrate = 100000; checkpointrate = 100000; }\n"
+    rdf = "rdf ANALYSIS { type = PAIRCORRELATION; eval_rate = 10; outputrate = 50; delta_r = 0.1 Angstrom; length = 100; }\n"
+    other = "writeCharmm ANALYSIS { type = subsetWrite; outputrate = 10; }\n"
+    da, db, dc = (_copy(tmp_path, "water_deck", n) for n in ("mixed", "rdf", "vaf"))
+    out = _run(da, sim % "analysis = vaf writeCharmm rdf; " + VAF % 40 + other + rdf)
+    _run(db, sim % "analysis = rdf; " + rdf)
+    _run(dc, sim % "analysis = vaf; " + VAF % 40)
+    data = [open(str(d / "data"), "rb").read() for d in (da, db, dc)]
+    assert len(data[0]) > 0 and data[0] == data[1] == data[2]
+    for single, name, loops in ((db, "paircorrelation.dat", (50, 100)), (dc, "vaf.dat", (40, 80))):
+        for loop in loops:
+            (a,) = glob.glob(str(da / ("snapshot.*%d" % loop) / name))
+            (b,) = glob.glob(str(single / ("snapshot.*%d" % loop) / name))
+            ta, tb = open(a, "rb").read(), open(b, "rb").read()
+            assert len(ta) > 0 and ta == tb, (name, loop)
+    written = sorted(set(_files(da)) - set(_files(os.path.join(ROOT, "tests", "golden", "water_deck"))))
+    assert written == ["data", "snapshot.%012d/vaf.dat" % 40, "snapshot.%012d/paircorrelation.dat" % 50, "snapshot.%012d/vaf.dat" % 80,
+                       "snapshot.%012d/paircorrelation.dat" % 100]      # no other analysis file
+    lines = [l for l in out.stderr.splitlines() if "writeCharmm" in l]
+    assert len(lines) == 1 and "subsetWrite" in lines[0] and "not supported" in lines[0]
