@@ -82,14 +82,15 @@ c_u64_p = ctypes.POINTER(ctypes.c_uint64)
 c_char_pp = ctypes.POINTER(ctypes.c_char_p)
 
 
-AN_NONE, AN_PAIRCORRELATION, AN_VAF = range(3)      # enum ddcmi_analysis_kind
+AN_NONE, AN_PAIRCORRELATION, AN_VAF, AN_VCMWRITE, AN_ZDENSITY = range(5)      # enum ddcmi_analysis_kind
 
 
 class CAnalysis(ctypes.Structure):
     """Mirror of struct ddcmi_analysis (ddcmd_amd/csrc/host/deck.h)."""
     _fields_ = [("name", ctypes.c_char_p), ("type_name", ctypes.c_char_p), ("type", ctypes.c_int), ("eval_rate", ctypes.c_int), ("outputrate", ctypes.c_int),
                 ("filename", ctypes.c_char_p), ("length", ctypes.c_int),
-                ("rscale_log", ctypes.c_int), ("method", ctypes.c_int), ("rmin", ctypes.c_double), ("delta_r", ctypes.c_double)]
+                ("rscale_log", ctypes.c_int), ("method", ctypes.c_int), ("rmin", ctypes.c_double), ("delta_r", ctypes.c_double),
+                ("nz", ctypes.c_int), ("smear_method", ctypes.c_int), ("smear_radius", ctypes.c_double)]
 
 
 class CSetup(ctypes.Structure):

@@ -1,9 +1,10 @@
-"""ANALYSIS types PAIRCORRELATION and VELOCITYAUTOCORRELATION on the host side.
+"""ANALYSIS types PAIRCORRELATION, VELOCITYAUTOCORRELATION, vcmWrite and zdensity on the host side.
 PairCorrelation: accumulation of the device's pair counts into g(r) and the output file, as paircorrelation_eval_geom /
 paircorrelation_output (paircorrelation.c) do.  The counting itself is ddcmi_pair_correlation (Martini*.pair_correlation); nothing
 here searches pairs.
 VelocityAutocorrelation: the windows of velocityAutocorrelation_eval and the file of velocityAutocorrelation_output
-(velocityAutocorrelation.c) over the device's sums (Martini*.vaf_origin / vaf_sample)."""
+(velocityAutocorrelation.c) over the device's sums (Martini*.vaf_origin / vaf_sample).
+VcmWrite, ZDensity: the file text of vcmWrite.c / zdensity.c from the device's sums (Martini*.momentum_by_class / zdensity)."""
 import numpy as np
 
 from .deck import units_convert
@@ -201,3 +202,69 @@ def parse_vaf_output(text):
     rows = np.array([[float(x) for x in ln.split()] for ln in lines[1:] if ln.strip()])
     assert rows.shape[1] == 1 + 2 * len(labels)
     return labels, rows[:, 0], rows[:, 1::2].T, rows[:, 2::2].T
+
+
+LOOP_WIDTH = 12      # the driver's loop format: the width of the data file's loop column
+
+
+class VcmWrite(object):
+    """one vcmWrite analysis (vcmWrite.c): header() is the line written when the file is opened, line(loop, time, mv, m) one output
+    line from the sums over the ranks (Martini*.momentum_by_class: mv[nclass, 3] = sum m v, m[nclass] = sum m, internal units).
+    Every group and every species has a block, a single one too."""
+
+    def __init__(self, group_names, species_names, outputrate=0, filename="vcm.data"):
+        self.group_names, self.species_names = list(group_names) or ["group"], list(species_names)
+        self.ncl = 1 + len(self.group_names) + len(self.species_names)
+        self.outputrate, self.filename = int(outputrate), filename
+
+    def header(self):
+        head = "-%*s %14s" % (LOOP_WIDTH, "#loop", "time(fs)")      # (the reference's format as it stands)
+        head += "%-51s" % "     System vx vy vz (Ang/fs)"
+        head += "".join("%-51s" % ("     Group %s vx vy vz (Ang/fs)" % g) for g in self.group_names)
+        head += "".join("%-51s" % ("     Species %s vx vy vz (Ang/fs)" % sp) for sp in self.species_names)
+        return head + "\n"
+
+    def velocities(self, mv, m):
+        """vcm[nclass, 3] in Ang/fs: sum m v / sum m where the class has mass, the sum as it is otherwise"""
+        mv, m = np.array(mv, dtype=np.float64).reshape(self.ncl, 3), np.asarray(m, dtype=np.float64).reshape(self.ncl)
+        for c in range(self.ncl):
+            if m[c] > 0.0:
+                mv[c] *= 1 / m[c]
+        return mv * units_convert(1.0, None, "Ang/fs")
+
+    def line(self, loop, time, mv, m):
+        """time in internal units"""
+        row = "%*d" % (LOOP_WIDTH, int(loop)) + " %16.6f" % (units_convert(1.0, None, "fs") * time)
+        row += "".join(" %16.6e %16.6e %16.6e" % tuple(v) for v in self.velocities(mv, m))
+        return row + "\n"
+
+
+def parse_vcm_output(text):
+    """(loop[nline], time[nline] in fs, vcm[nline, nclass, 3] in Ang/fs) of a vcmWrite file (header lines skipped)"""
+    rows = [ln.split() for ln in text.splitlines() if ln.strip() and not ln.startswith("-")]
+    loop = np.array([int(r[0]) for r in rows], np.int64)
+    val = np.array([[float(x) for x in r[1:]] for r in rows], dtype=np.float64).reshape(len(rows), -1)
+    return loop, val[:, 0], val[:, 1:].reshape(len(rows), -1, 3)
+
+
+class ZDensity(object):
+    """one zdensity analysis (zdensity.c): output_text(density, box) is the file from the histogram summed over the ranks
+    (Martini*.zdensity); box = (Lx, Ly, Lz) in internal units"""
+
+    def __init__(self, nz, smear_radius=0.0, smear_method="impulse", outputrate=0, filename="zden.dat"):
+        if int(nz) < 1:
+            raise ValueError("nz = %d" % nz)
+        self.nz, self.smear_radius = int(nz), float(smear_radius)
+        self.smear_method = "hat" if str(smear_method).lower() == "hat" else "impulse"
+        self.outputrate, self.filename = int(outputrate), filename
+
+    def output_text(self, density, box):
+        density = np.asarray(density, dtype=np.float64).reshape(self.nz)
+        lc = units_convert(1.0, None, "Angstrom")
+        box_vol = (box[0] * box[1] * box[2]) * lc * lc * lc
+        bz = float(box[2])
+        lines = []
+        for ii in range(self.nz):
+            z = ((ii + 0.5) * (bz / self.nz)) / bz
+            lines.append("%f %f %f\n" % (z, density[ii] * (self.nz / box_vol), density[ii]))
+        return "".join(lines)

@@ -371,6 +371,7 @@ struct ddcmi_ctx
    /* ANALYSIS VELOCITYAUTOCORRELATION (ddcmi_vaf.inl): the owned beads' reference records in slot order, moved with the beads like lcg
     * (k_gather_state, the migration records); vaf_part: the sample's per-workgroup sums and, behind them, its result */
    dbuf<VafRec> vaf, vaf2; bool vaf_on = false; dbuf<double> vaf_part;
+   dbuf<double> census_part;      /* ANALYSIS vcmWrite / zdensity (ddcmi_census.inl): the pass's per-workgroup sums and, behind them, its result */
    /* what is not a dbuf or an hbuf; those free themselves after this */
    ~ddcmi_ctx()
    {

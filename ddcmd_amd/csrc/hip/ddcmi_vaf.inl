@@ -43,8 +43,10 @@ __global__ void k_vaf_origin(int n, const double4 *__restrict__ pos, const doubl
    r.o[0] = p.x; r.o[1] = p.y; r.o[2] = p.z;
    vaf[i] = r;
 }
-/* the lanes whose key is k add a and b into row[2 k], row[2 k + 1] of the wave's LDS row, class after class (pending: lanes with a bead) */
-__device__ __forceinline__ void vaf_add_classes(unsigned long long pending, int key, double a, double b, double *row)
+/* the lanes whose key is k add their NV values into row[NV k .. NV k + NV - 1] of the wave's LDS row, class after class (pending: lanes with a
+ * bead).  NV = 2: this sample's {v0.v, d.d}; NV = 4: ddcmi_census.inl's {m vx, m vy, m vz, m} */
+template <int NV>
+__device__ __forceinline__ void vaf_add_classes(unsigned long long pending, int key, const double (&v)[NV], double *row)
 {
    const int lane = threadIdx.x & 63;
    while (pending)
@@ -52,8 +54,14 @@ __device__ __forceinline__ void vaf_add_classes(unsigned long long pending, int 
       const int lead = __ffsll((long long)pending) - 1;
       const int k = __shfl(key, lead, 64);
       const bool mine = (pending >> lane & 1ull) && key == k;
-      const double sa = wave_sum_dpp(mine ? a : 0.0), sb = wave_sum_dpp(mine ? b : 0.0);
-      if (lane == lead) { row[2 * k] += sa; row[2 * k + 1] += sb; }
+      double s[NV];
+#pragma unroll
+      for (int q = 0; q < NV; q++) s[q] = wave_sum_dpp(mine ? v[q] : 0.0);
+      if (lane == lead)
+      {
+#pragma unroll
+         for (int q = 0; q < NV; q++) row[NV * k + q] += s[q];
+      }
       pending &= ~__ballot(mine);
    }
 }
@@ -86,8 +94,9 @@ __global__ __launch_bounds__(VAF_THREADS) void k_vaf_sample(int n, int per_wg, i
       }
       sys_a += a; sys_b += b;
       const unsigned long long pending = __ballot(have);
-      vaf_add_classes(pending, 1 + g, a, b, row);
-      vaf_add_classes(pending, 1 + ngroup + s, a, b, row);
+      const double ab[2] = {a, b};
+      vaf_add_classes<2>(pending, 1 + g, ab, row);
+      vaf_add_classes<2>(pending, 1 + ngroup + s, ab, row);
    }
    sys_a = wave_sum_dpp(sys_a); sys_b = wave_sum_dpp(sys_b);
    if ((threadIdx.x & 63) == 0) { row[0] = sys_a; row[1] = sys_b; }

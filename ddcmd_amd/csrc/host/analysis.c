@@ -233,14 +233,126 @@ static void vaf_output(SIMULATE *simulate, const ddcmi_analysis *an, void *state
 }
 static void vaf_free(void *state) { VAFSTATE *p = state; free(p->vaf0); free(p->msd0); free(p->vaf_); free(p->msd_); free(p->buf); free(p); }
 
+/* ANALYSIS type vcmWrite (vcmWrite.c: parms :23-64, output :71-136, close :142-146): the centre-of-mass velocity of the system, of
+ * every group and of every species -- every block, a single group's and a single species' too -- one line per output into a file of
+ * the run directory that rank 0 opens for append, with a header line, at init.  The sums come from the device
+ * (ddcmi_momentum_by_class) and are added over the ranks in rank order.  eval does nothing; there is no clear. */
+#define LOOP_WIDTH 12      /* loopFormatSize: the width printinfo writes the data file's loop column with (plugin.c) */
+typedef struct { FILE *file; int ng, ncl; double *buf; } VCMSTATE;
+static void vcm_parms(const OBJECT *obj, ddcmi_analysis *an, char *msg, int msglen) { (void)obj; (void)an; (void)msg; (void)msglen; }
+static void *vcm_init(SIMULATE *simulate, const ddcmi_analysis *an)
+{
+   const ddcmi_setup *s = simulate->setup;
+   VCMSTATE *p = zalloc(1, sizeof(VCMSTATE));
+   p->ng = s->ngroup > 0 ? s->ngroup : 1; p->ncl = 1 + p->ng + s->nspecies;
+   p->buf = zalloc(4 * (size_t)p->ncl, sizeof(double));
+   if (par.rank == 0)
+   {
+      p->file = fopen(an->filename, "a");
+      if (!p->file) die("vcmWrite_parms", "cannot open the output file");
+      char fmt[32]; snprintf(fmt, sizeof(fmt), "-%%%ds %%14s", LOOP_WIDTH);      /* (the reference's format as it stands, its leading '-' outside the conversion) */
+      fprintf(p->file, fmt, "#loop", "time(fs)");
+      fprintf(p->file, "%-51s", "     System vx vy vz (Ang/fs)");
+      for (int ii = 0; ii < p->ng; ii++)
+      {
+         char temp[300]; snprintf(temp, sizeof(temp), "     Group %s vx vy vz (Ang/fs)", s->ngroup > 0 ? s->group_name[ii] : "group");
+         fprintf(p->file, "%-51s", temp);
+      }
+      for (int ii = 0; ii < s->nspecies; ii++)
+      {
+         char temp[300]; snprintf(temp, sizeof(temp), "     Species %s vx vy vz (Ang/fs)", s->species_name[ii]);
+         fprintf(p->file, "%-51s", temp);
+      }
+      fprintf(p->file, "\n");
+      fflush(p->file);
+   }
+   return p;
+}
+static void vcm_eval(SIMULATE *simulate, const ddcmi_analysis *an, void *state) { (void)simulate; (void)an; (void)state; }
+static void vcm_output(SIMULATE *simulate, const ddcmi_analysis *an, void *state)
+{
+   (void)an;
+   VCMSTATE *p = state;
+   ddcmi_ctx *ctx = simulate->accelerator->parms;
+   double *mv = p->buf, *m = p->buf + 3 * p->ncl;
+   if (ddcmi_momentum_by_class(ctx, p->ng, simulate->setup->nspecies, mv, m) != DDCMI_OK) die("vcmWrite_output", ddcmi_last_error(ctx));
+   sum_over_ranks(p->buf, 4 * p->ncl, "vcmWrite_output");
+   if (par.rank != 0) return;
+   const double time = units_convert(1.0, NULL, "fs") * simulate->time, velocity_convert = units_convert(1.0, NULL, "Ang/fs");
+   fprintf(p->file, "%*" PRId64, LOOP_WIDTH, simulate->loop);
+   fprintf(p->file, " %16.6f", time);
+   for (int ii = 0; ii < p->ncl; ii++)
+   {
+      double v[3] = {mv[3 * ii], mv[3 * ii + 1], mv[3 * ii + 2]};
+      if (m[ii] > 0.0) { const double r = 1 / m[ii]; v[0] *= r; v[1] *= r; v[2] *= r; }      /* VSCALE(vmsum[ii], 1/msum[ii]) */
+      for (int a = 0; a < 3; a++) v[a] *= velocity_convert;
+      fprintf(p->file, " %16.6e %16.6e %16.6e", v[0], v[1], v[2]);
+   }
+   fprintf(p->file, "\n");
+   fflush(p->file);
+}
+static void vcm_free(void *state) { VCMSTATE *p = state; if (p->file) fclose(p->file); free(p->buf); free(p); }
+
+/* ANALYSIS type zdensity (zdensity.c: parms :36-50, output :56-175): the beads' density profile along z, orthorhombic boxes.  The
+ * histogram comes from the device (ddcmi_zdensity: at most 2048 bins), is added over the ranks in rank order, and rank 0 writes
+ * snapshot.<loop>/<filename>.  eval does nothing; there is no clear.  nz < 1 (the reference writes an empty file) is refused. */
+typedef struct { double *density; } ZDSTATE;
+static void zd_parms(const OBJECT *obj, ddcmi_analysis *an, char *msg, int msglen)
+{
+   char *sm = NULL;
+   object_get(obj, "nz", &an->nz, INT, 1, "0");
+   object_get(obj, "smearRadius", &an->smear_radius, WITH_UNITS, 1, "0", "l", NULL);
+   object_get(obj, "smearMethod", &sm, STRING, 1, "impulse");
+   an->smear_method = sm && strcasecmp(sm, "hat") == 0;      /* anything else is impulse */
+   free(sm);
+   if (an->nz < 1) snprintf(msg, msglen, "ANALYSIS %s: nz = %d", an->name, an->nz);
+}
+static void *zd_init(SIMULATE *simulate, const ddcmi_analysis *an)
+{
+   (void)simulate;
+   ZDSTATE *p = zalloc(1, sizeof(ZDSTATE));
+   p->density = zalloc(an->nz, sizeof(double));
+   return p;
+}
+static void zd_eval(SIMULATE *simulate, const ddcmi_analysis *an, void *state) { (void)simulate; (void)an; (void)state; }
+static void zd_output(SIMULATE *simulate, const ddcmi_analysis *an, void *state)
+{
+   ZDSTATE *p = state;
+   ddcmi_ctx *ctx = simulate->accelerator->parms;
+   const int nz = an->nz;
+   if (ddcmi_zdensity(ctx, nz, an->smear_radius, an->smear_method, p->density) != DDCMI_OK) die("zdensity_output", ddcmi_last_error(ctx));
+   sum_over_ranks(p->density, nz, "zdensity_output");
+   if (par.rank != 0) return;
+   FILE *f = snapshot_fopen(simulate, an->filename, "zdensity_output");
+   double h[9];
+   if (ddcmi_get_box(ctx, h) != DDCMI_OK) die("zdensity_output", ddcmi_last_error(ctx));
+   const double lc = units_convert(1.0, NULL, "Angstrom");
+   const double boxVol = (h[0] * h[4] * h[8]) * lc * lc * lc, bz = h[8];
+   for (int ii = 0; ii < nz; ii++)
+   {
+      const double z = ((ii + 0.5) * (bz / nz)) / (bz);
+      const double dens = p->density[ii] * (nz / boxVol);
+      fprintf(f, "%f %f %f\n", z, dens, p->density[ii]);
+   }
+   fclose(f);
+}
+static void zd_free(void *state) { ZDSTATE *p = state; free(p->density); free(p); }
+
 /* ------------------------------------------------------------------------- */
 static const ANALYSIS_TYPE types[] = {      /* indexed by enum ddcmi_analysis_kind; DDCMI_AN_NONE has no row */
    [DDCMI_AN_PAIRCORRELATION] = {"PAIRCORRELATION", DDCMI_AN_PAIRCORRELATION, "paircorrelation.dat", pc_parms, pc_init, pc_eval, pc_output, pc_clear, pc_free},
    [DDCMI_AN_VAF] = {"VELOCITYAUTOCORRELATION", DDCMI_AN_VAF, "vaf.dat", vaf_parms, vaf_init, vaf_eval, vaf_output, NULL, vaf_free},
+   [DDCMI_AN_VCMWRITE] = {"vcmWrite", DDCMI_AN_VCMWRITE, "vcm.data", vcm_parms, vcm_init, vcm_eval, vcm_output, NULL, vcm_free, 1, "vcm_write"},
+   [DDCMI_AN_ZDENSITY] = {"zdensity", DDCMI_AN_ZDENSITY, "zden.dat", zd_parms, zd_init, zd_eval, zd_output, NULL, zd_free, 1, NULL},
 };
 const ANALYSIS_TYPE *analysis_type_find(const char *type_name)
 {
-   for (size_t t = 1; t < sizeof(types) / sizeof(types[0]); t++) if (strncasecmp(type_name, types[t].prefix, strlen(types[t].prefix)) == 0) return &types[t];
+   for (size_t t = 1; t < sizeof(types) / sizeof(types[0]); t++)
+   {
+      const ANALYSIS_TYPE *row = &types[t];
+      if (!row->full_name) { if (strncasecmp(type_name, row->prefix, strlen(row->prefix)) == 0) return row; }
+      else if (strcasecmp(type_name, row->prefix) == 0 || (row->alias && strcasecmp(type_name, row->alias) == 0)) return row;
+   }
    return NULL;
 }
 

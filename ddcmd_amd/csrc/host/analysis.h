@@ -5,7 +5,8 @@
 #include "plugin.h"
 #include "object.h"
 
-/* a row of the table.  `prefix` is matched against the head of the type name, in any case (analysis.c:178) */
+/* a row of the table.  `prefix` is matched against the head of the type name, in any case (analysis.c:178) -- or, with `full_name`
+ * set, against the whole type name and against `alias` (analysis.c:240,317: vcmWrite | vcm_write, zdensity) */
 typedef struct analysis_type_st
 {
    const char *prefix;
@@ -18,6 +19,8 @@ typedef struct analysis_type_st
    void (*output)(SIMULATE *simulate, const ddcmi_analysis *an, void *state);
    void (*clear)(SIMULATE *simulate, const ddcmi_analysis *an, void *state);      /* NULL: analysis_NULL of the reference */
    void (*free)(void *state);
+   int full_name;                                          /* the whole type name must match, not its head */
+   const char *alias;                                      /* a second spelling (full_name rows), or NULL */
 } ANALYSIS_TYPE;
 const ANALYSIS_TYPE *analysis_type_find(const char *type_name);      /* NULL: not supported */
 

@@ -19,7 +19,7 @@ enum { DDCMI_GROUP_FREE = 0, DDCMI_GROUP_BERENDSEN = 1, DDCMI_GROUP_LANGEVIN = 2
 
 /* one ANALYSIS object (analysis_init, analysis.c:120-160).  type: the row of host/analysis.c's table that evaluates it; DDCMI_AN_NONE is any
  * other type (not supported: the driver names it once on stderr) */
-enum ddcmi_analysis_kind { DDCMI_AN_NONE = 0, DDCMI_AN_PAIRCORRELATION, DDCMI_AN_VAF };
+enum ddcmi_analysis_kind { DDCMI_AN_NONE = 0, DDCMI_AN_PAIRCORRELATION, DDCMI_AN_VAF, DDCMI_AN_VCMWRITE, DDCMI_AN_ZDENSITY };
 typedef struct ddcmi_analysis
 {
    char *name, *type_name;
@@ -29,6 +29,8 @@ typedef struct ddcmi_analysis
    int length;                  /* PAIRCORRELATION (paircorrelation.c:68-135): bins; VELOCITYAUTOCORRELATION (velocityAutocorrelation.c:59-60): samples per window behind the origin (>= 1) */
    int rscale_log, method;      /* from here on PAIRCORRELATION only, zero otherwise.  method: 0 geom, 1 grid, 2 neighborList (all evaluated the same way: exactly) */
    double rmin, delta_r;        /* internal length units */
+   int nz, smear_method;        /* from here on zdensity only (zdensity.c:36-50), zero otherwise.  nz: bins along z (>= 1); smear_method: 0 impulse, 1 hat */
+   double smear_radius;         /* internal length units; <= 0: no smearing */
 } ddcmi_analysis;
 
 typedef struct ddcmi_setup

@@ -181,7 +181,7 @@ def load_deck(object_file, restart_file=None, extra_objects=None):
         s.integrator_type = c.integrator_type.decode()
         s.accelerator_type = c.accelerator_type.decode()
         s.units = {k: getattr(c, "u_" + k).decode() for k in ("pressure", "volume", "temperature", "energy", "time", "length")}
-        # SIMULATE analysis = ...: one dict per ANALYSIS object, in list order (types PAIRCORRELATION and VELOCITYAUTOCORRELATION with their parameters, internal units)
+        # SIMULATE analysis = ...: one dict per ANALYSIS object, in list order (types PAIRCORRELATION, VELOCITYAUTOCORRELATION, vcmWrite and zdensity with their parameters, internal units)
         s.analysis = []
         for a in (c.analysis[i] for i in range(int(c.nanalysis))):
             d = {"name": a.name.decode(), "type": (a.type_name or b"").decode(), "eval_rate": int(a.eval_rate), "outputrate": int(a.outputrate),
@@ -191,6 +191,8 @@ def load_deck(object_file, restart_file=None, extra_objects=None):
             if a.type == _lib.AN_PAIRCORRELATION:
                 d.update(delta_r=float(a.delta_r), rmin=float(a.rmin), rscale="log" if a.rscale_log else "normal",
                          method=("geom", "grid", "neighborList")[a.method])
+            if a.type == _lib.AN_ZDENSITY:
+                d.update(nz=int(a.nz), smear_radius=float(a.smear_radius), smear_method=("impulse", "hat")[a.smear_method])
             s.analysis.append(d)
     finally:
         lib.ddcmi_setup_free(p)

@@ -29,6 +29,11 @@ def _i(a):
     return a.ctypes.data_as(_ip) if a is not None else None
 
 
+def _smear_method(m):
+    """zdensity's smearMethod as ddcmi_zdensity takes it: an int as it is, "hat" in any case 1, every other word 0 (zdensity.c:45-48)"""
+    return int(m) if isinstance(m, (int, np.integer)) else int(str(m).lower() == "hat")
+
+
 def _declare(lib):
     if getattr(lib, "_ddcmi_declared", False):
         return
@@ -104,6 +109,8 @@ def _declare(lib):
     lib.ddcmi_vaf_origin.argtypes = [vp]
     lib.ddcmi_vaf_sample.argtypes = [vp, ctypes.c_int, ctypes.c_int, _dp, _dp]
     lib.ddcmi_vaf_clear.argtypes = [vp]
+    lib.ddcmi_momentum_by_class.argtypes = [vp, ctypes.c_int, ctypes.c_int, _dp, _dp]
+    lib.ddcmi_zdensity.argtypes = [vp, ctypes.c_int, ctypes.c_double, ctypes.c_int, _dp]
     lib._ddcmi_declared = True
 
 
@@ -555,6 +562,21 @@ class MartiniHIP(object):
         """tracking off, the reference records released (ddcmi_vaf_clear)"""
         self._chk(self.lib.ddcmi_vaf_clear(self.ctx))
 
+    def momentum_by_class(self):
+        """ANALYSIS vcmWrite's sums of this rank (ddcmi_momentum_by_class): (mv[nclass, 3], m[nclass]) = sum m v and sum m in internal
+        units for the system, every group, every species -- class 0, 1 + g, 1 + ngroup + s"""
+        ng, ns = max(1, int(self.s.ngroup)), int(self.s.nspecies)
+        mv, m = np.zeros((1 + ng + ns, 3)), np.zeros(1 + ng + ns)
+        self._chk(self.lib.ddcmi_momentum_by_class(self.ctx, ng, ns, _d(mv), _d(m)))
+        return mv, m
+
+    def zdensity(self, nz, smear_radius=0.0, smear_method="impulse"):
+        """ANALYSIS zdensity's histogram of this rank (ddcmi_zdensity): density[nz] weights along z; smear_radius in internal
+        length units (<= 0: one bin per bead), smear_method "impulse" or "hat" (anything else is impulse)"""
+        density = np.zeros(max(1, int(nz)))
+        self._chk(self.lib.ddcmi_zdensity(self.ctx, int(nz), float(smear_radius), _smear_method(smear_method), _d(density)))
+        return density
+
     def download(self, mask=POS | VEL | FORCE):
         n = self.n
         out = [np.zeros(n) for _ in range(9)]
@@ -644,6 +666,8 @@ def _declare_domains(lib):
     lib.ddcmi_group_vaf_origin.argtypes = [ctypes.POINTER(vp), ctypes.c_int]
     lib.ddcmi_group_vaf_clear.argtypes = [ctypes.POINTER(vp), ctypes.c_int]
     lib.ddcmi_group_vaf_sample.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp]
+    lib.ddcmi_group_momentum_by_class.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp]
+    lib.ddcmi_group_zdensity.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, _dp]
     lib._ddcmi_dom_declared = True
 
 
@@ -815,6 +839,30 @@ class MartiniGroup(object):
             tv += vaf[r]
             tm += msd[r]
         return tv, tm
+
+    def momentum_by_class(self, per_rank=False):
+        """ddcmi_group_momentum_by_class: the domains' (mv, m) summed in rank order -- or, per_rank, stacked [rank, class, ...]"""
+        ng, ns = max(1, int(self.s.ngroup)), int(self.s.nspecies)
+        mv, m = np.zeros((self.n, 1 + ng + ns, 3)), np.zeros((self.n, 1 + ng + ns))
+        self._chk(self.lib.ddcmi_group_momentum_by_class(self.arr, self.n, ng, ns, _d(mv), _d(m)))
+        if per_rank:
+            return mv, m
+        tv, tm = mv[0].copy(), m[0].copy()
+        for r in range(1, self.n):
+            tv += mv[r]
+            tm += m[r]
+        return tv, tm
+
+    def zdensity(self, nz, smear_radius=0.0, smear_method="impulse", per_rank=False):
+        """ddcmi_group_zdensity: the domains' histograms summed in rank order -- or, per_rank, stacked [rank, bin]"""
+        density = np.zeros((self.n, max(1, int(nz))))
+        self._chk(self.lib.ddcmi_group_zdensity(self.arr, self.n, int(nz), float(smear_radius), _smear_method(smear_method), _d(density)))
+        if per_rank:
+            return density
+        tot = density[0].copy()
+        for r in range(1, self.n):
+            tot += density[r]
+        return tot
 
     def energies(self):
         """sum over ranks = energyInfo.c allreduce()"""

@@ -259,6 +259,19 @@ int ddcmi_vaf_sample(ddcmi_ctx *ctx, int ngroup, int nspecies, double *vaf, doub
  * run every rank calls it at the same point of the run, as with the origin: the migration records carry the reference record
  * while tracking is on, and sender and receiver must agree on that. */
 int ddcmi_vaf_clear(ddcmi_ctx *ctx);
+/* ANALYSIS vcmWrite and zdensity on the device: one read-only pass over the owned beads each.  Both read the state that a download
+ * returns at this point of the run, change nothing of it (a run with calls and one without are bit for bit the same), need no
+ * communication and give identical bits when repeated; a domain that holds no bead gives zeros.
+ * vcmWrite_output's sums (vcmWrite.c:95-110) over this rank's beads, internal units: mv[3 c .. 3 c + 2] = sum m v, m[c] = sum m, class c = 0 the
+ * system, 1 + g group g, 1 + ngroup + s species s ([1 + ngroup + nspecies] classes, at most 512).  m is the species' mass of
+ * ddcmi_set_species, the one the integrator's kick uses.  ngroup and nspecies must be the context's.  Sums over ranks are the global
+ * sums; no communication.  Changes nothing of the run. [sync] */
+int ddcmi_momentum_by_class(ddcmi_ctx *ctx, int ngroup, int nspecies, double *mv, double *m);
+/* zdensity_output's histogram (zdensity.c:66-151) over this rank's beads: density[nz] weights, 1 <= nz <= 2048.  smear_radius <= 0: one bin per bead,
+ * weight 1 (the sums are integers, exact at any bead count).  smear_radius > 0 (internal length): two neighbouring bins per bead,
+ * smear_method 0 impulse, 1 hat.  The positions are binned as a download returns them, without a further wrap: a bead outside
+ * the box lands where the reference's clamp puts it (bin nz - 1 in general).  Sums over ranks are the global histogram. [sync] */
+int ddcmi_zdensity(ddcmi_ctx *ctx, int nz, double smear_radius, int smear_method, double *density);
 
 /* ---- introspection / measurement ------------------------------------------- */
 /* list statistics of the last build: stats[0]=stored full-list entries,

@@ -59,6 +59,10 @@ int ddcmi_group_pair_correlation(ddcmi_ctx **ctxs, int n, double rmin, double de
 int ddcmi_group_vaf_origin(ddcmi_ctx **ctxs, int n);
 int ddcmi_group_vaf_clear(ddcmi_ctx **ctxs, int n);
 int ddcmi_group_vaf_sample(ddcmi_ctx **ctxs, int n, int ngroup, int nspecies, double *vaf, double *msd);
+/* ddcmi_momentum_by_class / ddcmi_zdensity for an in-process group: every domain's own result, domain after domain --
+ * mv[r*3*nclass ...], m[r*nclass ...] and density[r*nz ...] for domain r */
+int ddcmi_group_momentum_by_class(ddcmi_ctx **ctxs, int n, int ngroup, int nspecies, double *mv, double *m);
+int ddcmi_group_zdensity(ddcmi_ctx **ctxs, int n, int nz, double smear_radius, int smear_method, double *density);
 /* the lean step (a single domain of FREE beads without bonded terms: one launch per step, the second stage of its energy / virial /
  * kinetic sums formed for all pending steps at once): the sums of the steps of the last such launch, 32 doubles per step --
  * {lj, ele, virial xx yy zz xy xz yz} as the full list counts them (twice), {rk, tion xx yy zz xy xz yz}, 0, the bonded kernels'

@@ -1,0 +1,81 @@
+#!/usr/bin/env python3
+"""ANALYSIS vcmWrite and zdensity on the headline boxes: what one call of each entry point costs, beside one ddcmi_vaf_sample and
+one plain step of the same box in the same process.
+   python3 tools/time_census.py [water:<lattice> | lipid:<x,y,z>] ...   (default: water:102 lipid:12,12,6 -- 4.24 M and 2.04 M beads)
+Every call is timed by HIP events recorded on the context's stream around it (the kernels and the copy of the result; median of
+20 after 3 warm-up calls), with the host clock around the [sync] call next to it; the step is the mean of 200 steps after 50
+(rebuilds included), host clock.  Bytes read per bead: momentum 24 (velocity) + 8 (group, species words); zdensity 32 (the position
+record); the VAF sample 32 + 24 + 48 + 8."""
+import ctypes, os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import ddcmd_amd
+from ddcmd_amd.martini import MartiniHIP
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+hip = ctypes.CDLL("libamdhip64.so")
+vp = ctypes.c_void_p
+hip.hipEventCreate.argtypes = [ctypes.POINTER(vp)]
+hip.hipEventRecord.argtypes = [vp, vp]
+hip.hipEventSynchronize.argtypes = [vp]
+hip.hipEventElapsedTime.argtypes = [ctypes.POINTER(ctypes.c_float), vp, vp]
+
+
+def system(spec):
+    kind, arg = spec.split(":")
+    if kind == "water":
+        return ddcmd_amd.make_water_setup(int(arg)), "water"
+    from ddcmd_amd.deck import load_deck
+    from ddcmd_amd.synth import replicate_setup
+    deck = os.path.join(ROOT, "tests", "golden", "lipid_deck")
+    s = load_deck(os.path.join(deck, "object_nvt.data"), restart_file=os.path.join(deck, "relaxed", "restart"))
+    return replicate_setup(s, tuple(int(x) for x in arg.split(","))), "bilayer"
+
+
+def timed(m, call, e0, e1, reps=20, warm=3):
+    """(median ms by events, min, median ms on the host clock)"""
+    stream = m.lib.ddcmi_stream(m.ctx)
+    for _ in range(warm):
+        call()
+    host, dev = [], []
+    for _ in range(reps):
+        hip.hipEventRecord(e0, stream)
+        t0 = time.perf_counter()
+        call()
+        host.append(time.perf_counter() - t0)
+        hip.hipEventRecord(e1, stream)
+        hip.hipEventSynchronize(e1)
+        ms = ctypes.c_float(0)
+        hip.hipEventElapsedTime(ctypes.byref(ms), e0, e1)
+        dev.append(ms.value)
+    return float(np.median(dev)), min(dev), 1e3 * float(np.median(host))
+
+
+for spec in (sys.argv[1:] or ["water:102", "lipid:12,12,6"]):
+    s, name = system(spec)
+    m = MartiniHIP(s)
+    m.eval_forces()
+    m.group_temperatures()
+    m.step(50)
+    m.sync()
+    t0 = time.perf_counter()
+    m.step(200)
+    m.sync()
+    step_ms = 1e3 * (time.perf_counter() - t0) / 200
+    m.vaf_origin()
+    m.step(10)
+    e0, e1 = vp(), vp()
+    assert hip.hipEventCreate(ctypes.byref(e0)) == 0 and hip.hipEventCreate(ctypes.byref(e1)) == 0
+    smear = ddcmd_amd.units_convert(1.0, "Angstrom", None)
+    rows = [("ddcmi_vaf_sample", 32 + 24 + 48 + 8, m.vaf_sample),
+            ("ddcmi_momentum_by_class", 24 + 8, m.momentum_by_class),
+            ("ddcmi_zdensity nz=300", 32, lambda: m.zdensity(300)),
+            ("ddcmi_zdensity nz=300 hat 1 A", 32, lambda: m.zdensity(300, smear, "hat")),
+            ("ddcmi_zdensity nz=2048", 32, lambda: m.zdensity(2048))]
+    print("%s: %d beads, %d groups, %d species; one plain step %.4f ms" % (name, s.natoms, max(1, s.ngroup), s.nspecies, step_ms), flush=True)
+    for label, bpb, call in rows:
+        med, lo, host = timed(m, call, e0, e1)
+        nbytes = s.natoms * bpb
+        print("  %-32s %8.4f ms by events (min %.4f; host clock %.4f ms)  %.3f GB read, %.2f TB/s = %.0f %% of 8 TB/s"
+              % (label, med, lo, host, nbytes / 1e9, nbytes / (1e-3 * med) / 1e12, 100 * nbytes / (1e-3 * med) / 8e12), flush=True)
+    m.close()
