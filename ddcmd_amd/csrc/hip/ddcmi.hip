@@ -588,6 +588,9 @@ extern "C" int ddcmi_set_species(ddcmi_ctx *ctx, int nspecies, const double *mas
       if (!(mass[s] > 0)) SETERR(ctx, DDCMI_EINVAL, "species %d has non-positive mass", s);      /* (before anything is kept: a refused call changes nothing) */
       if (charge && !std::isfinite(charge[s])) SETERR(ctx, DDCMI_EINVAL, "species %d: charge %g is not finite", s, charge[s]);
    }
+   /* the beads of the uploaded state keep their species: the kick reads invmass[species[i]], the kinetic sums massv[species[i]] */
+   if (ctx->nloc > 0 && nspecies <= ctx->max_species)
+      SETERR(ctx, DDCMI_EINVAL, "ddcmi_set_species: %d species, the uploaded state holds beads of species %d (upload a state that fits first)", nspecies, ctx->max_species);
    (void)hipSetDevice(ctx->device);
    ctx->nspecies = nspecies;
    ctx->mass.assign(mass, mass + nspecies);
@@ -774,13 +777,18 @@ extern "C" int ddcmi_set_groups(ddcmi_ctx *ctx, int ngroup, const int *type, con
       if (type[g] == DDCMI_LANGEVIN && Teq && !(Teq[g] >= 0.0 && std::isfinite(Teq[g]))) SETERR(ctx, DDCMI_EINVAL, "group %d: LANGEVIN needs a finite Teq >= 0", g);
       if (type[g] == DDCMI_LANGEVIN && tau && !std::isfinite(tau[g])) SETERR(ctx, DDCMI_EINVAL, "group %d: LANGEVIN needs a finite tau > 0", g);
    }
+   /* (every check before anything is kept: a refused call changes nothing -- until this was so, a refused call had already replaced the thermostat, and one
+    *  with a larger count left ngroup ahead of the Berendsen scalars' vectors, which the next step then wrote past) */
+   for (int g = 0; g < ngroup; g++)
+   {
+      if (type[g] != DDCMI_FREE && type[g] != DDCMI_BERENDSEN && type[g] != DDCMI_LANGEVIN) SETERR(ctx, DDCMI_EUNSUPPORTED, "group %d: only FREE, BERENDSEN and LANGEVIN groups are supported", g);
+      if (type[g] == DDCMI_LANGEVIN && (!tau || !(tau[g] > 0.0) || !Teq)) SETERR(ctx, DDCMI_EINVAL, "group %d: LANGEVIN needs Teq and tau > 0", g);
+   }
    ctx->ngroup = ngroup;
    ctx->gtype.assign(type, type + ngroup);
    ctx->gTeq.assign(ngroup, 0.0); ctx->gtau.assign(ngroup, 0.0); ctx->ginterval.assign(ngroup, 1);
    for (int g = 0; g < ngroup; g++)
    {
-      if (type[g] != DDCMI_FREE && type[g] != DDCMI_BERENDSEN && type[g] != DDCMI_LANGEVIN) SETERR(ctx, DDCMI_EUNSUPPORTED, "group %d: only FREE, BERENDSEN and LANGEVIN groups are supported", g);
-      if (type[g] == DDCMI_LANGEVIN && (!tau || !(tau[g] > 0.0) || !Teq)) SETERR(ctx, DDCMI_EINVAL, "group %d: LANGEVIN needs Teq and tau > 0", g);
       if (Teq) ctx->gTeq[g] = Teq[g];
       if (tau) ctx->gtau[g] = tau[g];
       if (interval && interval[g] > 0) ctx->ginterval[g] = interval[g];
@@ -944,7 +952,7 @@ extern "C" int ddcmi_upload_state(ddcmi_ctx *ctx, int nlocal, const double *rx, 
    for (auto b : i1) ENSURE(ctx, *b, n + 1);
    if (n == 0)
    {
-      ctx->nloc = 0; ctx->nhalo = 0; ctx->npad = DDCMI_BLOCK; ctx->self_ele = 0.0; ctx->sp_count.assign(ctx->nspecies, 0);
+      ctx->nloc = 0; ctx->nhalo = 0; ctx->npad = DDCMI_BLOCK; ctx->self_ele = 0.0; ctx->sp_count.assign(ctx->nspecies, 0); ctx->max_species = -1;
       ctx->list_valid = false; ctx->forces_valid = false;
       return DDCMI_OK;
    }
@@ -987,7 +995,8 @@ extern "C" int ddcmi_upload_state(ddcmi_ctx *ctx, int nlocal, const double *rx, 
    ctx->npad = cdiv(n, DDCMI_BLOCK) * DDCMI_BLOCK;
    /* self electrostatic term -1/2 sum q_i^2 keR crf over local atoms (bioMartini.c:1030-1035) */
    ctx->sp_count.assign(ctx->nspecies, 0);
-   for (int i = 0; i < n; i++) ctx->sp_count[species[i]]++;
+   ctx->max_species = -1;
+   for (int i = 0; i < n; i++) { ctx->sp_count[species[i]]++; ctx->max_species = std::max(ctx->max_species, species[i]); }
    {
       double q2 = 0.0;      /* (in bead order, as every round summed it: decomposed ranks keep this value until their first rebuild) */
       for (int i = 0; i < n; i++) { double q = ctx->charge[species[i]]; q2 += q * q; }

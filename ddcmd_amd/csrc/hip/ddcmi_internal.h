@@ -317,6 +317,7 @@ struct ddcmi_ctx
    /* growable pinned host staging (so that small copies are truly asynchronous): [0] tile work, [1] tile order, [2] count exchange */
    hbuf h_pin[3];
    int *pinned(int which, size_t n) { return h_pin[which].ensure(n, n / 4 + 64) ? nullptr : h_pin[which].h; }
+   int max_species = -1;               /* largest species id of the last ddcmi_upload_state (-1: no bead): ddcmi_set_species keeps its tables longer than that */
    double self_ele = 0.0; std::vector<long> sp_count;      /* sp_count: beads per species of the last ddcmi_upload_state (one domain: the self term follows new charges / constants without the beads) */
    /* what the last rebuild's tail left zeroed for this one (k_rebuild_tail): the cell counters (for this cell count, in these buffers),
     * the flags, the arena counter, the direction counters; a rebuild that cannot rely on it clears them itself */

@@ -67,7 +67,9 @@ const char *ddcmi_version(void);
 /* ---- parameters ------------------------------------------------------------
  * Every setter checks what it is handed -- counts, NULL arrays, offsets (start at 0, never decrease), indices (not negative), constants (finite; rmax > 0,
  * deltaR >= 0, masses > 0, pbc in 0..7) -- and refuses with DDCMI_EINVAL and a message; a refused call changes nothing.  What only a rebuild can know is
- * checked there (molecule types against ddcmi_set_molecules, index-named terms / constraint pairs / molecules against the bead count of the upload).  The
+ * checked there (molecule types against ddcmi_set_molecules, index-named terms / constraint pairs / molecules against the bead count of the upload).  Under
+ * an uploaded state ddcmi_set_species also checks its count against the beads: a table that ends at or below the largest species id of the last
+ * ddcmi_upload_state is refused (the kick would read past it); ddcmi_set_groups checks every group's kind and constants before it keeps any.  The
  * caller's promise that an array is as long as its count says cannot be checked.  New species or nonbonded parameters under an uploaded state invalidate
  * the forces on the device: the next ddcmi_eval_forces rebuilds the class tables, the beads' tags and the list (ddcmi_step_nglf asks for it). */
 /* BOX h (row-major 3x3, orthorhombic) and pbc bitmask: allocGPUBoxInfo */
