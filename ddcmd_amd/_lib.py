@@ -82,7 +82,12 @@ c_u64_p = ctypes.POINTER(ctypes.c_uint64)
 c_char_pp = ctypes.POINTER(ctypes.c_char_p)
 
 
-AN_NONE, AN_PAIRCORRELATION, AN_VAF, AN_VCMWRITE, AN_ZDENSITY = range(5)      # enum ddcmi_analysis_kind
+AN_NONE, AN_PAIRCORRELATION, AN_VAF, AN_VCMWRITE, AN_ZDENSITY, AN_KDIST = range(6)      # enum ddcmi_analysis_kind
+
+
+class CKdistGroup(ctypes.Structure):
+    """Mirror of struct ddcmi_kdist_group (ddcmd_amd/csrc/host/deck.h)."""
+    _fields_ = [("name", ctypes.c_char_p), ("species", ctypes.c_char_p), ("emin", ctypes.c_double), ("emax", ctypes.c_double), ("nbins", ctypes.c_int)]
 
 
 class CAnalysis(ctypes.Structure):
@@ -90,7 +95,8 @@ class CAnalysis(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char_p), ("type_name", ctypes.c_char_p), ("type", ctypes.c_int), ("eval_rate", ctypes.c_int), ("outputrate", ctypes.c_int),
                 ("filename", ctypes.c_char_p), ("length", ctypes.c_int),
                 ("rscale_log", ctypes.c_int), ("method", ctypes.c_int), ("rmin", ctypes.c_double), ("delta_r", ctypes.c_double),
-                ("nz", ctypes.c_int), ("smear_method", ctypes.c_int), ("smear_radius", ctypes.c_double)]
+                ("nz", ctypes.c_int), ("smear_method", ctypes.c_int), ("smear_radius", ctypes.c_double),
+                ("ndist", ctypes.c_int), ("dist", ctypes.POINTER(CKdistGroup))]
 
 
 class CSetup(ctypes.Structure):

@@ -1,10 +1,12 @@
-"""ANALYSIS types PAIRCORRELATION, VELOCITYAUTOCORRELATION, vcmWrite and zdensity on the host side.
+"""ANALYSIS types PAIRCORRELATION, VELOCITYAUTOCORRELATION, vcmWrite, zdensity and KINETICENERGYDISTN on the host side.
 PairCorrelation: accumulation of the device's pair counts into g(r) and the output file, as paircorrelation_eval_geom /
 paircorrelation_output (paircorrelation.c) do.  The counting itself is ddcmi_pair_correlation (Martini*.pair_correlation); nothing
 here searches pairs.
 VelocityAutocorrelation: the windows of velocityAutocorrelation_eval and the file of velocityAutocorrelation_output
 (velocityAutocorrelation.c) over the device's sums (Martini*.vaf_origin / vaf_sample).
-VcmWrite, ZDensity: the file text of vcmWrite.c / zdensity.c from the device's sums (Martini*.momentum_by_class / zdensity)."""
+VcmWrite, ZDensity: the file text of vcmWrite.c / zdensity.c from the device's sums (Martini*.momentum_by_class / zdensity).
+KineticEnergyDistn: the accumulation and the two files of kineticEnergyDistn.c from the device's histograms
+(Martini*.kinetic_energy_distn)."""
 import numpy as np
 
 from .deck import units_convert
@@ -268,3 +270,97 @@ class ZDensity(object):
             z = ((ii + 0.5) * (bz / self.nz)) / bz
             lines.append("%f %f %f\n" % (z, density[ii] * (self.nz / box_vol), density[ii]))
         return "".join(lines)
+
+
+class KineticEnergyDistn(object):
+    """one KINETICENERGYDISTN analysis (kineticEnergyDistn.c).  groups: one dict per BIN object of distGroups, {"name", "species",
+    "emin", "emax", "nbins"} in internal units (load_deck's "dist_groups").  add() takes one evaluation combined over the ranks
+    (Martini*.kinetic_energy_distn: counts and sums added, minimum of minima, maximum of maxima); evaluations accumulate until
+    clear().  dist_text(i) is snapshot.<loop>/<name>_kDist.data of group i, line(loop, time) the line of kinetic.data, header() the
+    line written when that file is opened; the reference clears after writing both."""
+
+    def __init__(self, groups, eval_rate=0, outputrate=0):
+        self.groups = [dict(g) for g in groups]
+        for g in self.groups:
+            if int(g["nbins"]) < 1 or not g["emax"] > g["emin"]:
+                raise ValueError("BIN %s: nBins = %d, emin = %g, emax = %g" % (g.get("name", "?"), g["nbins"], g["emin"], g["emax"]))
+        self.nd = len(self.groups)
+        self.emin = np.array([g["emin"] for g in self.groups], np.float64)
+        self.emax = np.array([g["emax"] for g in self.groups], np.float64)
+        self.nbins = np.array([g["nbins"] for g in self.groups], np.int32)
+        self.offset = np.concatenate([[0], np.cumsum(self.nbins, dtype=np.int64)])
+        self.eval_rate, self.outputrate = int(eval_rate), int(outputrate)
+        self.clear()
+
+    def species_dist(self, species_names):
+        """mapS2D: the group of each species, or -1; the reference asserts that no species is claimed twice"""
+        out = -np.ones(len(species_names), np.int32)
+        for j, g in enumerate(self.groups):
+            if g["species"] in species_names:
+                i = list(species_names).index(g["species"])
+                if out[i] != -1:
+                    raise ValueError("species %s is claimed by two BINs" % g["species"])
+                out[i] = j
+        return out
+
+    def filename(self, i):
+        return "%s_kDist.data" % self.groups[i]["name"]
+
+    def clear(self):
+        self.cnt = np.zeros(int(self.offset[-1]))
+        self.tallies = np.zeros((self.nd, 3))      # cntTotal, subCnt, supCnt
+        self.sum = np.zeros(self.nd)
+        self.min, self.max = np.full(self.nd, 1e300), np.zeros(self.nd)
+
+    def add(self, counts, tallies, stats):
+        stats = np.asarray(stats, np.float64).reshape(self.nd, 3)
+        self.cnt += np.asarray(counts, np.float64).reshape(-1)
+        self.tallies += np.asarray(tallies, np.float64).reshape(self.nd, 3)
+        self.sum += stats[:, 0]
+        self.min = np.where(stats[:, 1] < self.min, stats[:, 1], self.min)
+        self.max = np.where(stats[:, 2] > self.max, stats[:, 2], self.max)
+
+    def header(self):
+        return "# loop  time(fs)   \n"
+
+    def dist_text(self, i):
+        ec = units_convert(1.0, None, "eV")
+        delta = (self.emax[i] - self.emin[i]) / self.nbins[i]
+        cnt = self.cnt[self.offset[i]:self.offset[i + 1]]
+        with np.errstate(all="ignore"):
+            pdf = cnt / (self.tallies[i, 0] * delta) / ec      # (an empty group: 0/0, printed as C prints it)
+        lines = ["%-14s %14s %14s\n" % ("# Energy (eV)", "pdf (1/eV)", "cnt")]
+        for j in range(int(self.nbins[i])):
+            lines.append("%e %e %e\n" % (((j + 0.5) * delta + self.emin[i]) * ec, pdf[j], cnt[j]))
+        return "".join(lines)
+
+    def line(self, loop, time):
+        """time as simulate->time holds it (internal units: the reference converts nothing here)"""
+        ec = units_convert(1.0, None, "eV")
+        row = ""
+        for i in range(self.nd):
+            total = self.tallies[i, 0]
+            ave = self.sum[i] / total if total else 0.0
+            row += "%*d" % (LOOP_WIDTH, int(loop)) + " %16.6f " % time
+            row += "%12.6f %12.8f %12.8f %4.0f %4.0f %8.0f " % (ave * ec, self.min[i] * ec, self.max[i] * ec, self.tallies[i, 1], self.tallies[i, 2], total)
+        return row + "\n"
+
+
+def parse_kdist_output(text):
+    """(energy[nbins] in eV, pdf[nbins] in 1/eV, cnt[nbins]) of a <name>_kDist.data file"""
+    rows = np.array([[float(x) for x in ln.split()] for ln in text.splitlines() if ln.strip() and not ln.startswith("#")]).reshape(-1, 3)
+    return rows[:, 0], rows[:, 1], rows[:, 2]
+
+
+def parse_kinetic_output(text):
+    """one (loop[ngroup], time[ngroup], values[ngroup, 6] = {ave, min, max in eV, subCnt, supCnt, cntTotal}) per output line of
+    kinetic.data (header lines skipped; a line of an analysis without groups is empty)"""
+    out = []
+    for ln in text.splitlines():
+        if ln.startswith("#"):
+            continue
+        w = ln.split()
+        assert len(w) % 8 == 0, ln
+        v = np.array([float(x) for x in w], np.float64).reshape(-1, 8)
+        out.append((v[:, 0].astype(np.int64), v[:, 1], v[:, 2:]))
+    return out

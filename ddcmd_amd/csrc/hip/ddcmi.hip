@@ -1283,3 +1283,4 @@ extern "C" int ddcmi_timing_fused(ddcmi_ctx *ctx, int64_t *launches, double *tot
 #include "ddcmi_analysis.inl"
 #include "ddcmi_vaf.inl"
 #include "ddcmi_census.inl"
+#include "ddcmi_kdist.inl"

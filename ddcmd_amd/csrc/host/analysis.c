@@ -338,12 +338,154 @@ static void zd_output(SIMULATE *simulate, const ddcmi_analysis *an, void *state)
 }
 static void zd_free(void *state) { ZDSTATE *p = state; free(p->density); free(p); }
 
+/* ANALYSIS type KINETICENERGYDISTN (kineticEnergyDistn.c: parms :45-93, eval :157-188, output :98-155, clear :189-203): per BIN object of
+ * distGroups the histogram of one species' kinetic energies.  Every evaluation comes from the device (ddcmi_kinetic_energy_distn: all
+ * groups in one pass), is combined over the ranks -- the counts and the sum of K added in rank order (integers below 2^53: exact),
+ * the minima and maxima by a maximum over the ranks -- and accumulated until the output, where rank 0 writes
+ * snapshot.<loop>/<BIN name>_kDist.data per group and one line of kinetic.data (opened for append, with a header line, at init; the
+ * time stays in internal units, as in the reference), and everything is cleared.  The startup evaluation is cleared as well. */
+typedef struct { FILE *file; int nd, nbt; int *nbins, *map; double *emin, *emax; int64_t *cnt, *tal; double *stats, *buf, *acc, *accmin, *accmax; } KDSTATE;
+static void kd_parms(const OBJECT *obj, ddcmi_analysis *an, char *msg, int msglen)
+{
+   char **names = NULL;
+   const int nd = object_getv(obj, "distGroups", (void **)&names, STRING, IGNORE_IF_NOT_FOUND);
+   an->ndist = nd > 0 ? nd : 0;
+   an->dist = zalloc(an->ndist > 0 ? an->ndist : 1, sizeof(ddcmi_kdist_group));
+   long nbt = 0;
+   for (int j = 0; j < an->ndist; j++)
+   {
+      ddcmi_kdist_group *b = &an->dist[j];
+      b->name = names[j];
+      const OBJECT *og = object_find(b->name, "BIN");
+      if (!og) { b->species = strdup(""); b->nbins = 1; snprintf(msg, msglen, "ANALYSIS %s: distGroups names %s, and there is no BIN object of that name", an->name, b->name); continue; }
+      object_get(og, "species", &b->species, STRING, 1, "");
+      if (!b->species) b->species = strdup("");
+      object_get(og, "emin", &b->emin, WITH_UNITS, 1, "0", "energy", NULL);
+      object_get(og, "emax", &b->emax, WITH_UNITS, 1, "0", "energy", NULL);
+      object_get(og, "nBins", &b->nbins, INT, 1, "1");
+      if (b->nbins < 1) snprintf(msg, msglen, "ANALYSIS %s: BIN %s: nBins = %d", an->name, b->name, b->nbins);
+      else if (!isfinite(b->emin) || !isfinite(b->emax)) snprintf(msg, msglen, "ANALYSIS %s: BIN %s: emin = %g, emax = %g: not finite", an->name, b->name, b->emin, b->emax);
+      else if (!(b->emax > b->emin)) snprintf(msg, msglen, "ANALYSIS %s: BIN %s: emax = %g <= emin = %g", an->name, b->name, b->emax, b->emin);
+      for (int i = 0; i < j; i++)      /* the reference's assert(mapS2D[i] == -1) */
+         if (b->species[0] && an->dist[i].species && strcmp(an->dist[i].species, b->species) == 0)
+         { snprintf(msg, msglen, "ANALYSIS %s: species %s is claimed by BIN %s and by BIN %s", an->name, b->species, an->dist[i].name, b->name); break; }
+      nbt += b->nbins > 0 ? b->nbins : 0;
+   }
+   free(names);
+   if (DDCMI_KDIST_LDS_BYTES((long)an->ndist, nbt) > DDCMI_KDIST_MAX_LDS)
+      snprintf(msg, msglen, "ANALYSIS %s: %ld bins in %d groups need %ld bytes of the device's LDS, at most %d (4 per bin, 108 per group)", an->name, nbt, an->ndist,
+               DDCMI_KDIST_LDS_BYTES((long)an->ndist, nbt), DDCMI_KDIST_MAX_LDS);
+}
+static void kd_clear(SIMULATE *simulate, const ddcmi_analysis *an, void *state)
+{
+   (void)simulate; (void)an;
+   KDSTATE *p = state;
+   memset(p->acc, 0, sizeof(double) * (size_t)(p->nbt + 4 * p->nd));
+   for (int g = 0; g < p->nd; g++) { p->accmin[g] = 1e300; p->accmax[g] = 0.0; }
+}
+static void *kd_init(SIMULATE *simulate, const ddcmi_analysis *an)
+{
+   const ddcmi_setup *s = simulate->setup;
+   KDSTATE *p = zalloc(1, sizeof(KDSTATE));
+   const int nd = p->nd = an->ndist;
+   p->nbins = zalloc(nd + 1, sizeof(int)); p->emin = zalloc(nd + 1, sizeof(double)); p->emax = zalloc(nd + 1, sizeof(double));
+   p->map = zalloc(s->nspecies + 1, sizeof(int));
+   for (int i = 0; i < s->nspecies; i++) p->map[i] = -1;
+   for (int j = 0; j < nd; j++)
+   {
+      p->nbins[j] = an->dist[j].nbins; p->emin[j] = an->dist[j].emin; p->emax[j] = an->dist[j].emax;
+      p->nbt += an->dist[j].nbins;
+      for (int i = 0; i < s->nspecies; i++)
+         if (strcmp(an->dist[j].species, s->species_name[i]) == 0) { p->map[i] = j; break; }      /* (a BIN of a species the system lacks stays empty) */
+   }
+   const size_t nv = (size_t)p->nbt + 4 * nd;
+   p->cnt = zalloc(p->nbt + 1, sizeof(int64_t)); p->tal = zalloc(3 * nd + 1, sizeof(int64_t)); p->stats = zalloc(3 * nd + 1, sizeof(double));
+   p->buf = zalloc(nv + 2 * nd + 1, sizeof(double)); p->acc = zalloc(nv + 1, sizeof(double));
+   p->accmin = zalloc(nd + 1, sizeof(double)); p->accmax = zalloc(nd + 1, sizeof(double));
+   kd_clear(simulate, an, p);
+   if (par.rank == 0)
+   {
+      p->file = fopen("kinetic.data", "a");
+      if (!p->file) die("kineticEnergyDistn_parms", "cannot open kinetic.data");
+      fprintf(p->file, "# loop  time(fs)   \n");
+      fflush(p->file);
+   }
+   return p;
+}
+static void kd_eval(SIMULATE *simulate, const ddcmi_analysis *an, void *state)
+{
+   (void)an;
+   KDSTATE *p = state;
+   ddcmi_ctx *ctx = simulate->accelerator->parms;
+   const int nd = p->nd, nbt = p->nbt, nv = nbt + 4 * nd;
+   if (nd == 0) return;
+   if (ddcmi_kinetic_energy_distn(ctx, simulate->setup->nspecies, nd, p->emin, p->emax, p->nbins, p->map, p->cnt, p->tal, p->stats) != DDCMI_OK)
+      die("kineticEnergyDistn_eval", ddcmi_last_error(ctx));
+   double *mm = p->buf + nv;      /* {-min, max} of every group: both go by a maximum over the ranks */
+   for (int k = 0; k < nbt; k++) p->buf[k] = (double)p->cnt[k];
+   for (int g = 0; g < nd; g++)
+   {
+      for (int q = 0; q < 3; q++) p->buf[nbt + 4 * g + q] = (double)p->tal[3 * g + q];
+      p->buf[nbt + 4 * g + 3] = p->stats[3 * g];
+      mm[g] = -p->stats[3 * g + 1]; mm[nd + g] = p->stats[3 * g + 2];
+   }
+   sum_over_ranks(p->buf, nv, "kineticEnergyDistn_eval");
+   if (par.world > 1 && ddcmi_rdzv_allreduce_f64(par.rdzv, mm, 2 * nd, 1) != DDCMI_OK) die("kineticEnergyDistn_eval", ddcmi_rdzv_last_error(par.rdzv));
+   for (int k = 0; k < nv; k++) p->acc[k] += p->buf[k];
+   for (int g = 0; g < nd; g++)
+   {
+      if (-mm[g] < p->accmin[g]) p->accmin[g] = -mm[g];
+      if (mm[nd + g] > p->accmax[g]) p->accmax[g] = mm[nd + g];
+   }
+}
+static void kd_output(SIMULATE *simulate, const ddcmi_analysis *an, void *state)
+{
+   KDSTATE *p = state;
+   if (par.rank == 0)
+   {
+      const double eC = units_convert(1.0, NULL, "eV");
+      int off = 0;
+      for (int i = 0; i < p->nd; i++)
+      {
+         char filename[600];
+         snprintf(filename, sizeof(filename), "%s_kDist.data", an->dist[i].name);
+         FILE *f = snapshot_fopen(simulate, filename, "kineticEnergyDistn_output");
+         fprintf(f, "%-14s %14s %14s\n", "# Energy (eV)", "pdf (1/eV)", "cnt");
+         const double *t = p->acc + p->nbt + 4 * i;      /* cntTotal, subCnt, supCnt, sum K */
+         const double cntTotal = t[0], minValue = p->emin[i], delta = (p->emax[i] - p->emin[i]) / p->nbins[i];
+         for (int j = 0; j < p->nbins[i]; j++)
+         {
+            const double cnt = p->acc[off + j];
+            const double energy = ((j + 0.5) * delta + minValue) * eC;
+            const double pdf = cnt / (cntTotal * delta) / eC;
+            fprintf(f, "%e %e %e\n", energy, pdf, cnt);
+         }
+         fclose(f);
+         off += p->nbins[i];
+         const double ave = cntTotal ? t[3] / cntTotal : 0.0;
+         fprintf(p->file, "%*" PRId64, LOOP_WIDTH, simulate->loop);
+         fprintf(p->file, " %16.6f ", simulate->time);
+         fprintf(p->file, "%12.6f %12.8f %12.8f %4.0f %4.0f %8.0f ", ave * eC, p->accmin[i] * eC, p->accmax[i] * eC, t[1], t[2], cntTotal);
+      }
+      fprintf(p->file, "\n");
+      fflush(p->file);
+   }
+   kd_clear(simulate, an, p);
+}
+static void kd_free(void *state)
+{
+   KDSTATE *p = state;
+   if (p->file) fclose(p->file);
+   free(p->nbins); free(p->map); free(p->emin); free(p->emax); free(p->cnt); free(p->tal); free(p->stats); free(p->buf); free(p->acc); free(p->accmin); free(p->accmax); free(p);
+}
+
 /* ------------------------------------------------------------------------- */
 static const ANALYSIS_TYPE types[] = {      /* indexed by enum ddcmi_analysis_kind; DDCMI_AN_NONE has no row */
    [DDCMI_AN_PAIRCORRELATION] = {"PAIRCORRELATION", DDCMI_AN_PAIRCORRELATION, "paircorrelation.dat", pc_parms, pc_init, pc_eval, pc_output, pc_clear, pc_free},
    [DDCMI_AN_VAF] = {"VELOCITYAUTOCORRELATION", DDCMI_AN_VAF, "vaf.dat", vaf_parms, vaf_init, vaf_eval, vaf_output, NULL, vaf_free},
    [DDCMI_AN_VCMWRITE] = {"vcmWrite", DDCMI_AN_VCMWRITE, "vcm.data", vcm_parms, vcm_init, vcm_eval, vcm_output, NULL, vcm_free, 1, "vcm_write"},
    [DDCMI_AN_ZDENSITY] = {"zdensity", DDCMI_AN_ZDENSITY, "zden.dat", zd_parms, zd_init, zd_eval, zd_output, NULL, zd_free, 1, NULL},
+   [DDCMI_AN_KDIST] = {"KINETICENERGYDISTN", DDCMI_AN_KDIST, "kinetic.data", kd_parms, kd_init, kd_eval, kd_output, kd_clear, kd_free},
 };
 const ANALYSIS_TYPE *analysis_type_find(const char *type_name)
 {

@@ -1084,7 +1084,12 @@ void ddcmi_setup_free(ddcmi_setup *s)
    free(s->integrator_type); free(s->accelerator_type);
    free(s->u_energyflux);
    free(s->random_name); free(s->lcg_state); free(s->lcg_multID); free(s->lcg_prime);
-   for (int a = 0; a < s->nanalysis; a++) { free(s->analysis[a].name); free(s->analysis[a].type_name); free(s->analysis[a].filename); }
+   for (int a = 0; a < s->nanalysis; a++)
+   {
+      ddcmi_analysis *an = &s->analysis[a];
+      for (int g = 0; g < an->ndist; g++) { free(an->dist[g].name); free(an->dist[g].species); }
+      free(an->dist); free(an->name); free(an->type_name); free(an->filename);
+   }
    free(s->analysis);
    free(s->u_pressure); free(s->u_volume); free(s->u_temperature); free(s->u_energy); free(s->u_time); free(s->u_length);
    free(s);

@@ -19,7 +19,9 @@ enum { DDCMI_GROUP_FREE = 0, DDCMI_GROUP_BERENDSEN = 1, DDCMI_GROUP_LANGEVIN = 2
 
 /* one ANALYSIS object (analysis_init, analysis.c:120-160).  type: the row of host/analysis.c's table that evaluates it; DDCMI_AN_NONE is any
  * other type (not supported: the driver names it once on stderr) */
-enum ddcmi_analysis_kind { DDCMI_AN_NONE = 0, DDCMI_AN_PAIRCORRELATION, DDCMI_AN_VAF, DDCMI_AN_VCMWRITE, DDCMI_AN_ZDENSITY };
+enum ddcmi_analysis_kind { DDCMI_AN_NONE = 0, DDCMI_AN_PAIRCORRELATION, DDCMI_AN_VAF, DDCMI_AN_VCMWRITE, DDCMI_AN_ZDENSITY, DDCMI_AN_KDIST };
+/* one BIN object of a KINETICENERGYDISTN analysis (kineticEnergyDistn.c:58-83): the histogram of one species' kinetic energies */
+typedef struct ddcmi_kdist_group { char *name, *species; double emin, emax; int nbins; } ddcmi_kdist_group;      /* internal energy units; nbins >= 1, emax > emin */
 typedef struct ddcmi_analysis
 {
    char *name, *type_name;
@@ -31,6 +33,8 @@ typedef struct ddcmi_analysis
    double rmin, delta_r;        /* internal length units */
    int nz, smear_method;        /* from here on zdensity only (zdensity.c:36-50), zero otherwise.  nz: bins along z (>= 1); smear_method: 0 impulse, 1 hat */
    double smear_radius;         /* internal length units; <= 0: no smearing */
+   int ndist;                   /* from here on KINETICENERGYDISTN only (kineticEnergyDistn.c:45-93), zero otherwise: the BIN objects of distGroups, in list order */
+   ddcmi_kdist_group *dist;
 } ddcmi_analysis;
 
 typedef struct ddcmi_setup

@@ -120,6 +120,9 @@ static double internal_factor(const int dim[NDIM])
 double units_convert(double value, const char *from, const char *to)
 {
    if (!initialised) units_ddcmd_defaults();
+   /* "energy", the default unit of kineticEnergyDistn.c:62-63, is the internal unit of energy: a bare number stays as it is */
+   if (from && strcmp(from, "energy") == 0) from = NULL;
+   if (to && strcmp(to, "energy") == 0) to = NULL;
    double ff = 1.0, ft = 1.0;
    int df[NDIM], dt[NDIM];
    int have_from = (from != NULL), have_to = (to != NULL);

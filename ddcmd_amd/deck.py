@@ -181,7 +181,7 @@ def load_deck(object_file, restart_file=None, extra_objects=None):
         s.integrator_type = c.integrator_type.decode()
         s.accelerator_type = c.accelerator_type.decode()
         s.units = {k: getattr(c, "u_" + k).decode() for k in ("pressure", "volume", "temperature", "energy", "time", "length")}
-        # SIMULATE analysis = ...: one dict per ANALYSIS object, in list order (types PAIRCORRELATION, VELOCITYAUTOCORRELATION, vcmWrite and zdensity with their parameters, internal units)
+        # SIMULATE analysis = ...: one dict per ANALYSIS object, in list order (types PAIRCORRELATION, VELOCITYAUTOCORRELATION, vcmWrite, zdensity and KINETICENERGYDISTN with their parameters, internal units)
         s.analysis = []
         for a in (c.analysis[i] for i in range(int(c.nanalysis))):
             d = {"name": a.name.decode(), "type": (a.type_name or b"").decode(), "eval_rate": int(a.eval_rate), "outputrate": int(a.outputrate),
@@ -193,6 +193,9 @@ def load_deck(object_file, restart_file=None, extra_objects=None):
                          method=("geom", "grid", "neighborList")[a.method])
             if a.type == _lib.AN_ZDENSITY:
                 d.update(nz=int(a.nz), smear_radius=float(a.smear_radius), smear_method=("impulse", "hat")[a.smear_method])
+            if a.type == _lib.AN_KDIST:
+                d.update(dist_groups=[{"name": g.name.decode(), "species": g.species.decode(), "emin": float(g.emin), "emax": float(g.emax),
+                                       "nbins": int(g.nbins)} for g in (a.dist[k] for k in range(int(a.ndist)))])
             s.analysis.append(d)
     finally:
         lib.ddcmi_setup_free(p)

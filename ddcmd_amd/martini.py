@@ -34,6 +34,18 @@ def _smear_method(m):
     return int(m) if isinstance(m, (int, np.integer)) else int(str(m).lower() == "hat")
 
 
+def _kdist_args(nspecies, emin, emax, nbins, species_dist, nrank=1):
+    """the arrays ddcmi_kinetic_energy_distn takes and fills: (emin, emax, nbins, species_dist, counts, tallies, stats), nrank blocks"""
+    emin, emax = np.ascontiguousarray(emin, np.float64).reshape(-1), np.ascontiguousarray(emax, np.float64).reshape(-1)
+    nbins, sd = np.ascontiguousarray(nbins, np.int32).reshape(-1), np.ascontiguousarray(species_dist, np.int32).reshape(-1)
+    if not (len(emin) == len(emax) == len(nbins)) or len(sd) != int(nspecies):
+        raise ValueError("kinetic_energy_distn: %d emin, %d emax, %d nbins; %d entries of species_dist for %d species"
+                         % (len(emin), len(emax), len(nbins), len(sd), nspecies))
+    nd, nbt = len(nbins), int(np.maximum(nbins, 0).astype(np.int64).sum())
+    return (emin, emax, nbins, sd, np.zeros((nrank, nbt), np.int64), np.zeros((nrank, max(nd, 1), 3), np.int64)[:, :nd],
+            np.zeros((nrank, max(nd, 1), 3))[:, :nd])
+
+
 def _declare(lib):
     if getattr(lib, "_ddcmi_declared", False):
         return
@@ -111,6 +123,7 @@ def _declare(lib):
     lib.ddcmi_vaf_clear.argtypes = [vp]
     lib.ddcmi_momentum_by_class.argtypes = [vp, ctypes.c_int, ctypes.c_int, _dp, _dp]
     lib.ddcmi_zdensity.argtypes = [vp, ctypes.c_int, ctypes.c_double, ctypes.c_int, _dp]
+    lib.ddcmi_kinetic_energy_distn.argtypes = [vp, ctypes.c_int, ctypes.c_int, _dp, _dp, _ip, _ip, _lp, _lp, _dp]
     lib._ddcmi_declared = True
 
 
@@ -577,6 +590,17 @@ class MartiniHIP(object):
         self._chk(self.lib.ddcmi_zdensity(self.ctx, int(nz), float(smear_radius), _smear_method(smear_method), _d(density)))
         return density
 
+    def kinetic_energy_distn(self, emin, emax, nbins, species_dist):
+        """ANALYSIS KINETICENERGYDISTN, one evaluation of this rank (ddcmi_kinetic_energy_distn): group g histograms the kinetic
+        energies of the species s with species_dist[s] == g into nbins[g] bins from emin[g] to emax[g] (internal units).  Returns
+        (counts[sum nbins] int64 in group order, tallies[ndist, 3] int64 = {cntTotal, subCnt, supCnt}, stats[ndist, 3] = {sum K,
+        min K, max K})"""
+        emin, emax, nbins, sd, counts, tallies, stats = _kdist_args(self.s.nspecies, emin, emax, nbins, species_dist)
+        counts, tallies, stats = counts[0], np.ascontiguousarray(tallies[0]), np.ascontiguousarray(stats[0])
+        self._chk(self.lib.ddcmi_kinetic_energy_distn(self.ctx, int(self.s.nspecies), len(nbins), _d(emin), _d(emax), _i(nbins), _i(sd),
+                                                      counts.ctypes.data_as(_lp), tallies.ctypes.data_as(_lp), _d(stats)))
+        return counts, tallies, stats
+
     def download(self, mask=POS | VEL | FORCE):
         n = self.n
         out = [np.zeros(n) for _ in range(9)]
@@ -668,6 +692,7 @@ def _declare_domains(lib):
     lib.ddcmi_group_vaf_sample.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp]
     lib.ddcmi_group_momentum_by_class.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp]
     lib.ddcmi_group_zdensity.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, _dp]
+    lib.ddcmi_group_kinetic_energy_distn.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _ip, _ip, _lp, _lp, _dp]
     lib._ddcmi_dom_declared = True
 
 
@@ -863,6 +888,22 @@ class MartiniGroup(object):
         for r in range(1, self.n):
             tot += density[r]
         return tot
+
+    def kinetic_energy_distn(self, emin, emax, nbins, species_dist, per_rank=False):
+        """ddcmi_group_kinetic_energy_distn: the domains' (counts, tallies, stats) combined -- counts and sums added in rank order,
+        minimum of the minima, maximum of the maxima -- or, per_rank, stacked [rank, ...]"""
+        emin, emax, nbins, sd, counts, tallies, stats = _kdist_args(self.s.nspecies, emin, emax, nbins, species_dist, self.n)
+        tallies, stats = np.ascontiguousarray(tallies), np.ascontiguousarray(stats)
+        self._chk(self.lib.ddcmi_group_kinetic_energy_distn(self.arr, self.n, int(self.s.nspecies), len(nbins), _d(emin), _d(emax), _i(nbins), _i(sd),
+                                                            counts.ctypes.data_as(_lp), tallies.ctypes.data_as(_lp), _d(stats)))
+        if per_rank:
+            return counts, tallies, stats
+        tot = stats[0].copy()
+        for r in range(1, self.n):
+            tot[:, 0] += stats[r, :, 0]
+            tot[:, 1] = np.minimum(tot[:, 1], stats[r, :, 1])
+            tot[:, 2] = np.maximum(tot[:, 2], stats[r, :, 2])
+        return counts.sum(axis=0), tallies.sum(axis=0), tot
 
     def energies(self):
         """sum over ranks = energyInfo.c allreduce()"""

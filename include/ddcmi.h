@@ -261,7 +261,7 @@ int ddcmi_vaf_sample(ddcmi_ctx *ctx, int ngroup, int nspecies, double *vaf, doub
  * run every rank calls it at the same point of the run, as with the origin: the migration records carry the reference record
  * while tracking is on, and sender and receiver must agree on that. */
 int ddcmi_vaf_clear(ddcmi_ctx *ctx);
-/* ANALYSIS vcmWrite and zdensity on the device: one read-only pass over the owned beads each.  Both read the state that a download
+/* ANALYSIS vcmWrite, zdensity and KINETICENERGYDISTN on the device: one read-only pass over the owned beads each.  All read the state that a download
  * returns at this point of the run, change nothing of it (a run with calls and one without are bit for bit the same), need no
  * communication and give identical bits when repeated; a domain that holds no bead gives zeros.
  * vcmWrite_output's sums (vcmWrite.c:95-110) over this rank's beads, internal units: mv[3 c .. 3 c + 2] = sum m v, m[c] = sum m, class c = 0 the
@@ -274,6 +274,24 @@ int ddcmi_momentum_by_class(ddcmi_ctx *ctx, int ngroup, int nspecies, double *mv
  * smear_method 0 impulse, 1 hat.  The positions are binned as a download returns them, without a further wrap: a bead outside
  * the box lands where the reference's clamp puts it (bin nz - 1 in general).  Sums over ranks are the global histogram. [sync] */
 int ddcmi_zdensity(ddcmi_ctx *ctx, int nz, double smear_radius, int smear_method, double *density);
+/* ANALYSIS KINETICENERGYDISTN on the device: kineticEnergyDistn_eval's loop (kineticEnergyDistn.c:157-188) over this rank's beads, for
+ * all ndist histograms ("groups") in one read-only pass under the rules above.  Group g has nbins[g] bins of width
+ * delta = (emax[g] - emin[g]) / nbins[g] from emin[g] (internal energy units; finite, emax > emin, nbins >= 1); species_dist[nspecies]
+ * names the group of each species, or -1 (two species may share a group).  A bead of group g has K = (0.5 mass)((vx vx + vy vy) + vz vz),
+ * every operation rounded once as the reference's C does, mass the species' mass of ddcmi_set_species, and goes
+ *    K < emin: tallies[3 g + 1] (subCnt);   K >= emax, +inf included: tallies[3 g + 2] (supCnt);
+ *    otherwise counts[off(g) + min((int)((K - emin)/delta), nbins - 1)], off(g) = nbins[0] + ... + nbins[g - 1]
+ * (the quotient of a K just below emax may round up to nbins: the last bin, where the reference asserts).  tallies[3 g] counts every
+ * bead of the group (cntTotal); stats[3 g .. 3 g + 2] = {sum K, min K, max K}, the extremes starting at the reference's 1e300 and 0.0,
+ * which a group without beads returns.  A bead whose K is NaN is counted in cntTotal and joins the sum, and enters no bin, neither
+ * outer count, neither extreme.  Counts are exact 64-bit integers; over ranks, add counts and sums and take the minimum of the
+ * minima and the maximum of the maxima.  nspecies must be the context's.  ndist = 0 is valid and touches nothing.  The bins of all
+ * groups share one workgroup's LDS: DDCMI_KDIST_LDS_BYTES(ndist, sum of nbins) <= DDCMI_KDIST_MAX_LDS, else DDCMI_EUNSUPPORTED
+ * (16357 bins for one group; 8192 and more for up to 303 groups). [sync] */
+#define DDCMI_KDIST_MAX_LDS 65536
+#define DDCMI_KDIST_LDS_BYTES(ndist, nbins_total) (4 * ((nbins_total) + 3 * (ndist)) + 96 * (ndist))
+int ddcmi_kinetic_energy_distn(ddcmi_ctx *ctx, int nspecies, int ndist, const double *emin, const double *emax, const int *nbins,
+                               const int *species_dist, int64_t *counts, int64_t *tallies, double *stats);
 
 /* ---- introspection / measurement ------------------------------------------- */
 /* list statistics of the last build: stats[0]=stored full-list entries,

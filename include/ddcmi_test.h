@@ -63,6 +63,10 @@ int ddcmi_group_vaf_sample(ddcmi_ctx **ctxs, int n, int ngroup, int nspecies, do
  * mv[r*3*nclass ...], m[r*nclass ...] and density[r*nz ...] for domain r */
 int ddcmi_group_momentum_by_class(ddcmi_ctx **ctxs, int n, int ngroup, int nspecies, double *mv, double *m);
 int ddcmi_group_zdensity(ddcmi_ctx **ctxs, int n, int nz, double smear_radius, int smear_method, double *density);
+/* ddcmi_kinetic_energy_distn for an in-process group: every domain's own result, domain after domain -- counts[r*nbt ...] (nbt the
+ * sum of nbins), tallies[r*3*ndist ...], stats[r*3*ndist ...] for domain r */
+int ddcmi_group_kinetic_energy_distn(ddcmi_ctx **ctxs, int n, int nspecies, int ndist, const double *emin, const double *emax, const int *nbins,
+                                     const int *species_dist, int64_t *counts, int64_t *tallies, double *stats);
 /* the lean step (a single domain of FREE beads without bonded terms: one launch per step, the second stage of its energy / virial /
  * kinetic sums formed for all pending steps at once): the sums of the steps of the last such launch, 32 doubles per step --
  * {lj, ele, virial xx yy zz xy xz yz} as the full list counts them (twice), {rk, tion xx yy zz xy xz yz}, 0, the bonded kernels'

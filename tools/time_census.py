@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
-"""ANALYSIS vcmWrite and zdensity on the headline boxes: what one call of each entry point costs, beside one ddcmi_vaf_sample and
+"""ANALYSIS vcmWrite, zdensity and KINETICENERGYDISTN on the headline boxes: what one call of each entry point costs, beside one ddcmi_vaf_sample and
 one plain step of the same box in the same process.
    python3 tools/time_census.py [water:<lattice> | lipid:<x,y,z>] ...   (default: water:102 lipid:12,12,6 -- 4.24 M and 2.04 M beads)
 Every call is timed by HIP events recorded on the context's stream around it (the kernels and the copy of the result; median of
 20 after 3 warm-up calls), with the host clock around the [sync] call next to it; the step is the mean of 200 steps after 50
 (rebuilds included), host clock.  Bytes read per bead: momentum 24 (velocity) + 8 (group, species words); zdensity 32 (the position
-record); the VAF sample 32 + 24 + 48 + 8."""
+record); the VAF sample 32 + 24 + 48 + 8; the kinetic-energy histogram 24 (velocity) + 4 (species word)."""
 import ctypes, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -67,11 +67,19 @@ for spec in (sys.argv[1:] or ["water:102", "lipid:12,12,6"]):
     e0, e1 = vp(), vp()
     assert hip.hipEventCreate(ctypes.byref(e0)) == 0 and hip.hipEventCreate(ctypes.byref(e1)) == 0
     smear = ddcmd_amd.units_convert(1.0, "Angstrom", None)
+    # KINETICENERGYDISTN: 0 to 6 kT at 310 K (the bulk of a Maxwell-Boltzmann distribution); the most populous species alone in 100
+    # bins and in the largest histogram one group may have, and every species in a group of its own with 100 bins each
+    kd_lo, kd_hi = np.zeros(s.nspecies), np.full(s.nspecies, 6 * 310.0 * ddcmd_amd.units_convert(1.0, "K", None))
+    kd_one = np.full(s.nspecies, -1, np.int32)
+    kd_one[np.argmax(np.bincount(s.species, minlength=s.nspecies))] = 0
     rows = [("ddcmi_vaf_sample", 32 + 24 + 48 + 8, m.vaf_sample),
             ("ddcmi_momentum_by_class", 24 + 8, m.momentum_by_class),
             ("ddcmi_zdensity nz=300", 32, lambda: m.zdensity(300)),
             ("ddcmi_zdensity nz=300 hat 1 A", 32, lambda: m.zdensity(300, smear, "hat")),
-            ("ddcmi_zdensity nz=2048", 32, lambda: m.zdensity(2048))]
+            ("ddcmi_zdensity nz=2048", 32, lambda: m.zdensity(2048)),
+            ("kinetic_energy_distn 100 bins", 24 + 4, lambda: m.kinetic_energy_distn(kd_lo[:1], kd_hi[:1], [100], kd_one)),
+            ("kinetic_energy_distn all x 100", 24 + 4, lambda: m.kinetic_energy_distn(kd_lo, kd_hi, [100] * s.nspecies, np.arange(s.nspecies))),
+            ("kinetic_energy_distn 16357 bins", 24 + 4, lambda: m.kinetic_energy_distn(kd_lo[:1], kd_hi[:1], [16357], kd_one))]
     print("%s: %d beads, %d groups, %d species; one plain step %.4f ms" % (name, s.natoms, max(1, s.ngroup), s.nspecies, step_ms), flush=True)
     for label, bpb, call in rows:
         med, lo, host = timed(m, call, e0, e1)
