@@ -134,18 +134,26 @@ __device__ __forceinline__ double dpp_move(double v)
    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false);
    return __hiloint2double(hi, lo);
 }
-__device__ __forceinline__ double wave_sum_dpp(double v)
+/* Op::f(o, v): the value v combined with the other lane's o.  Minimum and maximum are comparisons, not fmin / fmax: a NaN that
+ * arrives as o loses every comparison and drops out */
+struct WaveSum { static __device__ __forceinline__ double f(double o, double v) { return v + o; } };
+struct WaveMin { static __device__ __forceinline__ double f(double o, double v) { return o < v ? o : v; } };
+struct WaveMax { static __device__ __forceinline__ double f(double o, double v) { return o > v ? o : v; } };
+template <class Op>
+__device__ __forceinline__ double wave_reduce_dpp(double v)
 {
-   v += dpp_move<0xB1>(v);
-   v += dpp_move<0x4E>(v);
-   v += dpp_move<0x141>(v);
-   v += dpp_move<0x140>(v);
+   v = Op::f(dpp_move<0xB1>(v), v);
+   v = Op::f(dpp_move<0x4E>(v), v);
+   v = Op::f(dpp_move<0x141>(v), v);
+   v = Op::f(dpp_move<0x140>(v), v);
    double r[4];
 #pragma unroll
    for (int q = 0; q < 4; q++)
       r[q] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 16 * q), __builtin_amdgcn_readlane(__double2loint(v), 16 * q));
-   return (r[0] + r[1]) + (r[2] + r[3]);
+   const double a = Op::f(r[1], r[0]), b = Op::f(r[3], r[2]);
+   return Op::f(b, a);
 }
+__device__ __forceinline__ double wave_sum_dpp(double v) { return wave_reduce_dpp<WaveSum>(v); }
 /* the first half of it: every lane gets the sum over its ROW of 16 lanes (four DPP butterflies, no readlane) */
 __device__ __forceinline__ double row_sum_dpp(double v)
 {
@@ -1280,6 +1288,7 @@ extern "C" int ddcmi_timing_fused(ddcmi_ctx *ctx, int64_t *launches, double *tot
 }
 
 #include "ddcmi_multigpu.inl"
+#include "ddcmi_census_frame.inl"
 #include "ddcmi_analysis.inl"
 #include "ddcmi_vaf.inl"
 #include "ddcmi_census.inl"

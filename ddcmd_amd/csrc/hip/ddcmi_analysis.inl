@@ -341,48 +341,35 @@ static int pc_eval(ddcmi_ctx *ctx, const PcReq &q, int64_t *counts, int64_t *nbe
 
 extern "C" int ddcmi_pair_correlation(ddcmi_ctx *ctx, double rmin, double delta_r, int nbins, int log_scale, int nspecies, int64_t *counts, int64_t *nbeads)
 {
-   if (!ctx) return DDCMI_EINVAL;
-   if (ctx->group_) SETERR(ctx, DDCMI_EINVAL, "contexts of an in-process group: use ddcmi_group_pair_correlation");
    const PcReq q = {rmin, delta_r, nbins, log_scale, nspecies};
-   int rc = pc_check(ctx, q, counts, nbeads);
-   if (rc) return rc;
-   (void)hipSetDevice(ctx->device);
-   if ((rc = ddcmi_agree_poll(ctx))) return rc;
-   if (!pc_one_domain(ctx))
-   {
-      /* collective: the received beads' current positions, along the per-step halo's messages */
-      if ((rc = pc_pack(ctx))) return rc;
-      if (mg_transport(ctx) && (rc = mg_xchg_halo(ctx, ctx->pc_send.p, ctx->pc_recv.p, 4, ctx->stream))) return rc;
-   }
-   return pc_eval(ctx, q, counts, nbeads);
+   return analysis_single(ctx, "pair_correlation", true, [=](ddcmi_ctx *c, const char *) { return pc_check(c, q, counts, nbeads); },
+                          [=](ddcmi_ctx *c) {
+                             int rc;
+                             if (!pc_one_domain(c))
+                             {
+                                /* collective: the received beads' current positions, along the per-step halo's messages */
+                                if ((rc = pc_pack(c))) return rc;
+                                if (mg_transport(c) && (rc = mg_xchg_halo(c, c->pc_send.p, c->pc_recv.p, 4, c->stream))) return rc;
+                             }
+                             return pc_eval(c, q, counts, nbeads);
+                          });
 }
 
 /* in-process group: per-rank results, rank after rank (counts[r * ncombo * nbins ...], nbeads[r * nspecies ...]) */
 extern "C" int ddcmi_group_pair_correlation(ddcmi_ctx **ctxs, int n, double rmin, double delta_r, int nbins, int log_scale, int nspecies,
                                             int64_t *counts, int64_t *nbeads)
 {
-   if (!ctxs || n < 1 || !ctxs[0] || !ctxs[0]->group_) return DDCMI_EINVAL;
-   ddcmi_group *g = ctxs[0]->group_;
-   ARGCHK(ctxs[0], n != (int)g->ranks.size(), "ddcmi_group_pair_correlation: n = %d, the group has %d domains", n, (int)g->ranks.size());
    const PcReq q = {rmin, delta_r, nbins, log_scale, nspecies};
-   int rc;
-   for (ddcmi_ctx *c : g->ranks)
-      if ((rc = pc_check(c, q, counts, nbeads)))
-      {
-         if (c != ctxs[0]) ctxs[0]->err = c->err;
-         return rc;
-      }
    const size_t nhist = (size_t)nspecies * (nspecies + 1) / 2 * nbins;
-   if (g->ranks[0]->nranks > 1)
-   {
-      for (ddcmi_ctx *c : g->ranks) if ((rc = pc_pack(c))) return rc;
-      if ((rc = mg_xchg_data_local(g, 3))) return rc;
-   }
-   for (size_t r = 0; r < g->ranks.size(); r++)
-      if ((rc = pc_eval(g->ranks[r], q, counts + r * nhist, nbeads + r * (size_t)nspecies)))
-      {
-         if (r) ctxs[0]->err = g->ranks[r]->err;
-         return rc;
-      }
-   return DDCMI_OK;
+   return analysis_group(ctxs, n, "pair_correlation", [=](ddcmi_ctx *c, const char *) { return pc_check(c, q, counts, nbeads); },
+                         [](ddcmi_group *g) {
+                            int rc;
+                            if (g->ranks[0]->nranks > 1)
+                            {
+                               for (ddcmi_ctx *c : g->ranks) if ((rc = pc_pack(c))) return rc;
+                               if ((rc = mg_xchg_data_local(g, 3))) return rc;
+                            }
+                            return (int)DDCMI_OK;
+                         },
+                         [=](ddcmi_ctx *c, size_t r) { return pc_eval(c, q, counts + r * nhist, nbeads + r * (size_t)nspecies); });
 }

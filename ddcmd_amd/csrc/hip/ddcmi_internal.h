@@ -370,9 +370,9 @@ struct ddcmi_ctx
    /* ANALYSIS PAIRCORRELATION (ddcmi_analysis.inl): its own records, cell sort and histogram; the halo's records travel in pc_send / pc_recv */
    dbuf<double4> pc_rec, pc_sorted; dbuf<int> pc_cnt, pc_start; dbuf<unsigned long long> pc_hist; dbuf<double> pc_send, pc_recv;
    /* ANALYSIS VELOCITYAUTOCORRELATION (ddcmi_vaf.inl): the owned beads' reference records in slot order, moved with the beads like lcg
-    * (k_gather_state, the migration records); vaf_part: the sample's per-workgroup sums and, behind them, its result */
-   dbuf<VafRec> vaf, vaf2; bool vaf_on = false; dbuf<double> vaf_part;
-   dbuf<double> census_part;      /* ANALYSIS vcmWrite / zdensity (ddcmi_census.inl): the pass's per-workgroup sums and, behind them, its result */
+    * (k_gather_state, the migration records) */
+   dbuf<VafRec> vaf, vaf2; bool vaf_on = false;
+   dbuf<double> census_part;      /* the census passes (ddcmi_census_frame.inl): the pass's per-workgroup sums and, behind them, its result */
    /* what is not a dbuf or an hbuf; those free themselves after this */
    ~ddcmi_ctx()
    {

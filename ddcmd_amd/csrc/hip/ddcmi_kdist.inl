@@ -1,9 +1,8 @@
 /* ddcmi_kdist.inl -- ANALYSIS type KINETICENERGYDISTN on the device (kineticEnergyDistn.c:157-188, kineticEnergyDistn_eval): the
  * histogram of the beads' kinetic energies, one histogram ("group") per chosen species, all groups in one read-only pass over the
- * owned beads.  Included from ddcmi.hip behind ddcmi_census.inl, whose rules it follows: it reads the state ddcmi_download_state
- * returns (the velocities k_census_momentum reads, the mass ctx->d_mass[species]), changes nothing of the run, needs no
- * communication (the caller combines the ranks' results: counts and sums added, minimum of minima, maximum of maxima), uses no
- * floating-point atomics and repeats bit for bit.
+ * owned beads: a census pass (ddcmi_census_frame.inl) over the velocities and the mass ctx->d_mass[species] that the momentum pass
+ * reads.  Included from ddcmi.hip behind ddcmi_census.inl.  The caller combines the ranks' results: counts and sums added, minimum
+ * of minima, maximum of maxima.
  *
  * Per bead whose species has a group g (species_dist[species] >= 0), the reference's statements in its operations:
  *    v2 = (vx*vx + vy*vy) + vz*vz;  K = (0.5*mass)*v2;                     every product kept from contraction into an FMA (zd_rounded)
@@ -18,47 +17,16 @@
  *
  * Shape (k_census_kdist).  Slots: the bins of all groups one after the other (off[g] + ibin), then three tallies per group
  * (nbt + 3 g + {0 cntTotal, 1 subCnt, 2 supCnt}); one row of 32-bit integers per workgroup in LDS.  A bead has two keys: its
- * group's cntTotal slot, and its bin or outer tally (none for a NaN).  Per key, as in k_census_zdensity<false>: a ballot picks the
- * lanes that share the first pending lane's key, the popcount of the ballot is added by that one lane with an integer LDS add.
- * With the first key go the doubles: the sum of the K of those lanes (wave_sum_dpp, the other lanes at zero), their minimum and
- * maximum (the same butterfly with a comparison; the other lanes at 1e300 and 0.0), which the lead lane puts into its wave's own
- * LDS row {sum, min, max} of the group -- one writer per row at a time.  The workgroup adds its waves' rows in wave order, the
- * second launch (k_census_kdist_final) adds the workgroups' 32-bit counts in 64-bit integers and the doubles in workgroup order.
+ * group's cntTotal slot, and its bin or outer tally (none for a NaN); both are counted as in k_census_zdensity<false>.
+ * With the first key go the doubles: the sum of the K of those lanes (the other lanes at zero), their minimum and maximum
+ * (wave_reduce_dpp with a comparison; the other lanes at 1e300 and 0.0), which the lead lane puts into its wave's own LDS row
+ * {sum, min, max} of the group.  Rows and workgroups combine by RowsSumMinMax.
  *
  * The cap.  LDS per workgroup: 4 B per slot and CENSUS_WAVES x 3 x 8 B = 96 B per group of per-wave rows, i.e.
  *    DDCMI_KDIST_LDS_BYTES(ndist, nbt) = 4 (nbt + 3 ndist) + 96 ndist <= DDCMI_KDIST_MAX_LDS = 64 KB
  * (the 64 KB every census kernel stays within): 16357 bins for one group, 16114 in all for ten, 8192 and more for up to 303 groups. */
 
 struct KdGroup { double emin, emax, delta; int nbins, off; };
-
-__device__ __forceinline__ double kd_wave_min_dpp(double v)      /* wave_sum_dpp's butterfly with `<` */
-{
-   double o;
-   o = dpp_move<0xB1>(v); v = o < v ? o : v;
-   o = dpp_move<0x4E>(v); v = o < v ? o : v;
-   o = dpp_move<0x141>(v); v = o < v ? o : v;
-   o = dpp_move<0x140>(v); v = o < v ? o : v;
-   double r[4];
-#pragma unroll
-   for (int q = 0; q < 4; q++)
-      r[q] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 16 * q), __builtin_amdgcn_readlane(__double2loint(v), 16 * q));
-   const double a = r[1] < r[0] ? r[1] : r[0], b = r[3] < r[2] ? r[3] : r[2];
-   return b < a ? b : a;
-}
-__device__ __forceinline__ double kd_wave_max_dpp(double v)
-{
-   double o;
-   o = dpp_move<0xB1>(v); v = o > v ? o : v;
-   o = dpp_move<0x4E>(v); v = o > v ? o : v;
-   o = dpp_move<0x141>(v); v = o > v ? o : v;
-   o = dpp_move<0x140>(v); v = o > v ? o : v;
-   double r[4];
-#pragma unroll
-   for (int q = 0; q < 4; q++)
-      r[q] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 16 * q), __builtin_amdgcn_readlane(__double2loint(v), 16 * q));
-   const double a = r[1] > r[0] ? r[1] : r[0], b = r[3] > r[2] ? r[3] : r[2];
-   return b > a ? b : a;
-}
 
 /* part_d: [nwg][ndist][3] doubles {sum, min, max}; part_c: [nwg][nbt + 3 ndist] 32-bit counts */
 __global__ __launch_bounds__(CENSUS_THREADS) void k_census_kdist(int n, int per_wg, int nspecies, int ndist, int nbt, const double *__restrict__ vx,
@@ -67,7 +35,7 @@ __global__ __launch_bounds__(CENSUS_THREADS) void k_census_kdist(int n, int per_
                                                                  double *__restrict__ part_d, unsigned *__restrict__ part_c)
 {
    extern __shared__ double census_s[];      /* double [CENSUS_WAVES][ndist][3], then unsigned [nbt + 3 ndist] */
-   const int nd3 = 3 * ndist, nslot = nbt + nd3, lane = threadIdx.x & 63;
+   const int nd3 = 3 * ndist, nslot = nbt + nd3;
    unsigned *cnt_s = (unsigned *)(census_s + (size_t)CENSUS_WAVES * nd3);
    for (int k = threadIdx.x; k < CENSUS_WAVES * nd3; k += CENSUS_THREADS) { const int q = k % 3; census_s[k] = q == 1 ? 1e300 : 0.0; }
    for (int k = threadIdx.x; k < nslot; k += CENSUS_THREADS) cnt_s[k] = 0u;
@@ -100,16 +68,10 @@ __global__ __launch_bounds__(CENSUS_THREADS) void k_census_kdist(int n, int per_
          }
       }
       /* first key: the group -- cntTotal, and the doubles */
-      unsigned long long pending = __ballot(g >= 0);
-      while (pending)
-      {
-         const int lead = __ffsll((long long)pending) - 1;
-         const int k = __shfl(g, lead, 64);
-         const bool mine = g == k;      /* (k >= 0: lanes without a group never match) */
-         const unsigned long long same = __ballot(mine);
+      wave_for_each_key(__ballot(g >= 0), g, [&](int k, bool lead, bool mine, unsigned long long same) {
          const bool ext = mine && K == K;      /* a NaN enters neither extreme */
-         const double sk = wave_sum_dpp(mine ? K : 0.0), mn = kd_wave_min_dpp(ext ? K : 1e300), mx = kd_wave_max_dpp(ext ? K : 0.0);
-         if (lane == lead)
+         const double sk = wave_sum_dpp(mine ? K : 0.0), mn = wave_reduce_dpp<WaveMin>(ext ? K : 1e300), mx = wave_reduce_dpp<WaveMax>(ext ? K : 0.0);
+         if (lead)
          {
             atomicAdd(&cnt_s[nbt + 3 * k], (unsigned)__popcll(same));      /* (integers: the order of the waves does not matter) */
             double *r = row + 3 * k;
@@ -117,58 +79,16 @@ __global__ __launch_bounds__(CENSUS_THREADS) void k_census_kdist(int n, int per_
             if (mn < r[1]) r[1] = mn;
             if (mx > r[2]) r[2] = mx;
          }
-         pending &= ~same;
-      }
+      });
       /* second key: the bin, or the outer tally */
-      pending = __ballot(slot >= 0);
-      while (pending)
-      {
-         const int lead = __ffsll((long long)pending) - 1;
-         const int k = __shfl(slot, lead, 64);
-         const unsigned long long same = __ballot(slot == k);
-         if (lane == lead) atomicAdd(&cnt_s[k], (unsigned)__popcll(same));
-         pending &= ~same;
-      }
+      wave_for_each_key(__ballot(slot >= 0), slot, [&](int k, bool lead, bool, unsigned long long same) {
+         if (lead) atomicAdd(&cnt_s[k], (unsigned)__popcll(same));
+      });
    }
    __syncthreads();
-   double *out_d = part_d + (size_t)blockIdx.x * nd3;
-   for (int k = threadIdx.x; k < nd3; k += CENSUS_THREADS)
-   {
-      const int q = k % 3;
-      double t = census_s[k];
-#pragma unroll
-      for (int w = 1; w < CENSUS_WAVES; w++)
-      {
-         const double o = census_s[(size_t)w * nd3 + k];
-         t = q == 0 ? t + o : (q == 1 ? (o < t ? o : t) : (o > t ? o : t));
-      }
-      out_d[k] = t;
-   }
+   census_rows_to_part<RowsSumMinMax>(census_s, nd3, part_d);
    unsigned *out_c = part_c + (size_t)blockIdx.x * nslot;
    for (int k = threadIdx.x; k < nslot; k += CENSUS_THREADS) out_c[k] = cnt_s[k];
-}
-/* the workgroups' rows in workgroup order: the counts in 64-bit integers, the doubles {sum, min, max} */
-__global__ void k_census_kdist_final(int nwg, int nd3, int nslot, const double *__restrict__ part_d, const unsigned *__restrict__ part_c,
-                                     double *__restrict__ out_d, long long *__restrict__ out_c)
-{
-   const int k = blockIdx.x * blockDim.x + threadIdx.x;
-   if (k < nslot)
-   {
-      unsigned long long t = 0ull;
-      for (int w = 0; w < nwg; w++) t += part_c[(size_t)w * nslot + k];
-      out_c[k] = (long long)t;
-   }
-   if (k < nd3)
-   {
-      const int q = k % 3;
-      double t = part_d[k];
-      for (int w = 1; w < nwg; w++)
-      {
-         const double o = part_d[(size_t)w * nd3 + k];
-         t = q == 0 ? t + o : (q == 1 ? (o < t ? o : t) : (o > t ? o : t));
-      }
-      out_d[k] = t;
-   }
 }
 
 /* ---- host side ---------------------------------------------------------- */
@@ -221,7 +141,7 @@ static int census_kdist_one(ddcmi_ctx *ctx, int ndist, const double *emin, const
    }
    const int nslot = nbt + nd3;
    int per_wg, nwg;
-   census_split(n, &per_wg, &nwg);
+   census_split(n, CENSUS_MAX_WG, &per_wg, &nwg);
    /* census_part, in doubles: the groups' parameters | species_dist | part_d | out_d | out_c | part_c */
    const size_t o_map = (size_t)ndist * (sizeof(KdGroup) / sizeof(double)), o_pd = o_map + ((size_t)ns + 1) / 2, o_od = o_pd + (size_t)nwg * nd3,
                 o_oc = o_od + nd3, o_pc = o_oc + nslot, total = o_pc + ((size_t)nwg * nslot + 1) / 2;
@@ -232,8 +152,8 @@ static int census_kdist_one(ddcmi_ctx *ctx, int ndist, const double *emin, const
    const size_t lds = (size_t)DDCMI_KDIST_LDS_BYTES(ndist, nbt);
    hipLaunchKernelGGL(k_census_kdist, dim3(nwg), dim3(CENSUS_THREADS), lds, st, n, per_wg, ns, ndist, nbt, ctx->vx.p, ctx->vy.p, ctx->vz.p, ctx->species.p,
                       ctx->d_mass.p, (const KdGroup *)base, (const int *)(base + o_map), base + o_pd, (unsigned *)(base + o_pc));
-   hipLaunchKernelGGL(k_census_kdist_final, dim3(cdiv(nslot, 64)), dim3(64), 0, st, nwg, nd3, nslot, base + o_pd, (const unsigned *)(base + o_pc), base + o_od,
-                      (long long *)(base + o_oc));
+   hipLaunchKernelGGL((k_census_final<RowsSumMinMax, long long>), dim3(cdiv(nslot, 64)), dim3(64), 0, st, nwg, nd3, base + o_pd, base + o_od, nslot,
+                      (const unsigned *)(base + o_pc), (long long *)(base + o_oc));
    HIPCHK(ctx, hipGetLastError());
    std::vector<int64_t> hc((size_t)nslot);
    HIPCHK(ctx, hipMemcpyAsync(stats, base + o_od, (size_t)nd3 * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -247,29 +167,19 @@ static int census_kdist_one(ddcmi_ctx *ctx, int ndist, const double *emin, const
 extern "C" int ddcmi_kinetic_energy_distn(ddcmi_ctx *ctx, int nspecies, int ndist, const double *emin, const double *emax, const int *nbins,
                                           const int *species_dist, int64_t *counts, int64_t *tallies, double *stats)
 {
-   if (!ctx) return DDCMI_EINVAL;
-   if (ctx->group_) SETERR(ctx, DDCMI_EINVAL, "contexts of an in-process group: use ddcmi_group_kinetic_energy_distn");
-   int rc = census_kdist_check(ctx, "ddcmi_kinetic_energy_distn", nspecies, ndist, emin, emax, nbins, species_dist, counts, tallies, stats);
-   if (rc) return rc;
-   (void)hipSetDevice(ctx->device);
-   if ((rc = ddcmi_agree_poll(ctx))) return rc;
-   return census_kdist_one(ctx, ndist, emin, emax, nbins, species_dist, counts, tallies, stats);
+   return analysis_single(ctx, "kinetic_energy_distn", true,
+                          [=](ddcmi_ctx *c, const char *fn) { return census_kdist_check(c, fn, nspecies, ndist, emin, emax, nbins, species_dist, counts, tallies, stats); },
+                          [=](ddcmi_ctx *c) { return census_kdist_one(c, ndist, emin, emax, nbins, species_dist, counts, tallies, stats); });
 }
 /* in-process group: per-rank blocks, rank after rank (counts[r * nbt ...], tallies[r * 3 ndist ...], stats[r * 3 ndist ...]) */
 extern "C" int ddcmi_group_kinetic_energy_distn(ddcmi_ctx **ctxs, int n, int nspecies, int ndist, const double *emin, const double *emax, const int *nbins,
                                                 const int *species_dist, int64_t *counts, int64_t *tallies, double *stats)
 {
-   if (!ctxs || n < 1 || !ctxs[0] || !ctxs[0]->group_) return DDCMI_EINVAL;
-   ddcmi_group *g = ctxs[0]->group_;
-   ARGCHK(ctxs[0], n != (int)g->ranks.size(), "ddcmi_group_kinetic_energy_distn: n = %d, the group has %d domains", n, (int)g->ranks.size());
-   int rc;
-   for (ddcmi_ctx *c : g->ranks)
-      if ((rc = census_kdist_check(c, "ddcmi_group_kinetic_energy_distn", nspecies, ndist, emin, emax, nbins, species_dist, counts, tallies, stats)))
-      { if (c != ctxs[0]) ctxs[0]->err = c->err; return rc; }
-   size_t nbt = 0;
-   for (int k = 0; k < ndist; k++) nbt += (size_t)nbins[k];
-   for (size_t r = 0; r < g->ranks.size(); r++)
-      if ((rc = census_kdist_one(g->ranks[r], ndist, emin, emax, nbins, species_dist, counts + r * nbt, tallies + r * 3 * (size_t)ndist, stats + r * 3 * (size_t)ndist)))
-      { if (r) ctxs[0]->err = g->ranks[r]->err; return rc; }
-   return DDCMI_OK;
+   return analysis_group(ctxs, n, "kinetic_energy_distn",
+                         [=](ddcmi_ctx *c, const char *fn) { return census_kdist_check(c, fn, nspecies, ndist, emin, emax, nbins, species_dist, counts, tallies, stats); },
+                         [=](ddcmi_ctx *c, size_t r) {
+                            size_t nbt = 0;      /* (the checks have seen nbins by now) */
+                            for (int k = 0; k < ndist; k++) nbt += (size_t)nbins[k];
+                            return census_kdist_one(c, ndist, emin, emax, nbins, species_dist, counts + r * nbt, tallies + r * 3 * (size_t)ndist, stats + r * 3 * (size_t)ndist);
+                         });
 }

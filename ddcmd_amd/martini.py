@@ -844,6 +844,14 @@ class MartiniGroup(object):
             return counts, nbeads
         return counts.sum(axis=0), nbeads.sum(axis=0)
 
+    @staticmethod
+    def _sum_in_rank_order(a):
+        """a[0] + a[1] + ... from left to right (np.sum(axis=0) may add pairwise): the same bits every time"""
+        tot = a[0].copy()
+        for r in range(1, len(a)):
+            tot += a[r]
+        return tot
+
     def vaf_origin(self):
         """ddcmi_group_vaf_origin: the time origin of every domain's beads"""
         self._chk(self.lib.ddcmi_group_vaf_origin(self.arr, self.n))
@@ -859,11 +867,7 @@ class MartiniGroup(object):
         self._chk(self.lib.ddcmi_group_vaf_sample(self.arr, self.n, ng, ns, _d(vaf), _d(msd)))
         if per_rank:
             return vaf, msd
-        tv, tm = vaf[0].copy(), msd[0].copy()
-        for r in range(1, self.n):
-            tv += vaf[r]
-            tm += msd[r]
-        return tv, tm
+        return self._sum_in_rank_order(vaf), self._sum_in_rank_order(msd)
 
     def momentum_by_class(self, per_rank=False):
         """ddcmi_group_momentum_by_class: the domains' (mv, m) summed in rank order -- or, per_rank, stacked [rank, class, ...]"""
@@ -872,11 +876,7 @@ class MartiniGroup(object):
         self._chk(self.lib.ddcmi_group_momentum_by_class(self.arr, self.n, ng, ns, _d(mv), _d(m)))
         if per_rank:
             return mv, m
-        tv, tm = mv[0].copy(), m[0].copy()
-        for r in range(1, self.n):
-            tv += mv[r]
-            tm += m[r]
-        return tv, tm
+        return self._sum_in_rank_order(mv), self._sum_in_rank_order(m)
 
     def zdensity(self, nz, smear_radius=0.0, smear_method="impulse", per_rank=False):
         """ddcmi_group_zdensity: the domains' histograms summed in rank order -- or, per_rank, stacked [rank, bin]"""
@@ -884,10 +884,7 @@ class MartiniGroup(object):
         self._chk(self.lib.ddcmi_group_zdensity(self.arr, self.n, int(nz), float(smear_radius), _smear_method(smear_method), _d(density)))
         if per_rank:
             return density
-        tot = density[0].copy()
-        for r in range(1, self.n):
-            tot += density[r]
-        return tot
+        return self._sum_in_rank_order(density)
 
     def kinetic_energy_distn(self, emin, emax, nbins, species_dist, per_rank=False):
         """ddcmi_group_kinetic_energy_distn: the domains' (counts, tallies, stats) combined -- counts and sums added in rank order,
@@ -899,8 +896,8 @@ class MartiniGroup(object):
         if per_rank:
             return counts, tallies, stats
         tot = stats[0].copy()
+        tot[:, 0] = self._sum_in_rank_order(stats[:, :, 0])
         for r in range(1, self.n):
-            tot[:, 0] += stats[r, :, 0]
             tot[:, 1] = np.minimum(tot[:, 1], stats[r, :, 1])
             tot[:, 2] = np.maximum(tot[:, 2], stats[r, :, 2])
         return counts.sum(axis=0), tallies.sum(axis=0), tot
