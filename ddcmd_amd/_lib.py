@@ -82,7 +82,7 @@ c_u64_p = ctypes.POINTER(ctypes.c_uint64)
 c_char_pp = ctypes.POINTER(ctypes.c_char_p)
 
 
-AN_NONE, AN_PAIRCORRELATION, AN_VAF, AN_VCMWRITE, AN_ZDENSITY, AN_KDIST = range(6)      # enum ddcmi_analysis_kind
+AN_NONE, AN_PAIRCORRELATION, AN_VAF, AN_VCMWRITE, AN_ZDENSITY, AN_KDIST, AN_DSF = range(7)      # enum ddcmi_analysis_kind
 
 
 class CKdistGroup(ctypes.Structure):
@@ -96,7 +96,8 @@ class CAnalysis(ctypes.Structure):
                 ("filename", ctypes.c_char_p), ("length", ctypes.c_int),
                 ("rscale_log", ctypes.c_int), ("method", ctypes.c_int), ("rmin", ctypes.c_double), ("delta_r", ctypes.c_double),
                 ("nz", ctypes.c_int), ("smear_method", ctypes.c_int), ("smear_radius", ctypes.c_double),
-                ("ndist", ctypes.c_int), ("dist", ctypes.POINTER(CKdistGroup))]
+                ("ndist", ctypes.c_int), ("dist", ctypes.POINTER(CKdistGroup)),
+                ("nm", ctypes.c_int), ("m", c_int_p), ("dsf_species", ctypes.c_char_p)]
 
 
 class CSetup(ctypes.Structure):

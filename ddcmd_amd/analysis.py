@@ -1,4 +1,4 @@
-"""ANALYSIS types PAIRCORRELATION, VELOCITYAUTOCORRELATION, vcmWrite, zdensity and KINETICENERGYDISTN on the host side.
+"""ANALYSIS types PAIRCORRELATION, VELOCITYAUTOCORRELATION, vcmWrite, zdensity, KINETICENERGYDISTN and DSF on the host side.
 PairCorrelation: accumulation of the device's pair counts into g(r) and the output file, as paircorrelation_eval_geom /
 paircorrelation_output (paircorrelation.c) do.  The counting itself is ddcmi_pair_correlation (Martini*.pair_correlation); nothing
 here searches pairs.
@@ -6,7 +6,9 @@ VelocityAutocorrelation: the windows of velocityAutocorrelation_eval and the fil
 (velocityAutocorrelation.c) over the device's sums (Martini*.vaf_origin / vaf_sample).
 VcmWrite, ZDensity: the file text of vcmWrite.c / zdensity.c from the device's sums (Martini*.momentum_by_class / zdensity).
 KineticEnergyDistn: the accumulation and the two files of kineticEnergyDistn.c from the device's histograms
-(Martini*.kinetic_energy_distn)."""
+(Martini*.kinetic_energy_distn).
+DynamicStructureFactor: the wave vectors, the buffer and the file text of dsf.c from the device's charge-density modes
+(Martini*.charge_density_modes)."""
 import numpy as np
 
 from .deck import units_convert
@@ -364,3 +366,63 @@ def parse_kinetic_output(text):
         v = np.array([float(x) for x in w], np.float64).reshape(-1, 8)
         out.append((v[:, 0].astype(np.int64), v[:, 1], v[:, 2:]))
     return out
+
+
+class DynamicStructureFactor(object):
+    """one DSF analysis (dsf.c).  m: the list of the `m` key as written -- every entry > 0 adds the wave vectors (0,0,m), (0,m,0),
+    (m,0,0), in that order and as often as it is listed (addKvectors); kvec is their list, mmax the largest m.  add(loop, time, rho,
+    count) takes one evaluation added over the ranks (Martini*.charge_density_modes(mmax): rho[3, mmax], the selected beads' count),
+    divides by the count where that is positive and buffers one row; it returns the text of the rows it had to flush first (the
+    buffer holds outputrate // eval_rate + 1 rows), "" otherwise.  output() is the text of the buffered rows and empties the buffer;
+    header() the line written when the file is opened.  The time is written as the driver holds it (internal units)."""
+
+    def __init__(self, m, species=None, eval_rate=1, outputrate=1, filename=None):
+        if int(eval_rate) < 1 or int(outputrate) < 1:
+            raise ValueError("eval_rate = %d, outputrate = %d: both must be at least 1" % (eval_rate, outputrate))
+        self.m = [int(x) for x in m]
+        if not self.m:
+            raise ValueError("no m")
+        self.species = species
+        self.eval_rate, self.outputrate = int(eval_rate), int(outputrate)
+        self.filename = filename or ("rho_k_%s.data" % species if species else "rho_k.data")
+        self.kvec = [v for x in self.m if x > 0 for v in ((0, 0, x), (0, x, 0), (x, 0, 0))]
+        self.mmax = max([x for x in self.m if x > 0] or [0])
+        self.nbufmax = self.outputrate // self.eval_rate + 1
+        self.rows = []
+
+    def select(self, species_names):
+        """the select array of Martini*.charge_density_modes: None without a species"""
+        if self.species is None:
+            return None
+        if self.species not in list(species_names):
+            raise ValueError("species %s is not a species of the system" % self.species)
+        return np.array([int(n == self.species) for n in species_names], np.int32)
+
+    def pick(self, rho):
+        """the kvec columns out of rho[3, mmax] (axis 0 x, 1 y, 2 z; column m - 1)"""
+        rho = np.asarray(rho, np.complex128).reshape(3, -1)
+        return np.array([rho[0 if kx else (1 if ky else 2), kx + ky + kz - 1] for kx, ky, kz in self.kvec], np.complex128)
+
+    def header(self):
+        return "%-8s %16s" % ("#loop", "time") + "".join("%-30s" % ("    (%d,%d,%d)" % k) for k in self.kvec) + "\n"
+
+    def add(self, loop, time, rho, count):
+        flushed = self.output() if len(self.rows) >= self.nbufmax else ""
+        z = self.pick(rho)
+        if count > 0:
+            z = z / float(count)
+        self.rows.append((int(loop), float(time), z))
+        return flushed
+
+    def output(self):
+        text = "".join("%8.8d %16.6f" % (loop, time) + "".join("   %13.6e %13.6e" % (v.real, v.imag) for v in z) + "\n" for loop, time, z in self.rows)
+        self.rows = []
+        return text
+
+
+def parse_dsf_output(text):
+    """(loop[nrow], time[nrow], rho complex128 [nrow, nk]) of a rho_k file (header lines skipped)"""
+    rows = [ln.split() for ln in text.splitlines() if ln.strip() and not ln.startswith("#")]
+    loop = np.array([int(r[0]) for r in rows], np.int64)
+    val = np.array([[float(x) for x in r[1:]] for r in rows], np.float64).reshape(len(rows), -1)
+    return loop, val[:, 0], val[:, 1::2] + 1j * val[:, 2::2]

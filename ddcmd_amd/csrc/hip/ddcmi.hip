@@ -1293,3 +1293,4 @@ extern "C" int ddcmi_timing_fused(ddcmi_ctx *ctx, int64_t *launches, double *tot
 #include "ddcmi_vaf.inl"
 #include "ddcmi_census.inl"
 #include "ddcmi_kdist.inl"
+#include "ddcmi_dsf.inl"

@@ -479,20 +479,141 @@ static void kd_free(void *state)
    free(p->nbins); free(p->map); free(p->emin); free(p->emax); free(p->cnt); free(p->tal); free(p->stats); free(p->buf); free(p->acc); free(p->accmin); free(p->accmax); free(p);
 }
 
+/* ANALYSIS type DSF | DynamicStructureFactor | Dynamic_Structure_Factor (dsf.c: parms :33-96, eval :127-217, output :98-124, close
+ * :219-231, addKvectors :234-269): the time series of the charge-density modes rho(k, t) = (1/N) sum q_j exp(i k.r_j) over the beads of
+ * one species (or all), N their global count, on the axis-aligned wave vectors k = m b_a of an orthorhombic box.  Every m > 0 of the
+ * list adds (0,0,m), (0,m,0), (m,0,0), in that order and as often as it is listed.  Every evaluation comes from the device
+ * (ddcmi_charge_density_modes: all m up to the largest in one pass), is added over the ranks in rank order together with the count,
+ * divided by the global count where that is positive, and buffered with the loop and the driver's time; output writes the buffered
+ * rows into a file of the run directory that rank 0 opens for append, with a header line, at init, and so does an evaluation that
+ * finds outputrate / eval_rate + 1 rows buffered.  There is no clear: the startup sample is kept.  What is still buffered at the end
+ * of the run is written before the file is closed.  What the reference leaves to an abort, an assert or a division by zero is
+ * refused at load: no `m` key, eval_rate < 1 or outputrate < 1, a species the system lacks (deck.c), a largest m above
+ * DDCMI_DSF_MAX_M. */
+typedef struct { FILE *file; int nk, mmax, nbuf, nbufmax, *axis, *mk, *select; int64_t *loop; double *time, *buffer, *rho; } DSFSTATE;
+static void dsf_parms(const OBJECT *obj, ddcmi_analysis *an, char *msg, int msglen)
+{
+   an->nm = object_testforkeyword(obj, "m") ? object_getv(obj, "m", (void **)&an->m, INT, IGNORE_IF_NOT_FOUND) : 0;
+   if (an->nm < 0) an->nm = 0;
+   if (object_testforkeyword(obj, "species")) object_get(obj, "species", &an->dsf_species, STRING, 1, "");
+   if (an->dsf_species && !an->dsf_species[0]) { free(an->dsf_species); an->dsf_species = NULL; }      /* "species = ;" */
+   if (an->dsf_species && !object_testforkeyword(obj, "filename"))
+   {
+      char name[600];
+      snprintf(name, sizeof(name), "rho_k_%s.data", an->dsf_species);
+      free(an->filename); an->filename = strdup(name);
+   }
+   int mmax = 0;
+   for (int i = 0; i < an->nm; i++) if (an->m[i] > mmax) mmax = an->m[i];
+   if (an->nm < 1) snprintf(msg, msglen, "ANALYSIS %s: no m key (the list of wave numbers)", an->name);
+   else if (an->eval_rate < 1 || an->outputrate < 1) snprintf(msg, msglen, "ANALYSIS %s: eval_rate = %d, outputrate = %d: both must be at least 1", an->name, an->eval_rate, an->outputrate);
+   else if (mmax > DDCMI_DSF_MAX_M) snprintf(msg, msglen, "ANALYSIS %s: m = %d, the device takes at most %d", an->name, mmax, DDCMI_DSF_MAX_M);
+}
+static void dsf_write(DSFSTATE *p)      /* dsf_output */
+{
+   if (par.rank == 0)
+   {
+      for (int ii = 0; ii < p->nbuf; ii++)
+      {
+         fprintf(p->file, "%8.8d %16.6f", (int)p->loop[ii], p->time[ii]);
+         for (int jj = 0; jj < p->nk; jj++) fprintf(p->file, "   %13.6e %13.6e", p->buffer[2 * ((size_t)ii * p->nk + jj)], p->buffer[2 * ((size_t)ii * p->nk + jj) + 1]);
+         fprintf(p->file, "\n");
+      }
+      fflush(p->file);
+   }
+   p->nbuf = 0;
+}
+static void *dsf_init(SIMULATE *simulate, const ddcmi_analysis *an)
+{
+   const ddcmi_setup *s = simulate->setup;
+   DSFSTATE *p = zalloc(1, sizeof(DSFSTATE));
+   p->axis = zalloc(3 * (size_t)an->nm + 1, sizeof(int)); p->mk = zalloc(3 * (size_t)an->nm + 1, sizeof(int));
+   for (int i = 0; i < an->nm; i++)
+   {
+      if (an->m[i] <= 0) continue;      /* addKvectors finds no vector */
+      if (an->m[i] > p->mmax) p->mmax = an->m[i];
+      for (int a = 2; a >= 0; a--) { p->axis[p->nk] = a; p->mk[p->nk] = an->m[i]; p->nk++; }      /* (0,0,m), (0,m,0), (m,0,0) */
+   }
+   if (an->dsf_species)
+   {
+      p->select = zalloc(s->nspecies + 1, sizeof(int));
+      for (int i = 0; i < s->nspecies; i++) p->select[i] = strcmp(an->dsf_species, s->species_name[i]) == 0;
+   }
+   p->nbufmax = an->outputrate / an->eval_rate + 1;
+   p->loop = zalloc(p->nbufmax, sizeof(int64_t)); p->time = zalloc(p->nbufmax, sizeof(double));
+   p->buffer = zalloc(2 * (size_t)p->nbufmax * p->nk + 1, sizeof(double));
+   p->rho = zalloc(6 * (size_t)(p->mmax > 0 ? p->mmax : 1) + 1, sizeof(double));
+   if (par.rank == 0)
+   {
+      p->file = fopen(an->filename, "a");
+      if (!p->file) die("dsf_parms", "cannot open the output file");
+      fprintf(p->file, "%-8s %16s", "#loop", "time");
+      for (int ii = 0; ii < p->nk; ii++)
+      {
+         char tmp[256];
+         const int a = p->axis[ii], m = p->mk[ii];
+         snprintf(tmp, sizeof(tmp), "    (%d,%d,%d)", a == 0 ? m : 0, a == 1 ? m : 0, a == 2 ? m : 0);
+         fprintf(p->file, "%-30s", tmp);
+      }
+      fprintf(p->file, "\n");
+      fflush(p->file);
+   }
+   return p;
+}
+static void dsf_eval(SIMULATE *simulate, const ddcmi_analysis *an, void *state)
+{
+   (void)an;
+   DSFSTATE *p = state;
+   ddcmi_ctx *ctx = simulate->accelerator->parms;
+   if (p->nbuf >= p->nbufmax) dsf_write(p);
+   const int nv = 6 * p->mmax;
+   int64_t count = 0;
+   if (p->mmax > 0 && ddcmi_charge_density_modes(ctx, simulate->setup->nspecies, p->select, p->mmax, p->rho, &count) != DDCMI_OK)
+      die("dsf_eval", ddcmi_last_error(ctx));
+   p->rho[nv] = (double)count;      /* (an integer below 2^53: the double sum is exact) */
+   sum_over_ranks(p->rho, nv + 1, "dsf_eval");
+   const double countSum = p->rho[nv];
+   double *row = p->buffer + 2 * (size_t)p->nbuf * p->nk;
+   for (int ii = 0; ii < p->nk; ii++)
+      for (int q = 0; q < 2; q++)
+      {
+         double v = p->rho[2 * ((size_t)p->axis[ii] * p->mmax + (p->mk[ii] - 1)) + q];
+         if (countSum > 0) v /= countSum;
+         row[2 * ii + q] = v;
+      }
+   p->loop[p->nbuf] = simulate->loop;
+   p->time[p->nbuf] = simulate->time;
+   p->nbuf++;
+}
+static void dsf_output(SIMULATE *simulate, const ddcmi_analysis *an, void *state) { (void)simulate; (void)an; dsf_write(state); }
+static void dsf_free(void *state)      /* dsf_close */
+{
+   DSFSTATE *p = state;
+   dsf_write(p);
+   if (p->file) fclose(p->file);
+   free(p->axis); free(p->mk); free(p->select); free(p->loop); free(p->time); free(p->buffer); free(p->rho); free(p);
+}
+
 /* ------------------------------------------------------------------------- */
+static const char *const dsf_heads[] = {"DynamicStructureFactor", "Dynamic_Structure_Factor", NULL};
 static const ANALYSIS_TYPE types[] = {      /* indexed by enum ddcmi_analysis_kind; DDCMI_AN_NONE has no row */
    [DDCMI_AN_PAIRCORRELATION] = {"PAIRCORRELATION", DDCMI_AN_PAIRCORRELATION, "paircorrelation.dat", pc_parms, pc_init, pc_eval, pc_output, pc_clear, pc_free},
    [DDCMI_AN_VAF] = {"VELOCITYAUTOCORRELATION", DDCMI_AN_VAF, "vaf.dat", vaf_parms, vaf_init, vaf_eval, vaf_output, NULL, vaf_free},
    [DDCMI_AN_VCMWRITE] = {"vcmWrite", DDCMI_AN_VCMWRITE, "vcm.data", vcm_parms, vcm_init, vcm_eval, vcm_output, NULL, vcm_free, 1, "vcm_write"},
    [DDCMI_AN_ZDENSITY] = {"zdensity", DDCMI_AN_ZDENSITY, "zden.dat", zd_parms, zd_init, zd_eval, zd_output, NULL, zd_free, 1, NULL},
    [DDCMI_AN_KDIST] = {"KINETICENERGYDISTN", DDCMI_AN_KDIST, "kinetic.data", kd_parms, kd_init, kd_eval, kd_output, kd_clear, kd_free},
+   [DDCMI_AN_DSF] = {"DSF", DDCMI_AN_DSF, "rho_k.data", dsf_parms, dsf_init, dsf_eval, dsf_output, NULL, dsf_free, 0, NULL, dsf_heads},
 };
 const ANALYSIS_TYPE *analysis_type_find(const char *type_name)
 {
    for (size_t t = 1; t < sizeof(types) / sizeof(types[0]); t++)
    {
       const ANALYSIS_TYPE *row = &types[t];
-      if (!row->full_name) { if (strncasecmp(type_name, row->prefix, strlen(row->prefix)) == 0) return row; }
+      if (!row->full_name)
+      {
+         if (strncasecmp(type_name, row->prefix, strlen(row->prefix)) == 0) return row;
+         for (const char *const *h = row->heads; h && *h; h++) if (strncasecmp(type_name, *h, strlen(*h)) == 0) return row;
+      }
       else if (strcasecmp(type_name, row->prefix) == 0 || (row->alias && strcasecmp(type_name, row->alias) == 0)) return row;
    }
    return NULL;

@@ -5,8 +5,9 @@
 #include "plugin.h"
 #include "object.h"
 
-/* a row of the table.  `prefix` is matched against the head of the type name, in any case (analysis.c:178) -- or, with `full_name`
- * set, against the whole type name and against `alias` (analysis.c:240,317: vcmWrite | vcm_write, zdensity) */
+/* a row of the table.  `prefix` is matched against the head of the type name, in any case (analysis.c:178), and so is every entry of
+ * `heads` (analysis.c:231-233: DSF | DynamicStructureFactor | Dynamic_Structure_Factor) -- or, with `full_name` set, `prefix` is
+ * matched against the whole type name and against `alias` (analysis.c:240,317: vcmWrite | vcm_write, zdensity) */
 typedef struct analysis_type_st
 {
    const char *prefix;
@@ -21,6 +22,7 @@ typedef struct analysis_type_st
    void (*free)(void *state);
    int full_name;                                          /* the whole type name must match, not its head */
    const char *alias;                                      /* a second spelling (full_name rows), or NULL */
+   const char *const *heads;                               /* further heads (rows matched by the head), NULL-terminated, or NULL */
 } ANALYSIS_TYPE;
 const ANALYSIS_TYPE *analysis_type_find(const char *type_name);      /* NULL: not supported */
 

@@ -783,6 +783,15 @@ ddcmi_setup *ddcmi_deck_load_with(const char *object_file, const char *restart_f
          object_get(so, "mass", &s->mass[i], WITH_UNITS, 1, "1.0", "m", NULL);       /* species.c:35 */
          object_get(so, "charge", &s->charge[i], WITH_UNITS, 1, "0.0", "i*t", NULL); /* species.c:36 */
       }
+      /* ANALYSIS DSF: its species is one of the system's (where the reference has assert(parms->species != NULL), dsf.c:50) */
+      for (int a = 0; a < s->nanalysis; a++)
+      {
+         const ddcmi_analysis *an = &s->analysis[a];
+         if (an->type != DDCMI_AN_DSF || !an->dsf_species) continue;
+         int found = 0;
+         for (int i = 0; i < s->nspecies; i++) found |= strcmp(an->dsf_species, s->species_name[i]) == 0;
+         if (!found) FAIL("ANALYSIS %s: species = %s, and the system has no species of that name", an->name, an->dsf_species);
+      }
    }
    /* POTENTIAL type=MARTINI */
    {
@@ -1088,7 +1097,7 @@ void ddcmi_setup_free(ddcmi_setup *s)
    {
       ddcmi_analysis *an = &s->analysis[a];
       for (int g = 0; g < an->ndist; g++) { free(an->dist[g].name); free(an->dist[g].species); }
-      free(an->dist); free(an->name); free(an->type_name); free(an->filename);
+      free(an->dist); free(an->name); free(an->type_name); free(an->filename); free(an->m); free(an->dsf_species);
    }
    free(s->analysis);
    free(s->u_pressure); free(s->u_volume); free(s->u_temperature); free(s->u_energy); free(s->u_time); free(s->u_length);

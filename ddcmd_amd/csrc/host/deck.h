@@ -19,7 +19,7 @@ enum { DDCMI_GROUP_FREE = 0, DDCMI_GROUP_BERENDSEN = 1, DDCMI_GROUP_LANGEVIN = 2
 
 /* one ANALYSIS object (analysis_init, analysis.c:120-160).  type: the row of host/analysis.c's table that evaluates it; DDCMI_AN_NONE is any
  * other type (not supported: the driver names it once on stderr) */
-enum ddcmi_analysis_kind { DDCMI_AN_NONE = 0, DDCMI_AN_PAIRCORRELATION, DDCMI_AN_VAF, DDCMI_AN_VCMWRITE, DDCMI_AN_ZDENSITY, DDCMI_AN_KDIST };
+enum ddcmi_analysis_kind { DDCMI_AN_NONE = 0, DDCMI_AN_PAIRCORRELATION, DDCMI_AN_VAF, DDCMI_AN_VCMWRITE, DDCMI_AN_ZDENSITY, DDCMI_AN_KDIST, DDCMI_AN_DSF };
 /* one BIN object of a KINETICENERGYDISTN analysis (kineticEnergyDistn.c:58-83): the histogram of one species' kinetic energies */
 typedef struct ddcmi_kdist_group { char *name, *species; double emin, emax; int nbins; } ddcmi_kdist_group;      /* internal energy units; nbins >= 1, emax > emin */
 typedef struct ddcmi_analysis
@@ -35,6 +35,9 @@ typedef struct ddcmi_analysis
    double smear_radius;         /* internal length units; <= 0: no smearing */
    int ndist;                   /* from here on KINETICENERGYDISTN only (kineticEnergyDistn.c:45-93), zero otherwise: the BIN objects of distGroups, in list order */
    ddcmi_kdist_group *dist;
+   int nm;                      /* from here on DSF only (dsf.c:33-96), zero / NULL otherwise: the list of the `m` key as written (an entry <= 0 adds no wave vector) */
+   int *m;
+   char *dsf_species;           /* the one species that takes part, or NULL: every bead */
 } ddcmi_analysis;
 
 typedef struct ddcmi_setup

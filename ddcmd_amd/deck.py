@@ -181,7 +181,7 @@ def load_deck(object_file, restart_file=None, extra_objects=None):
         s.integrator_type = c.integrator_type.decode()
         s.accelerator_type = c.accelerator_type.decode()
         s.units = {k: getattr(c, "u_" + k).decode() for k in ("pressure", "volume", "temperature", "energy", "time", "length")}
-        # SIMULATE analysis = ...: one dict per ANALYSIS object, in list order (types PAIRCORRELATION, VELOCITYAUTOCORRELATION, vcmWrite, zdensity and KINETICENERGYDISTN with their parameters, internal units)
+        # SIMULATE analysis = ...: one dict per ANALYSIS object, in list order (types PAIRCORRELATION, VELOCITYAUTOCORRELATION, vcmWrite, zdensity, KINETICENERGYDISTN and DSF with their parameters, internal units)
         s.analysis = []
         for a in (c.analysis[i] for i in range(int(c.nanalysis))):
             d = {"name": a.name.decode(), "type": (a.type_name or b"").decode(), "eval_rate": int(a.eval_rate), "outputrate": int(a.outputrate),
@@ -196,6 +196,8 @@ def load_deck(object_file, restart_file=None, extra_objects=None):
             if a.type == _lib.AN_KDIST:
                 d.update(dist_groups=[{"name": g.name.decode(), "species": g.species.decode(), "emin": float(g.emin), "emax": float(g.emax),
                                        "nbins": int(g.nbins)} for g in (a.dist[k] for k in range(int(a.ndist)))])
+            if a.type == _lib.AN_DSF:
+                d.update(m=[int(a.m[k]) for k in range(int(a.nm))], species=a.dsf_species.decode() if a.dsf_species else None)
             s.analysis.append(d)
     finally:
         lib.ddcmi_setup_free(p)

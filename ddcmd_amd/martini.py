@@ -46,6 +46,16 @@ def _kdist_args(nspecies, emin, emax, nbins, species_dist, nrank=1):
             np.zeros((nrank, max(nd, 1), 3))[:, :nd])
 
 
+def _dsf_args(nspecies, mmax, select, nrank=1):
+    """the arrays ddcmi_charge_density_modes takes and fills: (select or None, rho[nrank, 3, mmax, 2], count[nrank])"""
+    sel = None
+    if select is not None:
+        sel = np.ascontiguousarray(np.asarray(select) != 0, np.int32).reshape(-1)
+        if len(sel) != int(nspecies):
+            raise ValueError("charge_density_modes: %d entries of select for %d species" % (len(sel), nspecies))
+    return sel, np.zeros((nrank, 3, max(int(mmax), 1), 2)), np.zeros(nrank, np.int64)
+
+
 def _declare(lib):
     if getattr(lib, "_ddcmi_declared", False):
         return
@@ -124,6 +134,7 @@ def _declare(lib):
     lib.ddcmi_momentum_by_class.argtypes = [vp, ctypes.c_int, ctypes.c_int, _dp, _dp]
     lib.ddcmi_zdensity.argtypes = [vp, ctypes.c_int, ctypes.c_double, ctypes.c_int, _dp]
     lib.ddcmi_kinetic_energy_distn.argtypes = [vp, ctypes.c_int, ctypes.c_int, _dp, _dp, _ip, _ip, _lp, _lp, _dp]
+    lib.ddcmi_charge_density_modes.argtypes = [vp, ctypes.c_int, _ip, ctypes.c_int, _dp, _lp]
     lib._ddcmi_declared = True
 
 
@@ -601,6 +612,14 @@ class MartiniHIP(object):
                                                       counts.ctypes.data_as(_lp), tallies.ctypes.data_as(_lp), _d(stats)))
         return counts, tallies, stats
 
+    def charge_density_modes(self, mmax, select=None):
+        """ANALYSIS DSF, one evaluation of this rank (ddcmi_charge_density_modes): (rho complex128 [3, mmax], count) -- rho[a, m - 1] the
+        sum of q exp(i 2 pi m r_a / L_a) over the owned beads of the species select marks (None: all), count their number; the division
+        by the global count is the caller's"""
+        sel, rho, count = _dsf_args(self.s.nspecies, mmax, select)
+        self._chk(self.lib.ddcmi_charge_density_modes(self.ctx, int(self.s.nspecies), _i(sel), int(mmax), _d(rho), count.ctypes.data_as(_lp)))
+        return rho[0, :, :, 0] + 1j * rho[0, :, :, 1], int(count[0])
+
     def download(self, mask=POS | VEL | FORCE):
         n = self.n
         out = [np.zeros(n) for _ in range(9)]
@@ -693,6 +712,7 @@ def _declare_domains(lib):
     lib.ddcmi_group_momentum_by_class.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp]
     lib.ddcmi_group_zdensity.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, _dp]
     lib.ddcmi_group_kinetic_energy_distn.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _ip, _ip, _lp, _lp, _dp]
+    lib.ddcmi_group_charge_density_modes.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int, _ip, ctypes.c_int, _dp, _lp]
     lib._ddcmi_dom_declared = True
 
 
@@ -901,6 +921,15 @@ class MartiniGroup(object):
             tot[:, 1] = np.minimum(tot[:, 1], stats[r, :, 1])
             tot[:, 2] = np.maximum(tot[:, 2], stats[r, :, 2])
         return counts.sum(axis=0), tallies.sum(axis=0), tot
+
+    def charge_density_modes(self, mmax, select=None, per_rank=False):
+        """ddcmi_group_charge_density_modes: the domains' (rho, count) added in rank order -- or, per_rank, stacked [rank, ...]"""
+        sel, rho, count = _dsf_args(self.s.nspecies, mmax, select, self.n)
+        self._chk(self.lib.ddcmi_group_charge_density_modes(self.arr, self.n, int(self.s.nspecies), _i(sel), int(mmax), _d(rho), count.ctypes.data_as(_lp)))
+        z = rho[..., 0] + 1j * rho[..., 1]
+        if per_rank:
+            return z, count
+        return self._sum_in_rank_order(z), int(count.sum())
 
     def energies(self):
         """sum over ranks = energyInfo.c allreduce()"""

@@ -261,7 +261,7 @@ int ddcmi_vaf_sample(ddcmi_ctx *ctx, int ngroup, int nspecies, double *vaf, doub
  * run every rank calls it at the same point of the run, as with the origin: the migration records carry the reference record
  * while tracking is on, and sender and receiver must agree on that. */
 int ddcmi_vaf_clear(ddcmi_ctx *ctx);
-/* ANALYSIS vcmWrite, zdensity and KINETICENERGYDISTN on the device: one read-only pass over the owned beads each.  All read the state that a download
+/* ANALYSIS vcmWrite, zdensity, KINETICENERGYDISTN and DSF on the device: one read-only pass over the owned beads each.  All read the state that a download
  * returns at this point of the run, change nothing of it (a run with calls and one without are bit for bit the same), need no
  * communication and give identical bits when repeated; a domain that holds no bead gives zeros.
  * vcmWrite_output's sums (vcmWrite.c:95-110) over this rank's beads, internal units: mv[3 c .. 3 c + 2] = sum m v, m[c] = sum m, class c = 0 the
@@ -292,6 +292,16 @@ int ddcmi_zdensity(ddcmi_ctx *ctx, int nz, double smear_radius, int smear_method
 #define DDCMI_KDIST_LDS_BYTES(ndist, nbins_total) (4 * ((nbins_total) + 3 * (ndist)) + 96 * (ndist))
 int ddcmi_kinetic_energy_distn(ddcmi_ctx *ctx, int nspecies, int ndist, const double *emin, const double *emax, const int *nbins,
                                const int *species_dist, int64_t *counts, int64_t *tallies, double *stats);
+/* ANALYSIS DSF / DynamicStructureFactor on the device: dsf_eval's local sums (dsf.c:160-205) over this rank's beads for the axis-aligned
+ * wave vectors k = m b_a of an orthorhombic box, in one read-only pass under the rules above.  rho[3][mmax][2]: for axis a (0 x, 1 y,
+ * 2 z) and m = 1 .. mmax the {re, im} of sum q_j c^m, c = exp(i 2 pi r_a / L_a), over the owned beads whose species is selected --
+ * select[nspecies], nonzero: takes part; NULL: every species.  q is the species' charge of ddcmi_set_species.  *count: the selected
+ * owned beads.  Over ranks, add rho and the counts; the division by the global count (dsf.c:210-212) is the caller's.  The positions
+ * are those a download returns, without a further wrap: the phase is periodic, so a bead outside the box contributes correctly.
+ * nspecies must be the context's; 1 <= mmax <= DDCMI_DSF_MAX_M, above it DDCMI_EUNSUPPORTED.  A domain that holds no bead, or a
+ * select without a member, gives zeros and count 0. [sync] */
+#define DDCMI_DSF_MAX_M 256
+int ddcmi_charge_density_modes(ddcmi_ctx *ctx, int nspecies, const int *select, int mmax, double *rho, int64_t *count);
 
 /* ---- introspection / measurement ------------------------------------------- */
 /* list statistics of the last build: stats[0]=stored full-list entries,

@@ -67,6 +67,9 @@ int ddcmi_group_zdensity(ddcmi_ctx **ctxs, int n, int nz, double smear_radius, i
  * sum of nbins), tallies[r*3*ndist ...], stats[r*3*ndist ...] for domain r */
 int ddcmi_group_kinetic_energy_distn(ddcmi_ctx **ctxs, int n, int nspecies, int ndist, const double *emin, const double *emax, const int *nbins,
                                      const int *species_dist, int64_t *counts, int64_t *tallies, double *stats);
+/* ddcmi_charge_density_modes for an in-process group: every domain's own result, domain after domain -- rho[r*6*mmax ...], count[r]
+ * for domain r */
+int ddcmi_group_charge_density_modes(ddcmi_ctx **ctxs, int n, int nspecies, const int *select, int mmax, double *rho, int64_t *count);
 /* the lean step (a single domain of FREE beads without bonded terms: one launch per step, the second stage of its energy / virial /
  * kinetic sums formed for all pending steps at once): the sums of the steps of the last such launch, 32 doubles per step --
  * {lj, ele, virial xx yy zz xy xz yz} as the full list counts them (twice), {rk, tion xx yy zz xy xz yz}, 0, the bonded kernels'

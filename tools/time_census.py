@@ -79,7 +79,9 @@ for spec in (sys.argv[1:] or ["water:102", "lipid:12,12,6"]):
             ("ddcmi_zdensity nz=2048", 32, lambda: m.zdensity(2048)),
             ("kinetic_energy_distn 100 bins", 24 + 4, lambda: m.kinetic_energy_distn(kd_lo[:1], kd_hi[:1], [100], kd_one)),
             ("kinetic_energy_distn all x 100", 24 + 4, lambda: m.kinetic_energy_distn(kd_lo, kd_hi, [100] * s.nspecies, np.arange(s.nspecies))),
-            ("kinetic_energy_distn 16357 bins", 24 + 4, lambda: m.kinetic_energy_distn(kd_lo[:1], kd_hi[:1], [16357], kd_one))]
+            ("kinetic_energy_distn 16357 bins", 24 + 4, lambda: m.kinetic_energy_distn(kd_lo[:1], kd_hi[:1], [16357], kd_one)),
+            ("charge_density_modes mmax=8", 32 + 4, lambda: m.charge_density_modes(8)),      # one chunk of modes: one pass over the positions
+            ("charge_density_modes mmax=64", 8 * (32 + 4), lambda: m.charge_density_modes(64))]
     print("%s: %d beads, %d groups, %d species; one plain step %.4f ms" % (name, s.natoms, max(1, s.ngroup), s.nspecies, step_ms), flush=True)
     for label, bpb, call in rows:
         med, lo, host = timed(m, call, e0, e1)
