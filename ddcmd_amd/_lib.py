@@ -82,7 +82,7 @@ c_u64_p = ctypes.POINTER(ctypes.c_uint64)
 c_char_pp = ctypes.POINTER(ctypes.c_char_p)
 
 
-AN_NONE, AN_PAIRCORRELATION, AN_VAF, AN_VCMWRITE, AN_ZDENSITY, AN_KDIST, AN_DSF = range(7)      # enum ddcmi_analysis_kind
+AN_NONE, AN_PAIRCORRELATION, AN_VAF, AN_VCMWRITE, AN_ZDENSITY, AN_KDIST, AN_DSF, AN_SUBSETWRITE = range(8)      # enum ddcmi_analysis_kind
 
 
 class CKdistGroup(ctypes.Structure):
@@ -97,7 +97,12 @@ class CAnalysis(ctypes.Structure):
                 ("rscale_log", ctypes.c_int), ("method", ctypes.c_int), ("rmin", ctypes.c_double), ("delta_r", ctypes.c_double),
                 ("nz", ctypes.c_int), ("smear_method", ctypes.c_int), ("smear_radius", ctypes.c_double),
                 ("ndist", ctypes.c_int), ("dist", ctypes.POINTER(CKdistGroup)),
-                ("nm", ctypes.c_int), ("m", c_int_p), ("dsf_species", ctypes.c_char_p)]
+                ("nm", ctypes.c_int), ("m", c_int_p), ("dsf_species", ctypes.c_char_p),
+                ("sw_length_unit", ctypes.c_char_p), ("sw_modulus", ctypes.c_int), ("sw_odd", ctypes.c_int), ("sw_nfiles", ctypes.c_int),
+                ("sw_idmin", ctypes.c_uint64), ("sw_idmax", ctypes.c_uint64), ("sw_nid", ctypes.c_int), ("sw_idlist", c_u64_p),
+                ("sw_nspecies", ctypes.c_int), ("sw_species", c_char_pp),
+                ("sw_rmin", ctypes.c_double * 3), ("sw_rmax", ctypes.c_double * 3), ("sw_vmin", ctypes.c_double * 3), ("sw_vmax", ctypes.c_double * 3),
+                ("sw_given", ctypes.c_int)]
 
 
 class CSetup(ctypes.Structure):

@@ -1,4 +1,4 @@
-"""ANALYSIS types PAIRCORRELATION, VELOCITYAUTOCORRELATION, vcmWrite, zdensity, KINETICENERGYDISTN and DSF on the host side.
+"""ANALYSIS types PAIRCORRELATION, VELOCITYAUTOCORRELATION, vcmWrite, zdensity, KINETICENERGYDISTN, DSF and subsetWrite on the host side.
 PairCorrelation: accumulation of the device's pair counts into g(r) and the output file, as paircorrelation_eval_geom /
 paircorrelation_output (paircorrelation.c) do.  The counting itself is ddcmi_pair_correlation (Martini*.pair_correlation); nothing
 here searches pairs.
@@ -8,7 +8,12 @@ VcmWrite, ZDensity: the file text of vcmWrite.c / zdensity.c from the device's s
 KineticEnergyDistn: the accumulation and the two files of kineticEnergyDistn.c from the device's histograms
 (Martini*.kinetic_energy_distn).
 DynamicStructureFactor: the wave vectors, the buffer and the file text of dsf.c from the device's charge-density modes
-(Martini*.charge_density_modes)."""
+(Martini*.charge_density_modes).
+SubsetWrite: the pinfo tables of pinfo.c, the header of write_fileheader (io.c) and the file of subsetWriteBinaryCharmm
+(subsetWrite.c) around the device's packed records (Martini*.subset_records); read_subset reads such a file back."""
+import os
+import time as _time
+
 import numpy as np
 
 from .deck import units_convert
@@ -426,3 +431,152 @@ def parse_dsf_output(text):
     loop = np.array([int(r[0]) for r in rows], np.int64)
     val = np.array([[float(x) for x in r[1:]] for r in rows], np.float64).reshape(len(rows), -1)
     return loop, val[:, 0], val[:, 1::2] + 1j * val[:, 2::2]
+
+
+SUBSET_RECORD = np.dtype([("id", "<u8"), ("pinfo", "<u4"), ("r", "<f4", (3,))])      # a binaryCharmm record: 24 bytes
+
+
+def pinfo_field_size(ngroups, nspecies, ntypes):
+    """bytes of the pinfo field that holds pinfoMaxIndex = ngroups * nspecies * ntypes (pinfo.c:148-151); subsetWriteBinaryCharmm
+    asserts that 4 are enough, and here more is a ValueError"""
+    top, nbytes = int(ngroups) * int(nspecies) * int(ntypes), 1
+    while top >= 256 ** nbytes:
+        nbytes += 1
+    if nbytes > 4:
+        raise ValueError("%d groups, %d species and %d types need a pinfo field of %d bytes, more than 4" % (ngroups, nspecies, ntypes, nbytes))
+    return nbytes
+
+
+def _unique(names):
+    """(the distinct names in order, every entry's index among them): a repeated name has its first occurrence's index"""
+    uniq = []
+    index = []
+    for n in names:
+        if n not in uniq:
+            uniq.append(n)
+        index.append(uniq.index(n))
+    return uniq, index
+
+
+class SubsetWrite(object):
+    """one subsetWrite analysis with format = binaryCharmm (subsetWrite.c).  group_names / species_names: the system's, in index
+    order (a system without groups has the one group "group"); species_types: the species' type names, ATOM for every Martini
+    species.  group_term / species_term are pinfoEncode (pinfo.c:119-126) split in two: pinfo = group_term[group] +
+    species_term[species].  The filter's bounds are in internal units; None is the reference's default, -+ the longest box edge
+    through its "%e" for x, y, z and -+ DBL_MAX likewise for the velocities, which default() forms for a box.
+    filter() is the keyword dict of Martini*.subset_records; header(...) the file's header, file_bytes(...) header and records."""
+
+    def __init__(self, group_names, species_names, species_types=None, filename="subset", length_unit="Ang", modulus=1, odd=0, idmin=0, idmax=2 ** 64 - 1,
+                 id_list=None, species=None, rmin=None, rmax=None, vmin=None, vmax=None, outputrate=0, h=None):
+        if int(modulus) < 1:
+            raise ValueError("modulus = %d, it must be at least 1" % modulus)
+        self.group_names = list(group_names) or ["group"]
+        self.species_names = list(species_names)
+        self.species_types = list(species_types) if species_types is not None else ["ATOM"] * len(self.species_names)
+        for n in species or []:
+            if n not in self.species_names:
+                raise ValueError("species %s is not a species of the system" % n)
+        self.groups, gmap = _unique(self.group_names)
+        self.species_list, smap = _unique(self.species_names)
+        self.types, tmap = _unique(self.species_types)
+        self.pinfo_bytes = pinfo_field_size(len(self.groups), len(self.species_list), len(self.types))
+        ng, ns = len(self.groups), len(self.species_list)
+        self.group_term = np.array(gmap, np.uint32)
+        self.species_term = np.array([(smap[i] + tmap[i]) * ng + tmap[i] * ns for i in range(len(self.species_names))], np.uint32)
+        self.filename, self.length_unit, self.outputrate = filename, length_unit, int(outputrate)
+        self.modulus, self.odd, self.idmin, self.idmax = int(modulus), int(odd), int(idmin), int(idmax)
+        self.id_list = None if id_list is None else np.sort(np.asarray(id_list, np.uint64).reshape(-1))
+        self.species = None if not species else list(species)
+        big, vbig = self.default(h) if h is not None else (float("inf"), float("inf"))
+        self.rmin = [-big] * 3 if rmin is None else [float(x) for x in rmin]
+        self.rmax = [big] * 3 if rmax is None else [float(x) for x in rmax]
+        self.vmin = [-vbig] * 3 if vmin is None else [float(x) for x in vmin]
+        self.vmax = [vbig] * 3 if vmax is None else [float(x) for x in vmax]
+        self.cL = units_convert(1.0, None, length_unit)
+
+    @staticmethod
+    def default(h):
+        """(the default |bound| of x, y, z, that of the velocities) in internal units for the box h[9] (subsetWrite.c:119-139)"""
+        h = np.asarray(h, np.float64).reshape(-1)
+        big = units_convert(float("%e" % units_convert(float(max(h[0], h[4], h[8])), None, "l")), "l", None)
+        vbig = units_convert(float("%e" % np.finfo(np.float64).max), "l/t", None)
+        return big, vbig
+
+    def filter(self):
+        sel = None if self.species is None else [int(n in self.species) for n in self.species_names]
+        return dict(idmin=self.idmin, idmax=self.idmax, modulus=self.modulus, odd=self.odd, rmin=self.rmin, rmax=self.rmax, vmin=self.vmin, vmax=self.vmax,
+                    species=sel, id_list=self.id_list, group_term=self.group_term, species_term=self.species_term, cL=self.cL)
+
+    def parms_info(self):
+        """_parms_info (subsetWrite.c:149-166): the echo of the filter"""
+        lc, vc = units_convert(1.0, None, "Angstrom"), units_convert(1.0, None, "Angstrom/fs")
+        t = "idmin = %d; idmax = %d; modulus = %d; odd = %d;\n" % (self.idmin, self.idmax, self.modulus, self.odd)
+        for a, n in enumerate("xyz"):
+            t += "%smin = %f Ang; %smax = %f Ang;\n" % (n, self.rmin[a] * lc, n, self.rmax[a] * lc)
+        for a, n in enumerate("xyz"):
+            t += "v%smin = %f Ang/fs; v%smax = %f Ang/fs;\n" % (n, self.vmin[a] * vc, n, self.vmax[a] * vc)
+        return t
+
+    def misc_info(self):
+        """the pieces of subsetWriteBinaryCharmm's PioSet(file, "misc_info", ...) calls in their order (subsetWrite.c:465-481), joined by one blank"""
+        pieces = ["random = NONE;\n", "nrandomFieldSize = 0;\n", "types ="] + self.types + [";\n", "groups ="] + self.groups + [";\n", "species ="]
+        return " ".join(pieces + self.species_list + [";\n", self.parms_info()])
+
+    def header(self, nrecord, loop, time, h, version="", create_time=None):
+        """write_fileheader (io.c:352-404) for `nrecord` records: time and h in internal units"""
+        h = np.asarray(h, np.float64).reshape(-1) * units_convert(1.0, None, "l")
+        stamp = create_time or _time.strftime("%Y-%m-%d-%H:%M:%S", _time.localtime())
+        key = int(np.frombuffer(b"1234", "<i4")[0])
+        u = self.length_unit
+        t = "subset FILEHEADER {type=MULTILINE; datatype=FIXRECORDBINARY; checksum=NONE; create_time=%s; run_id=0x%08x;\n" % (stamp, 0)
+        t += "code_version=%s; srcpath=libddcmi;\n" % version
+        t += "loop=%d; time=%f fs;\n" % (loop, units_convert(time, None, "t"))
+        t += "nfiles=1; nrecord=%d; lrec=%d; nfields=5; endian_key=%d;\n" % (nrecord, SUBSET_RECORD.itemsize, key)
+        t += "field_names=id pinfo rx ry  rz;\n"
+        t += "field_types= u8 u4 f4 f4 f4;\n"
+        t += "field_units=1 1 %s %s %s;\n" % (u, u, u)
+        t += "reducedcorner=%21.14f %21.14f %21.14f;\n" % (-0.5, -0.5, -0.5)
+        t += "h=%21.14f %21.14f %21.14f\n  %21.14f %21.14f %21.14f\n  %21.14f %21.14f %21.14f Ang;\n" % tuple(h)
+        t += self.misc_info() + "\n"
+        return t + "}\n \n\n"
+
+    def file_bytes(self, records, loop, time, h, version="", create_time=None):
+        records = np.ascontiguousarray(records, SUBSET_RECORD)
+        return self.header(len(records), loop, time, h, version, create_time).encode() + records.tobytes()
+
+    def write(self, directory, records, loop, time, h, version=""):
+        """<directory>/<filename>#000000, under a temporary name first; returns the path"""
+        path = os.path.join(directory, self.filename + "#000000")
+        with open(path + ".tmp", "wb") as f:
+            f.write(self.file_bytes(records, loop, time, h, version))
+        os.rename(path + ".tmp", path)
+        return path
+
+
+def read_subset(path):
+    """(header dict, records) of a binaryCharmm subset file: every `key=value;` / `key = value;` of the FILEHEADER block as a string
+    (nrecord, lrec, nfields, nfiles, loop as int; groups, species, types, field_names, field_types, field_units as lists; h as nine
+    floats in Angstrom), and the structured array of SUBSET_RECORD behind it"""
+    raw = open(path, "rb").read()
+    end = raw.index(b"\n}\n")
+    text = raw[:end].decode()
+    off = end + 1 + len(b"}\n \n\n")      # write_fileheader closes the block and adds " \n\n"
+    if raw[end + 1:off] != b"}\n \n\n":
+        raise ValueError("%s: the header does not end as write_fileheader ends it" % path)
+    name, rest = text.split(" FILEHEADER {", 1)
+    hdr = {"name": name.strip()}
+    for item in rest.split(";"):
+        if "=" not in item:
+            continue
+        k, v = item.split("=", 1)
+        hdr[k.strip()] = v.strip()
+    for k in ("nrecord", "lrec", "nfields", "nfiles", "loop", "endian_key"):
+        hdr[k] = int(hdr[k])
+    for k in ("groups", "species", "types", "field_names", "field_types", "field_units"):
+        hdr[k] = hdr.get(k, "").split()
+    hdr["h"] = [float(x) for x in hdr["h"].split()[:9]]
+    if hdr["lrec"] != SUBSET_RECORD.itemsize or hdr["datatype"] != "FIXRECORDBINARY":
+        raise ValueError("%s: lrec = %d, datatype = %s: not a binaryCharmm subset file" % (path, hdr["lrec"], hdr["datatype"]))
+    if len(raw) - off != hdr["nrecord"] * hdr["lrec"]:
+        raise ValueError("%s: %d bytes behind the header, nrecord * lrec = %d" % (path, len(raw) - off, hdr["nrecord"] * hdr["lrec"]))
+    return hdr, np.frombuffer(raw, SUBSET_RECORD, count=hdr["nrecord"], offset=off).copy()

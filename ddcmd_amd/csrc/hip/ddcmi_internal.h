@@ -373,6 +373,8 @@ struct ddcmi_ctx
     * (k_gather_state, the migration records) */
    dbuf<VafRec> vaf, vaf2; bool vaf_on = false;
    dbuf<double> census_part;      /* the census passes (ddcmi_census_frame.inl): the pass's per-workgroup sums and, behind them, its result */
+   /* subsetWrite's frames (ddcmi_subset.inl): the filter's tables with the workgroups' counts and offsets, the idList, the packed records */
+   dbuf<unsigned> subset_tab; dbuf<unsigned long long> subset_ids, subset_rec;
    /* what is not a dbuf or an hbuf; those free themselves after this */
    ~ddcmi_ctx()
    {

@@ -8,6 +8,7 @@
 #include <math.h>
 #include <inttypes.h>
 #include <sys/stat.h>
+#include <time.h>
 
 static int analysis_due(int rate, int64_t loop) { return rate > 0 && loop % rate == 0; }      /* TEST0 */
 /* snapshot.<loop>/<filename>, opened for writing (rank 0) */
@@ -594,6 +595,209 @@ static void dsf_free(void *state)      /* dsf_close */
    free(p->axis); free(p->mk); free(p->select); free(p->loop); free(p->time); free(p->buffer); free(p->rho); free(p);
 }
 
+/* ANALYSIS type subsetWrite | subset_write with format = binaryCharmm (subsetWrite.c: parms :62-168, subsetWriteBinaryCharmm :409-522,
+ * rejectParticle :532-564; pinfo.c; write_fileheader, io.c:352-404): a trajectory frame of the beads a filter selects.  eval does
+ * nothing, as in the reference.  At outputrate every rank takes its records from the device (ddcmi_subset_records: selected, compacted
+ * and packed there, 24 bytes per selected bead), the counts are gathered, then the blocks on rank 0 in rank order, and rank 0 writes
+ * snapshot.<loop>/<filename>#000000 -- header, then the records -- under a temporary name and renames it.  One file whatever nfiles
+ * says.  The other formats (pio, ovito) carry a per-bead potential energy that the device does not keep: deck.c leaves those objects
+ * unsupported.  Refused at load where the reference would crash: modulus < 1 (a division by zero), a species the system lacks, a pinfo
+ * range beyond 4 bytes (deck.c).
+ * pinfo (pinfoEncodeInit / pinfoEncode): the distinct group names and the distinct species names in index order; every species has the
+ * type ATOM on this path, so pinfo = gMap[group] + sMap[species] * nGroups.  The reference leaves gMap / sMap of a repeated name
+ * unset; here it is the index of the name's first occurrence, the object pinfoDecode's lookup by name would return.
+ * misc_info: the pieces of the reference's PioSet(file, "misc_info", ...) calls in their order, joined by one blank (pio.c is not part
+ * of the reference tree; the blank is how its other headers read). */
+int ddcmi_pinfo_fits(int ngroups, int nspecies, int ntypes)
+{
+   if (ngroups < 1 || nspecies < 1 || ntypes < 1) return 1;
+   return (double)ngroups * (double)nspecies * (double)ntypes <= 4294967295.0;
+}
+typedef struct { ddcmi_subset_filter f; int *include; uint32_t *gterm, *sterm; int nug, nus; char **ugname, **usname; char *info; } SWSTATE;
+static void sw_parms(const OBJECT *obj, ddcmi_analysis *an, char *msg, int msglen)
+{
+   static const char *const rkey[6] = {"xmin", "xmax", "ymin", "ymax", "zmin", "zmax"};
+   static const char *const vkey[6] = {"vxmin", "vxmax", "vymin", "vymax", "vzmin", "vzmax"};
+   char buf[32];
+   object_get(obj, "nfiles", &an->sw_nfiles, INT, 1, "0");
+   object_get(obj, "modulus", &an->sw_modulus, INT, 1, "1");
+   if (object_testforkeyword(obj, "idList"))
+   {
+      an->sw_nid = object_getv(obj, "idList", (void **)&an->sw_idlist, U64, IGNORE_IF_NOT_FOUND);
+      if (an->sw_nid < 0) an->sw_nid = 0;
+      if (!an->sw_idlist) an->sw_idlist = zalloc(1, sizeof(uint64_t));      /* "idList = ;": a list without a member selects nothing */
+      for (int i = 1; i < an->sw_nid; i++)      /* qsort(compareGid) */
+      {
+         const uint64_t v = an->sw_idlist[i];
+         int j = i;
+         for (; j > 0 && an->sw_idlist[j - 1] > v; j--) an->sw_idlist[j] = an->sw_idlist[j - 1];
+         an->sw_idlist[j] = v;
+      }
+   }
+   object_get(obj, "idmin", &an->sw_idmin, U64, 1, "0");
+   snprintf(buf, sizeof(buf), "%" PRIu64, (uint64_t)UINT64_MAX);      /* gid_max */
+   object_get(obj, "idmax", &an->sw_idmax, U64, 1, buf);
+   object_get(obj, "odd", &an->sw_odd, INT, 1, "0");
+   object_get(obj, "lengthUnit", &an->sw_length_unit, LITERAL, 1, "Ang");
+   if (an->sw_length_unit)      /* (a literal keeps the blanks around it) */
+   {
+      char *b = an->sw_length_unit, *e = b + strlen(b);
+      while (*b == ' ' || *b == '\t' || *b == '\n') b++;
+      while (e > b && (e[-1] == ' ' || e[-1] == '\t' || e[-1] == '\n')) e--;
+      memmove(an->sw_length_unit, b, (size_t)(e - b)); an->sw_length_unit[e - b] = 0;
+   }
+   if (!an->sw_length_unit || !an->sw_length_unit[0]) { free(an->sw_length_unit); an->sw_length_unit = strdup("Ang"); }
+   if (object_testforkeyword(obj, "species"))
+   {
+      an->sw_nspecies = object_getv(obj, "species", (void **)&an->sw_species, STRING, IGNORE_IF_NOT_FOUND);
+      if (an->sw_nspecies < 0) an->sw_nspecies = 0;
+   }
+   for (int k = 0; k < 6; k++)
+   {
+      double *r = (k & 1) ? &an->sw_rmax[k / 2] : &an->sw_rmin[k / 2], *v = (k & 1) ? &an->sw_vmax[k / 2] : &an->sw_vmin[k / 2];
+      if (object_testforkeyword(obj, rkey[k])) { object_get(obj, rkey[k], r, WITH_UNITS, 1, "0", "l", NULL); an->sw_given |= 1 << k; }
+      if (object_testforkeyword(obj, vkey[k])) { object_get(obj, vkey[k], v, WITH_UNITS, 1, "0", "l/t", NULL); an->sw_given |= 1 << (6 + k); }
+   }
+   const double cL = units_convert(1.0, NULL, an->sw_length_unit);
+   if (an->sw_modulus < 1) snprintf(msg, msglen, "ANALYSIS %s: modulus = %d, it must be at least 1", an->name, an->sw_modulus);
+   else if (!isfinite(cL) || cL == 0.0) snprintf(msg, msglen, "ANALYSIS %s: lengthUnit = %s gives no finite conversion factor", an->name, an->sw_length_unit);
+}
+/* the distinct names of list[n] in order, and every entry's index among them (a repeated name: its first occurrence's) */
+static int sw_unique(int n, char *const *list, char **uniq, int *map)
+{
+   int nu = 0;
+   for (int i = 0; i < n; i++)
+   {
+      int k = 0;
+      while (k < nu && strcmp(uniq[k], list[i]) != 0) k++;
+      if (k == nu) uniq[nu++] = list[i];
+      map[i] = k;
+   }
+   return nu;
+}
+static void *sw_init(SIMULATE *simulate, const ddcmi_analysis *an)
+{
+   const ddcmi_setup *s = simulate->setup;
+   SWSTATE *p = zalloc(1, sizeof(SWSTATE));
+   const int ng = s->ngroup > 0 ? s->ngroup : 1, ns = s->nspecies;
+   static char one_group[] = "group";
+   char *one[1] = {one_group};
+   char *const *gnames = s->ngroup > 0 ? s->group_name : one;
+   p->ugname = zalloc(ng, sizeof(char *)); p->usname = zalloc(ns + 1, sizeof(char *));
+   int *gmap = zalloc(ng, sizeof(int)), *smap = zalloc(ns + 1, sizeof(int));
+   p->nug = sw_unique(ng, gnames, p->ugname, gmap);
+   p->nus = sw_unique(ns, s->species_name, p->usname, smap);
+   if (s->ngroup <= 0) p->ugname[0] = one_group;
+   p->gterm = zalloc(ng, sizeof(uint32_t)); p->sterm = zalloc(ns + 1, sizeof(uint32_t)); p->include = zalloc(ns + 1, sizeof(int));
+   for (int g = 0; g < ng; g++) p->gterm[g] = (uint32_t)gmap[g];
+   const uint32_t kSType = 0;      /* the one type, ATOM */
+   for (int i = 0; i < ns; i++) p->sterm[i] = ((uint32_t)smap[i] + kSType) * (uint32_t)p->nug + kSType * (uint32_t)p->nus;      /* pinfoEncode */
+   free(gmap); free(smap);
+   for (int i = 0; i < ns; i++)
+   {
+      p->include[i] = an->sw_nspecies <= 0;
+      for (int k = 0; k < an->sw_nspecies; k++) if (strcmp(an->sw_species[k], s->species_name[i]) == 0) p->include[i] = 1;
+   }
+   ddcmi_subset_filter *f = &p->f;
+   f->idmin = an->sw_idmin; f->idmax = an->sw_idmax; f->modulus = an->sw_modulus; f->odd = an->sw_odd;
+   for (int a = 0; a < 3; a++) { f->rmin[a] = an->sw_rmin[a]; f->rmax[a] = an->sw_rmax[a]; f->vmin[a] = an->sw_vmin[a]; f->vmax[a] = an->sw_vmax[a]; }
+   f->nspecies = ns; f->ngroup = ng; f->include_species = p->include; f->group_term = p->gterm; f->species_term = p->sterm;
+   f->nid = an->sw_idlist ? an->sw_nid : 0; f->idlist = an->sw_idlist;
+   f->cL = units_convert(1.0, NULL, an->sw_length_unit);
+   /* _parms_info, subsetWrite.c:149-166 */
+   const double lc = units_convert(1.0, NULL, "Angstrom"), vc = units_convert(1.0, NULL, "Angstrom/fs");
+   char string[1024];
+   snprintf(string, 1023, "idmin = %" PRIu64 "; idmax = %" PRIu64 "; modulus = %d; odd = %d;\n"
+            "xmin = %f Ang; xmax = %f Ang;\n" "ymin = %f Ang; ymax = %f Ang;\n" "zmin = %f Ang; zmax = %f Ang;\n"
+            "vxmin = %f Ang/fs; vxmax = %f Ang/fs;\n" "vymin = %f Ang/fs; vymax = %f Ang/fs;\n" "vzmin = %f Ang/fs; vzmax = %f Ang/fs;\n",
+            an->sw_idmin, an->sw_idmax, an->sw_modulus, an->sw_odd, an->sw_rmin[0] * lc, an->sw_rmax[0] * lc, an->sw_rmin[1] * lc, an->sw_rmax[1] * lc,
+            an->sw_rmin[2] * lc, an->sw_rmax[2] * lc, an->sw_vmin[0] * vc, an->sw_vmax[0] * vc, an->sw_vmin[1] * vc, an->sw_vmax[1] * vc,
+            an->sw_vmin[2] * vc, an->sw_vmax[2] * vc);
+   p->info = strdup(string);
+   return p;
+}
+static void sw_eval(SIMULATE *simulate, const ddcmi_analysis *an, void *state) { (void)simulate; (void)an; (void)state; }
+static void sw_output(SIMULATE *simulate, const ddcmi_analysis *an, void *state)
+{
+   SWSTATE *p = state;
+   ddcmi_ctx *ctx = simulate->accelerator->parms;
+   const char *where = "subsetWrite_output";
+   double h[9];
+   if (ddcmi_get_box(ctx, h) != DDCMI_OK) die(where, ddcmi_last_error(ctx));
+   for (int a = 0; a < 3; a++) p->f.corner[a] = h[4 * a] * -0.5;      /* box->corner = h0 * reducedcorner, reducedcorner = -0.5 on this path */
+   int64_t n = 0;
+   if (ddcmi_subset_records(ctx, &p->f, 0, NULL, &n) != DDCMI_OK) die(where, ddcmi_last_error(ctx));
+   int64_t *cnt = zalloc(par.world, sizeof(int64_t));
+   cnt[0] = n;
+   if (par.world > 1 && ddcmi_rdzv_allgather(par.rdzv, &n, cnt, sizeof(int64_t)) != DDCMI_OK) die(where, ddcmi_rdzv_last_error(par.rdzv));
+   int64_t tot = 0;
+   for (int r = 0; r < par.world; r++) tot += cnt[r];
+   ddcmi_subset_record *rec = zalloc((size_t)(par.rank == 0 ? tot : n) + 1, sizeof(ddcmi_subset_record));
+   int64_t got = 0;
+   if (n > 0 && ddcmi_subset_records(ctx, &p->f, n, rec, &got) != DDCMI_OK) die(where, ddcmi_last_error(ctx));
+   if (n > 0 && got != n) die(where, "the filter selected another number of beads the second time");
+   if (par.world > 1 && par.rank != 0)
+   {
+      const int peer = 0; const void *sb = rec; const size_t sbytes = sizeof(ddcmi_subset_record) * (size_t)n;
+      if (ddcmi_rdzv_exchange(par.rdzv, n > 0 ? 1 : 0, &peer, &sb, &sbytes, 0, NULL, NULL, NULL) != DDCMI_OK) die(where, ddcmi_rdzv_last_error(par.rdzv));
+   }
+   else if (par.world > 1)
+   {
+      int *peer = zalloc(par.world, sizeof(int)); void **rb = zalloc(par.world, sizeof(void *)); size_t *rbytes = zalloc(par.world, sizeof(size_t));
+      int nr = 0; size_t off = (size_t)n;
+      for (int r = 1; r < par.world; r++)
+      {
+         if (cnt[r] > 0) { peer[nr] = r; rb[nr] = rec + off; rbytes[nr] = sizeof(ddcmi_subset_record) * (size_t)cnt[r]; nr++; }
+         off += (size_t)cnt[r];
+      }
+      if (ddcmi_rdzv_exchange(par.rdzv, 0, NULL, NULL, NULL, nr, peer, rb, rbytes) != DDCMI_OK) die(where, ddcmi_rdzv_last_error(par.rdzv));
+      free(peer); free(rb); free(rbytes);
+   }
+   if (par.rank == 0)
+   {
+      char name[700], tmpname[720], dir[512], path[1300], tmppath[1300];
+      snprintf(name, sizeof(name), "%s#000000", an->filename);
+      snprintf(tmpname, sizeof(tmpname), "%s.tmp", name);
+      FILE *f = snapshot_fopen(simulate, tmpname, where);
+      time_t now = time(NULL);
+      char stamp[64];
+      strftime(stamp, sizeof(stamp), "%Y-%m-%d-%H:%M:%S", localtime(&now));
+      int key;
+      memcpy(&key, "1234", 4);
+      const double cLen = units_convert(1.0, NULL, "l");
+      const char *u = an->sw_length_unit;
+      /* write_fileheader */
+      fprintf(f, "subset FILEHEADER {type=MULTILINE; datatype=FIXRECORDBINARY; checksum=NONE; create_time=%s; run_id=0x%08x;\n", stamp, 0u);
+      fprintf(f, "code_version=%s; srcpath=libddcmi;\n", ddcmi_version());
+      fprintf(f, "loop=%" PRId64 "; time=%f fs;\n", simulate->loop, units_convert(simulate->time, NULL, "t"));
+      fprintf(f, "nfiles=1; nrecord=%" PRIu64 "; lrec=%d; nfields=5; endian_key=%d;\n", (uint64_t)tot, (int)sizeof(ddcmi_subset_record), key);
+      fprintf(f, "field_names=id pinfo rx ry  rz;\n");
+      fprintf(f, "field_types= u8 u4 f4 f4 f4;\n");
+      fprintf(f, "field_units=1 1 %s %s %s;\n", u, u, u);
+      fprintf(f, "reducedcorner=%21.14f %21.14f %21.14f;\n", -0.5, -0.5, -0.5);
+      fprintf(f, "h=%21.14f %21.14f %21.14f\n  %21.14f %21.14f %21.14f\n  %21.14f %21.14f %21.14f Ang;\n",
+              h[0] * cLen, h[1] * cLen, h[2] * cLen, h[3] * cLen, h[4] * cLen, h[5] * cLen, h[6] * cLen, h[7] * cLen, h[8] * cLen);
+      fprintf(f, "random = NONE;\n nrandomFieldSize = 0;\n types = ATOM ;\n groups =");
+      for (int g = 0; g < p->nug; g++) fprintf(f, " %s", p->ugname[g]);
+      fprintf(f, " ;\n species =");
+      for (int i = 0; i < p->nus; i++) fprintf(f, " %s", p->usname[i]);
+      fprintf(f, " ;\n %s\n", p->info);
+      fprintf(f, "}\n \n\n");
+      if (tot > 0 && fwrite(rec, sizeof(ddcmi_subset_record), (size_t)tot, f) != (size_t)tot) die(where, "cannot write the records");
+      if (fclose(f) != 0) die(where, "cannot write the output file");
+      snprintf(dir, sizeof(dir), "snapshot.%012" PRId64, simulate->loop);
+      snprintf(path, sizeof(path), "%s/%s", dir, name);
+      snprintf(tmppath, sizeof(tmppath), "%s/%s", dir, tmpname);
+      if (rename(tmppath, path) != 0) die(where, "cannot rename the output file");
+   }
+   free(rec); free(cnt);
+}
+static void sw_free(void *state)
+{
+   SWSTATE *p = state;
+   free(p->include); free(p->gterm); free(p->sterm); free(p->ugname); free(p->usname); free(p->info); free(p);
+}
+
 /* ------------------------------------------------------------------------- */
 static const char *const dsf_heads[] = {"DynamicStructureFactor", "Dynamic_Structure_Factor", NULL};
 static const ANALYSIS_TYPE types[] = {      /* indexed by enum ddcmi_analysis_kind; DDCMI_AN_NONE has no row */
@@ -603,6 +807,7 @@ static const ANALYSIS_TYPE types[] = {      /* indexed by enum ddcmi_analysis_ki
    [DDCMI_AN_ZDENSITY] = {"zdensity", DDCMI_AN_ZDENSITY, "zden.dat", zd_parms, zd_init, zd_eval, zd_output, NULL, zd_free, 1, NULL},
    [DDCMI_AN_KDIST] = {"KINETICENERGYDISTN", DDCMI_AN_KDIST, "kinetic.data", kd_parms, kd_init, kd_eval, kd_output, kd_clear, kd_free},
    [DDCMI_AN_DSF] = {"DSF", DDCMI_AN_DSF, "rho_k.data", dsf_parms, dsf_init, dsf_eval, dsf_output, NULL, dsf_free, 0, NULL, dsf_heads},
+   [DDCMI_AN_SUBSETWRITE] = {"subsetWrite", DDCMI_AN_SUBSETWRITE, "subset", sw_parms, sw_init, sw_eval, sw_output, NULL, sw_free, 1, "subset_write"},
 };
 const ANALYSIS_TYPE *analysis_type_find(const char *type_name)
 {

@@ -25,6 +25,8 @@ typedef struct analysis_type_st
    const char *const *heads;                               /* further heads (rows matched by the head), NULL-terminated, or NULL */
 } ANALYSIS_TYPE;
 const ANALYSIS_TYPE *analysis_type_find(const char *type_name);      /* NULL: not supported */
+/* pinfoMaxIndex (pinfo.c:148-151) of that many distinct group, species and type names fits the 4-byte field of a binaryCharmm record */
+int ddcmi_pinfo_fits(int ngroups, int nspecies, int ntypes);
 
 /* the driver's walks over the supported analyses of simulate->setup, in the order of the deck's list */
 void analysis_init_all(SIMULATE *simulate);                           /* names every other analysis once on stderr */

@@ -1,6 +1,7 @@
 /* deck.c -- see deck.h. */
 #include "deck.h"
 #include "analysis.h"
+#include <float.h>
 #include "object.h"
 #include "units.h"
 #include <stdio.h>
@@ -557,6 +558,14 @@ ddcmi_setup *ddcmi_deck_load_with(const char *object_file, const char *restart_f
             object_get(ao, "eval_rate", &an->eval_rate, INT, 1, "0");
             object_get(ao, "outputrate", &an->outputrate, INT, 1, "0");
             const ANALYSIS_TYPE *row = analysis_type_find(an->type_name);
+            if (row && row->type == DDCMI_AN_SUBSETWRITE)
+            {
+               /* subsetWrite (subsetWrite.c:170-176): only format = binaryCharmm is written; pio (the default) and ovito need a per-bead
+                * potential energy, which the device does not keep: those objects stay unsupported */
+               char *format = get_string(ao, "format", "pio");
+               if (!format || strcmp(format, "binaryCharmm") != 0) row = NULL;
+               free(format);
+            }
             if (!row) continue;
             an->type = row->type;
             an->filename = get_string(ao, "filename", row->filename);
@@ -791,6 +800,35 @@ ddcmi_setup *ddcmi_deck_load_with(const char *object_file, const char *restart_f
          int found = 0;
          for (int i = 0; i < s->nspecies; i++) found |= strcmp(an->dsf_species, s->species_name[i]) == 0;
          if (!found) FAIL("ANALYSIS %s: species = %s, and the system has no species of that name", an->name, an->dsf_species);
+      }
+      /* ANALYSIS subsetWrite: its species are the system's (species_find returns NULL and the reference dereferences it,
+       * subsetWrite.c:101-102); the bounds the deck leaves out (subsetWrite.c:119-139); the pinfo field (its assert, :419) */
+      for (int a = 0; a < s->nanalysis; a++)
+      {
+         ddcmi_analysis *an = &s->analysis[a];
+         if (an->type != DDCMI_AN_SUBSETWRITE) continue;
+         for (int k = 0; k < an->sw_nspecies; k++)
+         {
+            int found = 0;
+            for (int i = 0; i < s->nspecies; i++) found |= strcmp(an->sw_species[k], s->species_name[i]) == 0;
+            if (!found) FAIL("ANALYSIS %s: species = %s, and the system has no species of that name", an->name, an->sw_species[k]);
+         }
+         double maxSize = s->h[0] > s->h[4] ? s->h[0] : s->h[4];
+         if (s->h[8] > maxSize) maxSize = s->h[8];
+         char buf[64];
+         snprintf(buf, sizeof(buf), "%e", units_convert(maxSize, NULL, "l"));
+         const double big = units_convert(strtod(buf, NULL), "l", NULL);
+         snprintf(buf, sizeof(buf), "%e", DBL_MAX);
+         const double vbig = units_convert(strtod(buf, NULL), "l/t", NULL);
+         for (int k = 0; k < 3; k++)
+         {
+            if (!(an->sw_given >> (2 * k) & 1)) an->sw_rmin[k] = -big;
+            if (!(an->sw_given >> (2 * k + 1) & 1)) an->sw_rmax[k] = big;
+            if (!(an->sw_given >> (6 + 2 * k) & 1)) an->sw_vmin[k] = -vbig;
+            if (!(an->sw_given >> (6 + 2 * k + 1) & 1)) an->sw_vmax[k] = vbig;
+         }
+         if (!ddcmi_pinfo_fits(s->ngroup > 0 ? s->ngroup : 1, s->nspecies, 1))
+            FAIL("ANALYSIS %s: %d groups and %d species need a pinfo field of more than 4 bytes", an->name, s->ngroup, s->nspecies);
       }
    }
    /* POTENTIAL type=MARTINI */
@@ -1098,6 +1136,8 @@ void ddcmi_setup_free(ddcmi_setup *s)
       ddcmi_analysis *an = &s->analysis[a];
       for (int g = 0; g < an->ndist; g++) { free(an->dist[g].name); free(an->dist[g].species); }
       free(an->dist); free(an->name); free(an->type_name); free(an->filename); free(an->m); free(an->dsf_species);
+      for (int k = 0; k < an->sw_nspecies; k++) free(an->sw_species[k]);
+      free(an->sw_species); free(an->sw_idlist); free(an->sw_length_unit);
    }
    free(s->analysis);
    free(s->u_pressure); free(s->u_volume); free(s->u_temperature); free(s->u_energy); free(s->u_time); free(s->u_length);

@@ -19,7 +19,7 @@ enum { DDCMI_GROUP_FREE = 0, DDCMI_GROUP_BERENDSEN = 1, DDCMI_GROUP_LANGEVIN = 2
 
 /* one ANALYSIS object (analysis_init, analysis.c:120-160).  type: the row of host/analysis.c's table that evaluates it; DDCMI_AN_NONE is any
  * other type (not supported: the driver names it once on stderr) */
-enum ddcmi_analysis_kind { DDCMI_AN_NONE = 0, DDCMI_AN_PAIRCORRELATION, DDCMI_AN_VAF, DDCMI_AN_VCMWRITE, DDCMI_AN_ZDENSITY, DDCMI_AN_KDIST, DDCMI_AN_DSF };
+enum ddcmi_analysis_kind { DDCMI_AN_NONE = 0, DDCMI_AN_PAIRCORRELATION, DDCMI_AN_VAF, DDCMI_AN_VCMWRITE, DDCMI_AN_ZDENSITY, DDCMI_AN_KDIST, DDCMI_AN_DSF, DDCMI_AN_SUBSETWRITE };
 /* one BIN object of a KINETICENERGYDISTN analysis (kineticEnergyDistn.c:58-83): the histogram of one species' kinetic energies */
 typedef struct ddcmi_kdist_group { char *name, *species; double emin, emax; int nbins; } ddcmi_kdist_group;      /* internal energy units; nbins >= 1, emax > emin */
 typedef struct ddcmi_analysis
@@ -38,6 +38,17 @@ typedef struct ddcmi_analysis
    int nm;                      /* from here on DSF only (dsf.c:33-96), zero / NULL otherwise: the list of the `m` key as written (an entry <= 0 adds no wave vector) */
    int *m;
    char *dsf_species;           /* the one species that takes part, or NULL: every bead */
+   /* from here on subsetWrite with format = binaryCharmm only (subsetWrite.c:72-139), zero / NULL otherwise.  Internal units; a bound
+    * the deck leaves out is the reference's default: -+ the longest box edge (through its "%e") for x, y, z, -+ DBL_MAX for the velocities */
+   char *sw_length_unit;        /* lengthUnit, default Ang: the unit of the records' coordinates */
+   int sw_modulus, sw_odd, sw_nfiles;      /* nfiles is read and ignored: one file */
+   uint64_t sw_idmin, sw_idmax;
+   int sw_nid;                  /* idList, sorted ascending; sw_idlist NULL: no such key */
+   uint64_t *sw_idlist;
+   int sw_nspecies;             /* the names of the species key; 0: every species */
+   char **sw_species;
+   double sw_rmin[3], sw_rmax[3], sw_vmin[3], sw_vmax[3];
+   int sw_given;                /* bit 2 a + q of x, y, z and 6 + 2 a + q of vx, vy, vz: the deck has the key (q = 0 min, 1 max) */
 } ddcmi_analysis;
 
 typedef struct ddcmi_setup

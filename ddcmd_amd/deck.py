@@ -181,7 +181,7 @@ def load_deck(object_file, restart_file=None, extra_objects=None):
         s.integrator_type = c.integrator_type.decode()
         s.accelerator_type = c.accelerator_type.decode()
         s.units = {k: getattr(c, "u_" + k).decode() for k in ("pressure", "volume", "temperature", "energy", "time", "length")}
-        # SIMULATE analysis = ...: one dict per ANALYSIS object, in list order (types PAIRCORRELATION, VELOCITYAUTOCORRELATION, vcmWrite, zdensity, KINETICENERGYDISTN and DSF with their parameters, internal units)
+        # SIMULATE analysis = ...: one dict per ANALYSIS object, in list order (types PAIRCORRELATION, VELOCITYAUTOCORRELATION, vcmWrite, zdensity, KINETICENERGYDISTN, DSF and subsetWrite with format = binaryCharmm, with their parameters, internal units)
         s.analysis = []
         for a in (c.analysis[i] for i in range(int(c.nanalysis))):
             d = {"name": a.name.decode(), "type": (a.type_name or b"").decode(), "eval_rate": int(a.eval_rate), "outputrate": int(a.outputrate),
@@ -198,6 +198,12 @@ def load_deck(object_file, restart_file=None, extra_objects=None):
                                        "nbins": int(g.nbins)} for g in (a.dist[k] for k in range(int(a.ndist)))])
             if a.type == _lib.AN_DSF:
                 d.update(m=[int(a.m[k]) for k in range(int(a.nm))], species=a.dsf_species.decode() if a.dsf_species else None)
+            if a.type == _lib.AN_SUBSETWRITE:      # format = binaryCharmm; bounds in internal units, the reference's defaults where the deck has none
+                d.update(format="binaryCharmm", length_unit=a.sw_length_unit.decode(), modulus=int(a.sw_modulus), odd=int(a.sw_odd), nfiles=int(a.sw_nfiles),
+                         idmin=int(a.sw_idmin), idmax=int(a.sw_idmax),
+                         id_list=[int(a.sw_idlist[k]) for k in range(int(a.sw_nid))] if a.sw_idlist else None,
+                         species=[a.sw_species[k].decode() for k in range(int(a.sw_nspecies))] or None,
+                         rmin=list(a.sw_rmin), rmax=list(a.sw_rmax), vmin=list(a.sw_vmin), vmax=list(a.sw_vmax))
             s.analysis.append(d)
     finally:
         lib.ddcmi_setup_free(p)

@@ -56,6 +56,51 @@ def _dsf_args(nspecies, mmax, select, nrank=1):
     return sel, np.zeros((nrank, 3, max(int(mmax), 1), 2)), np.zeros(nrank, np.int64)
 
 
+SUBSET_RECORD = np.dtype([("id", "<u8"), ("pinfo", "<u4"), ("r", "<f4", (3,))])      # struct ddcmi_subset_record: 24 bytes, the file's record
+GID_MAX = 2 ** 64 - 1
+
+
+class CSubsetFilter(ctypes.Structure):
+    """Mirror of struct ddcmi_subset_filter (include/ddcmi.h)."""
+    _fields_ = [("idmin", ctypes.c_uint64), ("idmax", ctypes.c_uint64), ("modulus", ctypes.c_int), ("odd", ctypes.c_int),
+                ("rmin", ctypes.c_double * 3), ("rmax", ctypes.c_double * 3), ("vmin", ctypes.c_double * 3), ("vmax", ctypes.c_double * 3),
+                ("nspecies", ctypes.c_int), ("ngroup", ctypes.c_int), ("include_species", _ip),
+                ("group_term", ctypes.POINTER(ctypes.c_uint32)), ("species_term", ctypes.POINTER(ctypes.c_uint32)),
+                ("nid", ctypes.c_int64), ("idlist", _up), ("corner", ctypes.c_double * 3), ("cL", ctypes.c_double)]
+
+
+def _subset_filter(setup, idmin=0, idmax=GID_MAX, modulus=1, odd=False, rmin=None, rmax=None, vmin=None, vmax=None, species=None, id_list=None,
+                   group_term=None, species_term=None, corner=None, cL=1.0):
+    """(struct ddcmi_subset_filter, the arrays it points into) of ddcmi_subset_records.  Bounds in internal units, None: -+ inf; species:
+    one flag per species, None: all; id_list: ascending gids, None: no list; the two pinfo tables default to {group index} and {species
+    index * number of groups}; corner defaults to the box's (-L/2)."""
+    ns, ng = int(setup.nspecies), max(1, int(setup.ngroup))
+    inf = float("inf")
+    keep = {"include": None if species is None else np.ascontiguousarray(np.asarray(species) != 0, np.int32).reshape(-1),
+            "gterm": np.ascontiguousarray(np.arange(ng) if group_term is None else group_term, np.uint32).reshape(-1),
+            "sterm": np.ascontiguousarray(np.arange(ns) * ng if species_term is None else species_term, np.uint32).reshape(-1),
+            "ids": None if id_list is None else np.ascontiguousarray(np.concatenate([np.asarray(id_list, np.uint64).reshape(-1), np.zeros(1, np.uint64)]))}
+    if keep["include"] is not None and len(keep["include"]) != ns:
+        raise ValueError("subset_records: %d entries of species for %d species" % (len(keep["include"]), ns))
+    f = CSubsetFilter()
+    f.idmin, f.idmax, f.modulus, f.odd = int(idmin), int(idmax), int(modulus), int(bool(odd))
+    for k, (lo, hi) in enumerate(((rmin, rmax), (vmin, vmax))):
+        for a in range(3):
+            (f.rmin, f.vmin)[k][a] = -inf if lo is None else float(lo[a])
+            (f.rmax, f.vmax)[k][a] = inf if hi is None else float(hi[a])
+    f.nspecies, f.ngroup = len(keep["sterm"]), len(keep["gterm"])
+    f.include_species = _i(keep["include"])
+    f.group_term = keep["gterm"].ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
+    f.species_term = keep["sterm"].ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
+    f.nid = 0 if keep["ids"] is None else len(keep["ids"]) - 1      # (one spare entry: a list without a member still has an address)
+    f.idlist = None if keep["ids"] is None else keep["ids"].ctypes.data_as(_up)
+    box = np.asarray(setup.h, np.float64).reshape(-1)[[0, 4, 8]]
+    for a in range(3):
+        f.corner[a] = -0.5 * box[a] if corner is None else float(corner[a])
+    f.cL = float(cL)
+    return f, keep
+
+
 def _declare(lib):
     if getattr(lib, "_ddcmi_declared", False):
         return
@@ -135,6 +180,7 @@ def _declare(lib):
     lib.ddcmi_zdensity.argtypes = [vp, ctypes.c_int, ctypes.c_double, ctypes.c_int, _dp]
     lib.ddcmi_kinetic_energy_distn.argtypes = [vp, ctypes.c_int, ctypes.c_int, _dp, _dp, _ip, _ip, _lp, _lp, _dp]
     lib.ddcmi_charge_density_modes.argtypes = [vp, ctypes.c_int, _ip, ctypes.c_int, _dp, _lp]
+    lib.ddcmi_subset_records.argtypes = [vp, ctypes.POINTER(CSubsetFilter), ctypes.c_int64, vp, _lp]
     lib._ddcmi_declared = True
 
 
@@ -620,6 +666,21 @@ class MartiniHIP(object):
         self._chk(self.lib.ddcmi_charge_density_modes(self.ctx, int(self.s.nspecies), _i(sel), int(mmax), _d(rho), count.ctypes.data_as(_lp)))
         return rho[0, :, :, 0] + 1j * rho[0, :, :, 1], int(count[0])
 
+    def subset_records(self, count_only=False, cap=None, out=None, **filt):
+        """ANALYSIS subsetWrite, format binaryCharmm: this rank's selected beads as the file's records (ddcmi_subset_records), a
+        structured array of SUBSET_RECORD (id u8, pinfo u4, r 3 x f4) in the order of download_particles.  The filter's keywords are
+        those of _subset_filter.  count_only: the count alone.  cap / out: the capacity handed down (default: the count) and the
+        array the records land in -- for the refusal of a buffer that is too small."""
+        f, keep = _subset_filter(self.s, **filt)
+        n = np.zeros(1, np.int64)
+        self._chk(self.lib.ddcmi_subset_records(self.ctx, ctypes.byref(f), 0, None, n.ctypes.data_as(_lp)))
+        if count_only:
+            return int(n[0])
+        rec = np.zeros(int(n[0]), SUBSET_RECORD) if out is None else out
+        self._chk(self.lib.ddcmi_subset_records(self.ctx, ctypes.byref(f), int(n[0]) if cap is None else int(cap), rec.ctypes.data_as(ctypes.c_void_p), n.ctypes.data_as(_lp)))
+        del keep
+        return rec[:int(n[0])]
+
     def download(self, mask=POS | VEL | FORCE):
         n = self.n
         out = [np.zeros(n) for _ in range(9)]
@@ -713,6 +774,7 @@ def _declare_domains(lib):
     lib.ddcmi_group_zdensity.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, _dp]
     lib.ddcmi_group_kinetic_energy_distn.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _ip, _ip, _lp, _lp, _dp]
     lib.ddcmi_group_charge_density_modes.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int, _ip, ctypes.c_int, _dp, _lp]
+    lib.ddcmi_group_subset_records.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.POINTER(CSubsetFilter), ctypes.c_int64, vp, _lp]
     lib._ddcmi_dom_declared = True
 
 
@@ -930,6 +992,17 @@ class MartiniGroup(object):
         if per_rank:
             return z, count
         return self._sum_in_rank_order(z), int(count.sum())
+
+    def subset_records(self, per_rank=False, cap=None, out=None, **filt):
+        """ddcmi_group_subset_records: the domains' records one block behind the other in rank order -- or, per_rank, (records, count[rank])"""
+        f, keep = _subset_filter(self.s, **filt)
+        n = np.zeros(self.n, np.int64)
+        self._chk(self.lib.ddcmi_group_subset_records(self.arr, self.n, ctypes.byref(f), 0, None, n.ctypes.data_as(_lp)))
+        tot = int(n.sum())
+        rec = np.zeros(tot, SUBSET_RECORD) if out is None else out
+        self._chk(self.lib.ddcmi_group_subset_records(self.arr, self.n, ctypes.byref(f), tot if cap is None else int(cap), rec.ctypes.data_as(ctypes.c_void_p), n.ctypes.data_as(_lp)))
+        del keep
+        return (rec[:tot], n) if per_rank else rec[:tot]
 
     def energies(self):
         """sum over ranks = energyInfo.c allreduce()"""

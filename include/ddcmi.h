@@ -261,7 +261,7 @@ int ddcmi_vaf_sample(ddcmi_ctx *ctx, int ngroup, int nspecies, double *vaf, doub
  * run every rank calls it at the same point of the run, as with the origin: the migration records carry the reference record
  * while tracking is on, and sender and receiver must agree on that. */
 int ddcmi_vaf_clear(ddcmi_ctx *ctx);
-/* ANALYSIS vcmWrite, zdensity, KINETICENERGYDISTN and DSF on the device: one read-only pass over the owned beads each.  All read the state that a download
+/* ANALYSIS vcmWrite, zdensity, KINETICENERGYDISTN, DSF and subsetWrite on the device: one read-only pass over the owned beads each.  All read the state that a download
  * returns at this point of the run, change nothing of it (a run with calls and one without are bit for bit the same), need no
  * communication and give identical bits when repeated; a domain that holds no bead gives zeros.
  * vcmWrite_output's sums (vcmWrite.c:95-110) over this rank's beads, internal units: mv[3 c .. 3 c + 2] = sum m v, m[c] = sum m, class c = 0 the
@@ -302,6 +302,34 @@ int ddcmi_kinetic_energy_distn(ddcmi_ctx *ctx, int nspecies, int ndist, const do
  * select without a member, gives zeros and count 0. [sync] */
 #define DDCMI_DSF_MAX_M 256
 int ddcmi_charge_density_modes(ddcmi_ctx *ctx, int nspecies, const int *select, int mmax, double *rho, int64_t *count);
+/* ANALYSIS subsetWrite, format binaryCharmm, on the device (subsetWrite.c:409-522): the owned beads a filter selects as the file's
+ * 24-byte records, in one read-only pass under the rules above.  The filter is rejectParticle's (subsetWrite.c:532-564), in its order
+ * and with its comparisons: a bead is dropped if gid < idmin, gid > idmax, gid % modulus != 0, odd and gid even, r_a > rmax[a] or
+ * r_a < rmin[a], v_a > vmax[a] or v_a < vmin[a] (strict: a bead on a bound is kept, and a NaN coordinate passes), include_species[its
+ * species] == 0 (NULL: every species), or -- with an idlist -- its gid is not among the nid ascending entries (binary search on the
+ * device; idlist NULL and nid 0: no list).  Internal units; positions and velocities are those a download returns (wrapped).  A
+ * record is {gid, pinfo = group_term[group] + species_term[species], (float)((r_a - corner[a]) * cL)}: the difference and the product
+ * in double, rounded once; the two tables are pinfoEncode (pinfo.c:119-126) split by the caller.  nspecies and ngroup are the tables'
+ * lengths and must cover the context's species and groups (a context without groups has the one group 0).
+ * *count: this rank's selected beads, always.  rec NULL: nothing else.  Otherwise the records in the order of
+ * ddcmi_download_particles (a stable compaction) if cap >= *count; with a smaller cap DDCMI_EINVAL, *count set and rec untouched.
+ * The records are packed in a device buffer of the context and copied once: 24 * count bytes cross, not the state.  Over ranks,
+ * concatenate.  Refused: modulus < 1, an idlist that is not ascending, tables shorter than the context's ids, a cL that is not finite
+ * (DDCMI_EINVAL); a box that is not orthorhombic (DDCMI_EUNSUPPORTED). [sync] */
+typedef struct ddcmi_subset_filter
+{
+   uint64_t idmin, idmax;
+   int modulus, odd;
+   double rmin[3], rmax[3], vmin[3], vmax[3];
+   int nspecies, ngroup;
+   const int *include_species;
+   const uint32_t *group_term, *species_term;
+   int64_t nid;
+   const uint64_t *idlist;
+   double corner[3], cL;
+} ddcmi_subset_filter;
+typedef struct ddcmi_subset_record { uint64_t gid; uint32_t pinfo; float r[3]; } ddcmi_subset_record;      /* 24 bytes: the file's record */
+int ddcmi_subset_records(ddcmi_ctx *ctx, const ddcmi_subset_filter *filter, int64_t cap, ddcmi_subset_record *rec, int64_t *count);
 
 /* ---- introspection / measurement ------------------------------------------- */
 /* list statistics of the last build: stats[0]=stored full-list entries,

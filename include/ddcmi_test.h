@@ -70,6 +70,9 @@ int ddcmi_group_kinetic_energy_distn(ddcmi_ctx **ctxs, int n, int nspecies, int 
 /* ddcmi_charge_density_modes for an in-process group: every domain's own result, domain after domain -- rho[r*6*mmax ...], count[r]
  * for domain r */
 int ddcmi_group_charge_density_modes(ddcmi_ctx **ctxs, int n, int nspecies, const int *select, int mmax, double *rho, int64_t *count);
+/* ddcmi_subset_records for an in-process group: count[r] of every domain r; with rec, the domains' records one block behind the
+ * other in rank order, cap the room for all of them (too small: DDCMI_EINVAL, the counts set, rec untouched) */
+int ddcmi_group_subset_records(ddcmi_ctx **ctxs, int n, const ddcmi_subset_filter *filter, int64_t cap, ddcmi_subset_record *rec, int64_t *count);
 /* the lean step (a single domain of FREE beads without bonded terms: one launch per step, the second stage of its energy / virial /
  * kinetic sums formed for all pending steps at once): the sums of the steps of the last such launch, 32 doubles per step --
  * {lj, ele, virial xx yy zz xy xz yz} as the full list counts them (twice), {rk, tion xx yy zz xy xz yz}, 0, the bonded kernels'
