@@ -111,7 +111,9 @@ int ddcmi_set_bonded_gid(ddcmi_ctx *ctx,
 /* POTENTIAL type=RESTRAINT (restraint.c:259-361; restraintGPU.cu): harmonic position restraints on the
  * beads with the listed gids.  fc[3n] = fcx fcy fcz switches, r0[3n] = x0 y0 z0 as fractions of the box,
  * kb[n]; origin 0: the box is centred on the origin (r0*L - L/2).  Energy lands in DDCMI_E_RESTRAINT
- * and in DDCMI_E_TOTAL.  n = 0 removes them. */
+ * and in DDCMI_E_TOTAL.  n = 0 removes them.  fc takes any int (the force scales with fc, the virial with
+ * fc^2).  A bead may carry several restraints: their forces add.  A gid that no bead carries is accepted
+ * and contributes nothing -- no force, energy or virial -- like a restraintMap entry of -1 in the reference. */
 int ddcmi_set_restraints(ddcmi_ctx *ctx, int n, const uint64_t *gid, const int *fc, const double *r0, const double *kb, int origin);
 /* NEIGHBOR deltaR (neighbor.c:49) and DDC updateRate (ddc.c:96).  updateRate = 0: rebuild when
  * neighborCheck (neighbor.c:117-208) finds 2*max displacement >= deltaR (one host round trip per step) */
