@@ -3,50 +3,19 @@ at init, one line per output), snapshot.<loop>/zden.dat, both held against the r
 restart state the driver writes at the same loop; one rank against two; a mixed list against its members alone."""
 import glob
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from ddcmd_amd.analysis import VcmWrite, ZDensity, parse_vcm_output
 from ddcmd_amd.deck import load_deck, units_convert
+from ranks import GOLDEN, copy_deck, run_driver, tree_files
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "ddcmd_amd", "bin", "ddcmi_md")
 NZ = 16
 VCM = "vcm ANALYSIS { type = vcmWrite; outputrate = 10; }\n"
 ZDEN = "zden ANALYSIS { type = zdensity; outputrate = 10; nz = %d; }\n" % NZ
 SIM = "simulate SIMULATE { %sdeltaloop = 20; maxloop = 20; printrate = 5; snapshotrate = 10; checkpointrate = 100000; }\n"
-
-
-def _copy(tmp_path, name):
-    d = tmp_path / name
-    shutil.copytree(os.path.join(ROOT, "tests", "golden", "water_deck"), str(d))
-    return d
-
-
-def _run(cwd, extra, world=1):
-    args = ["-o", "object.data", "-d", "data", "-x", extra]
-    if world == 1:
-        out = subprocess.run([EXE] + args, capture_output=True, text=True, timeout=600, cwd=str(cwd))
-        assert out.returncode == 0, out.stdout + out.stderr
-        return out
-    env = dict(os.environ, WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", DDCMI_TRANSPORT="host", DDCMI_SINGLE_DEVICE="1",
-               DDCMI_RDZV_FILE=os.path.join(str(cwd), "rdzv_port"))
-    procs = [subprocess.Popen([EXE] + args, cwd=str(cwd), env=dict(env, RANK=str(r), LOCAL_RANK=str(r)), stdout=subprocess.PIPE,
-                              stderr=subprocess.PIPE, text=True) for r in range(world)]
-    outs = []
-    for p in procs:
-        try:
-            outs.append(p.communicate(timeout=600))
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-        assert p.returncode == 0, outs[-1]
-    return outs
 
 
 def _restated_vcm(s):
@@ -63,10 +32,10 @@ def _restated_vcm(s):
 
 
 def test_driver_writes_vcm_data_and_zden_files(tmp_path):
-    d = _copy(tmp_path, "with")
-    out = _run(d, SIM % "analysis = vcm zden; " + VCM + ZDEN)
-    d0 = _copy(tmp_path, "without")
-    _run(d0, SIM % "")
+    d = copy_deck(tmp_path, "water_deck", "with")
+    (out,) = run_driver(d, SIM % "analysis = vcm zden; " + VCM + ZDEN)
+    d0 = copy_deck(tmp_path, "water_deck", "without")
+    run_driver(d0, SIM % "")
     assert open(str(d / "data"), "rb").read() == open(str(d0 / "data"), "rb").read()      # the analyses change nothing of the run
     assert not [l for l in out.stderr.splitlines() if "not supported" in l]
     txt = open(str(d / "vcm.data")).read()
@@ -105,10 +74,10 @@ def test_driver_writes_vcm_data_and_zden_files(tmp_path):
 
 
 def test_driver_two_ranks_write_the_same_files(tmp_path):
-    d1 = _copy(tmp_path, "one")
-    _run(d1, SIM % "analysis = vcm zden; " + VCM + ZDEN)
-    d2 = _copy(tmp_path, "two")
-    outs = _run(d2, SIM % "analysis = vcm zden; " + VCM + ZDEN, world=2)
+    d1 = copy_deck(tmp_path, "water_deck", "one")
+    run_driver(d1, SIM % "analysis = vcm zden; " + VCM + ZDEN)
+    d2 = copy_deck(tmp_path, "water_deck", "two")
+    outs = run_driver(d2, SIM % "analysis = vcm zden; " + VCM + ZDEN, world=2)
     assert not [l for o in outs for l in o[1].splitlines() if "not supported" in l]
     for loop in (10, 20):
         a = open(str(d1 / ("snapshot.%012d" % loop) / "zden.dat"), "rb").read()
@@ -117,28 +86,24 @@ def test_driver_two_ranks_write_the_same_files(tmp_path):
     assert open(str(d1 / "vcm.data"), "rb").read() == open(str(d2 / "vcm.data"), "rb").read()
 
 
-def _files(d):
-    return sorted(os.path.relpath(os.path.join(p, f), str(d)) for p, _, fs in os.walk(str(d)) for f in fs)
-
-
 def test_driver_mixed_list_gives_every_file_each_analysis_gives_alone(tmp_path):
     sim = "simulate SIMULATE { %sdeltaloop = 40; maxloop = 40; printrate = 5; snapshotrate = 100000; checkpointrate = 100000; }\n"
     vaf = "vaf ANALYSIS { type = VELOCITYAUTOCORRELATION; eval_rate = 5; length = 4; outputrate = 20; }\n"
     rdf = "rdf ANALYSIS { type = PAIRCORRELATION; eval_rate = 10; outputrate = 20; delta_r = 0.1 Angstrom; length = 100; }\n"
     objs = {"vaf": vaf, "vcm": VCM, "rdf": rdf, "zden": ZDEN}
-    mixed = _copy(tmp_path, "mixed")
-    out = _run(mixed, sim % "analysis = vaf vcm rdf zden; " + "".join(objs.values()))
+    mixed = copy_deck(tmp_path, "water_deck", "mixed")
+    (out,) = run_driver(mixed, sim % "analysis = vaf vcm rdf zden; " + "".join(objs.values()))
     assert not [l for l in out.stderr.splitlines() if "not supported" in l]
-    golden = set(_files(os.path.join(ROOT, "tests", "golden", "water_deck")))
+    golden = set(tree_files(os.path.join(GOLDEN, "water_deck")))
     seen = set()
     for name, obj in objs.items():
-        d = _copy(tmp_path, name)
-        _run(d, sim % ("analysis = %s; " % name) + obj)
-        written = sorted(set(_files(d)) - golden - {"data"})
+        d = copy_deck(tmp_path, "water_deck", name)
+        run_driver(d, sim % ("analysis = %s; " % name) + obj)
+        written = sorted(set(tree_files(d)) - golden - {"data"})
         assert written, name
         for f in written:
             assert open(str(d / f), "rb").read() == open(str(mixed / f), "rb").read(), f
         assert open(str(d / "data"), "rb").read() == open(str(mixed / "data"), "rb").read()
         seen |= set(written)
-    assert seen == set(_files(mixed)) - golden - {"data"}      # and the mixed run writes nothing else
+    assert seen == set(tree_files(mixed)) - golden - {"data"}      # and the mixed run writes nothing else
     assert "vcm.data" in seen and "snapshot.%012d/zden.dat" % 40 in seen and "snapshot.%012d/vaf.dat" % 20 in seen

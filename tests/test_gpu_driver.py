@@ -8,11 +8,10 @@ import pytest
 
 import pyoracle
 from ddcmd_amd.deck import load_deck, units_convert
+from ranks import EXE, ROOT, driver_ranks
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DECK = os.path.join(ROOT, "tests", "golden", "lipid_deck", "object.data")
-EXE = os.path.join(ROOT, "ddcmd_amd", "bin", "ddcmi_md")
 
 
 def test_ddcmi_md_data_file(tmp_path):
@@ -393,27 +392,6 @@ def test_ddcmi_md_host_integrator_matches_device_integrator(tmp_path):
 
 
 # ---- more than one rank: the driver under a launcher that only sets RANK / WORLD_SIZE / LOCAL_RANK ----
-def _run_ranks(world, args, cwd, extra_env=None, timeout=600):
-    """start `world` ddcmi_md processes like a launcher does (all on the one GPU of a test box: host transport)"""
-    env = dict(os.environ, WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", DDCMI_TRANSPORT="host", DDCMI_SINGLE_DEVICE="1",
-               DDCMI_RDZV_FILE=os.path.join(cwd, "rdzv_port"))
-    env.update(extra_env or {})
-    procs = []
-    for r in range(world):
-        e = dict(env, RANK=str(r), LOCAL_RANK=str(r))
-        procs.append(subprocess.Popen([EXE] + args, cwd=cwd, env=e, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
-    outs = []
-    for p in procs:
-        try:
-            o, er = p.communicate(timeout=timeout)
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-        outs.append((p.returncode, o, er))
-    return outs
-
-
 def _rows(path):
     lines = [l for l in open(path).read().splitlines() if l.strip() and not l.startswith("#")]
     return np.array([[float(x) for x in l.split()] for l in lines])
@@ -429,7 +407,7 @@ def test_ddcmi_md_on_several_ranks_matches_one_rank(tmp_path, world):
     out = subprocess.run([EXE, "-o", DECK, "-d", "data", "-x", x], capture_output=True, text=True, timeout=300, cwd=str(d1))
     assert out.returncode == 0, out.stdout + out.stderr
     dn = tmp_path / "many"; dn.mkdir()
-    outs = _run_ranks(world, ["-o", DECK, "-d", "data", "-x", x], str(dn))
+    outs = driver_ranks(world, ["-o", DECK, "-d", "data", "-x", x], str(dn))
     for rc, o, er in outs:
         assert rc == 0, o + er
     assert "%d ranks on a" % world in outs[0][1] and all("ranks on a" not in o for _, o, _ in outs[1:])      # rank 0 owns stdout
@@ -458,7 +436,7 @@ def test_ddcmi_md_langevin_lcg64_on_two_ranks_matches_one_rank(tmp_path):
     out = subprocess.run([EXE, "-o", DECK, "-d", "data", "-x", x], capture_output=True, text=True, timeout=300, cwd=str(d1))
     assert out.returncode == 0, out.stdout + out.stderr
     dn = tmp_path / "two"; dn.mkdir()
-    outs = _run_ranks(2, ["-o", DECK, "-d", "data", "-x", x], str(dn))
+    outs = driver_ranks(2, ["-o", DECK, "-d", "data", "-x", x], str(dn))
     for rc, o, er in outs:
         assert rc == 0, o + er
     assert "they migrate with their beads" in outs[0][1]
@@ -490,7 +468,7 @@ def test_ddcmi_md_nglfconstraint_on_two_ranks(tmp_path):
     out = subprocess.run([EXE] + args, capture_output=True, text=True, timeout=300, cwd=str(d1))
     assert out.returncode == 0, out.stdout[-1000:] + out.stderr[-2000:]
     dn = tmp_path / "two"; dn.mkdir()
-    for rc, o, er in _run_ranks(2, args, str(dn)):
+    for rc, o, er in driver_ranks(2, args, str(dn)):
         assert rc == 0, o[-1000:] + er[-2000:]
     a, b = _rows(str(d1 / "data")), _rows(str(dn / "data"))
     assert a.shape == b.shape and a.shape[0] >= 3

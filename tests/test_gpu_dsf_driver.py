@@ -3,56 +3,25 @@ directory -- one header at init, one row per evaluation, the startup one include
 buffered, at the end of the run -- held against analysis.DynamicStructureFactor fed by a Python run of the same deck
 (Martini.charge_density_modes at the loops of the evaluations); one rank against two."""
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from ddcmd_amd.analysis import DynamicStructureFactor, parse_dsf_output
 from ddcmd_amd.deck import load_deck
+from ranks import copy_deck, run_driver
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "ddcmd_amd", "bin", "ddcmi_md")
 DSF = ("po4 ANALYSIS { type = DSF; m = 1 2 4; species = DPPCxPO4; eval_rate = 10; outputrate = 20; }\n"
        "all ANALYSIS { type = DynamicStructureFactor; m = 3 0 1; eval_rate = 10; outputrate = 20; filename = everything.data; }\n")
 SIM = "simulate SIMULATE { analysis = po4 all; deltaloop = 50; maxloop = 50; printrate = 10; snapshotrate = 100000; checkpointrate = 100000; }\n"
 LOOPS = [0, 10, 20, 30, 40, 50]      # 20 and 40 write three and two rows; the row of loop 50 is written when the run ends
 
 
-def _copy(tmp_path, name):
-    d = tmp_path / name
-    shutil.copytree(os.path.join(ROOT, "tests", "golden", "lipid_deck"), str(d))
-    return d
-
-
-def _run(cwd, extra, world=1):
-    args = ["-o", "object.data", "-d", "data", "-x", extra]
-    if world == 1:
-        out = subprocess.run([EXE] + args, capture_output=True, text=True, timeout=600, cwd=str(cwd))
-        assert out.returncode == 0, out.stdout + out.stderr
-        return [(out.stdout, out.stderr)]
-    env = dict(os.environ, WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", DDCMI_TRANSPORT="host", DDCMI_SINGLE_DEVICE="1",
-               DDCMI_RDZV_FILE=os.path.join(str(cwd), "rdzv_port"))
-    procs = [subprocess.Popen([EXE] + args, cwd=str(cwd), env=dict(env, RANK=str(r), LOCAL_RANK=str(r)), stdout=subprocess.PIPE,
-                              stderr=subprocess.PIPE, text=True) for r in range(world)]
-    outs = []
-    for p in procs:
-        try:
-            outs.append(p.communicate(timeout=600))
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-        assert p.returncode == 0, outs[-1]
-    return outs
-
-
 @pytest.fixture(scope="module")
 def one_rank(tmp_path_factory):
-    d = _copy(tmp_path_factory.mktemp("dsf"), "one")
-    return d, _run(d, SIM + DSF)
+    d = copy_deck(tmp_path_factory.mktemp("dsf"), "lipid_deck", "one")
+    return d, run_driver(d, SIM + DSF)
 
 
 def _python_files(deck):
@@ -117,8 +86,8 @@ def test_driver_writes_the_rows_of_a_python_run(one_rank):
 
 def test_driver_two_ranks_write_the_same_rows(one_rank, tmp_path):
     d1, _ = one_rank
-    d2 = _copy(tmp_path, "two")
-    outs = _run(d2, SIM + DSF, world=2)
+    d2 = copy_deck(tmp_path, "lipid_deck", "two")
+    outs = run_driver(d2, SIM + DSF, world=2)
     assert not [l for o in outs for l in o[1].splitlines() if "not supported" in l]
     for f in ("rho_k_DPPCxPO4.data", "everything.data"):
         a, b = open(str(d1 / f)).read(), open(str(d2 / f)).read()

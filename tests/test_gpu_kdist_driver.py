@@ -3,18 +3,15 @@ at init, one line per output with loop and time repeated per group) and snapshot
 restatement of kineticEnergyDistn.c applied to the restart states the driver writes at the loops of the evaluations; several
 evaluations per output; one rank against two; a mixed list against the same list without the new type."""
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from ddcmd_amd.analysis import KineticEnergyDistn, parse_kdist_output, parse_kinetic_output
 from ddcmd_amd.deck import load_deck
+from ranks import GOLDEN, copy_deck, run_driver, tree_files
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "ddcmd_amd", "bin", "ddcmi_md")
 KD = ("kd ANALYSIS { type = KINETICENERGYDISTN; eval_rate = 5; outputrate = 10; distGroups = wDist fDist none; }\n"
       "wDist BIN { species = WxW; emin = 0 eV; emax = 0.2 eV; nBins = 20; }\n"      # the Langevin groups hold 310 K: kT = 0.0267 eV, 0.2 eV = 7.5 kT
       "fDist BIN { species = WFxWF; emin = 0.01 eV; emax = 0.1 eV; nBins = 8; }\n"      # 0.37 kT to 3.7 kT: about 15 % of the beads below, 6 % above
@@ -22,38 +19,10 @@ KD = ("kd ANALYSIS { type = KINETICENERGYDISTN; eval_rate = 5; outputrate = 10; 
 SIM = "simulate SIMULATE { %sdeltaloop = 20; maxloop = 20; printrate = 5; snapshotrate = 5; checkpointrate = 100000; }\n"
 
 
-def _copy(tmp_path, name):
-    d = tmp_path / name
-    shutil.copytree(os.path.join(ROOT, "tests", "golden", "water_deck"), str(d))
-    return d
-
-
-def _run(cwd, extra, world=1):
-    args = ["-o", "object.data", "-d", "data", "-x", extra]
-    if world == 1:
-        out = subprocess.run([EXE] + args, capture_output=True, text=True, timeout=600, cwd=str(cwd))
-        assert out.returncode == 0, out.stdout + out.stderr
-        return [(out.stdout, out.stderr)]
-    env = dict(os.environ, WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", DDCMI_TRANSPORT="host", DDCMI_SINGLE_DEVICE="1",
-               DDCMI_RDZV_FILE=os.path.join(str(cwd), "rdzv_port"))
-    procs = [subprocess.Popen([EXE] + args, cwd=str(cwd), env=dict(env, RANK=str(r), LOCAL_RANK=str(r)), stdout=subprocess.PIPE,
-                              stderr=subprocess.PIPE, text=True) for r in range(world)]
-    outs = []
-    for p in procs:
-        try:
-            outs.append(p.communicate(timeout=600))
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-        assert p.returncode == 0, outs[-1]
-    return outs
-
-
 @pytest.fixture(scope="module")
 def one_rank(tmp_path_factory):
-    d = _copy(tmp_path_factory.mktemp("kdist"), "one")
-    return d, _run(d, SIM % "analysis = kd; " + KD)
+    d = copy_deck(tmp_path_factory.mktemp("kdist"), "water_deck", "one")
+    return d, run_driver(d, SIM % "analysis = kd; " + KD)
 
 
 def _restated(d, an, loops):
@@ -85,8 +54,8 @@ def _restated(d, an, loops):
 def test_driver_writes_kinetic_data_and_the_dist_files(one_rank, tmp_path):
     d, outs = one_rank
     assert not [l for l in outs[0][1].splitlines() if "not supported" in l]
-    d0 = _copy(tmp_path, "without")
-    _run(d0, SIM % "")
+    d0 = copy_deck(tmp_path, "water_deck", "without")
+    run_driver(d0, SIM % "")
     assert open(str(d / "data"), "rb").read() == open(str(d0 / "data"), "rb").read()      # the analysis changes nothing of the run
     s0 = load_deck(str(d / "object.data"), extra_objects=SIM % "analysis = kd; " + KD)
     (a,) = s0.analysis
@@ -127,8 +96,8 @@ def test_driver_writes_kinetic_data_and_the_dist_files(one_rank, tmp_path):
 
 def test_driver_two_ranks_write_the_same_files(one_rank, tmp_path):
     d1, _ = one_rank
-    d2 = _copy(tmp_path, "two")
-    outs = _run(d2, SIM % "analysis = kd; " + KD, world=2)
+    d2 = copy_deck(tmp_path, "water_deck", "two")
+    outs = run_driver(d2, SIM % "analysis = kd; " + KD, world=2)
     assert not [l for o in outs for l in o[1].splitlines() if "not supported" in l]
     a, b = open(str(d1 / "kinetic.data")).read(), open(str(d2 / "kinetic.data")).read()
     assert a.count("#") == 1 and b.count("#") == 1      # rank 0 alone opens the file
@@ -144,26 +113,22 @@ def test_driver_two_ranks_write_the_same_files(one_rank, tmp_path):
             assert open(str(d1 / f), "rb").read() == open(str(d2 / f), "rb").read(), f      # counts and their quotients only
 
 
-def _files(d):
-    return sorted(os.path.relpath(os.path.join(p, f), str(d)) for p, _, fs in os.walk(str(d)) for f in fs)
-
-
 def test_driver_mixed_list_leaves_the_other_types_files_as_they_are(tmp_path):
     sim = "simulate SIMULATE { %sdeltaloop = 20; maxloop = 20; printrate = 5; snapshotrate = 100000; checkpointrate = 100000; }\n"
     others = ("vaf ANALYSIS { type = VELOCITYAUTOCORRELATION; eval_rate = 5; length = 2; outputrate = 10; }\n"
               "vcm ANALYSIS { type = vcmWrite; outputrate = 10; }\n"
               "rdf ANALYSIS { type = PAIRCORRELATION; eval_rate = 10; outputrate = 20; delta_r = 0.1 Angstrom; length = 100; }\n"
               "zden ANALYSIS { type = zdensity; outputrate = 10; nz = 16; }\n")
-    mixed = _copy(tmp_path, "mixed")
-    outs = _run(mixed, sim % "analysis = vaf vcm kd rdf zden; " + others + KD)
+    mixed = copy_deck(tmp_path, "water_deck", "mixed")
+    outs = run_driver(mixed, sim % "analysis = vaf vcm kd rdf zden; " + others + KD)
     assert not [l for l in outs[0][1].splitlines() if "not supported" in l]
-    four = _copy(tmp_path, "four")
-    _run(four, sim % "analysis = vaf vcm rdf zden; " + others)
-    golden = set(_files(os.path.join(ROOT, "tests", "golden", "water_deck")))
-    theirs = sorted(set(_files(four)) - golden)
+    four = copy_deck(tmp_path, "water_deck", "four")
+    run_driver(four, sim % "analysis = vaf vcm rdf zden; " + others)
+    golden = set(tree_files(os.path.join(GOLDEN, "water_deck")))
+    theirs = sorted(set(tree_files(four)) - golden)
     assert "vcm.data" in theirs and "snapshot.%012d/zden.dat" % 20 in theirs and "snapshot.%012d/vaf.dat" % 10 in theirs \
         and "snapshot.%012d/paircorrelation.dat" % 20 in theirs and "data" in theirs
     for f in theirs:
         assert open(str(four / f), "rb").read() == open(str(mixed / f), "rb").read(), f      # byte for byte
-    new = sorted(set(_files(mixed)) - golden - set(theirs))
+    new = sorted(set(tree_files(mixed)) - golden - set(theirs))
     assert new == sorted(["kinetic.data"] + ["snapshot.%012d/%s_kDist.data" % (lp, n) for lp in (10, 20) for n in ("wDist", "fDist", "none")])

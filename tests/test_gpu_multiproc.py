@@ -20,27 +20,22 @@ import pyoracle
 import ddcmd_amd
 from conftest import rel_force_err
 from ddcmd_amd.deck import units_convert
+from ranks import ROOT, rank_env, run_ranks
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KINDS = ("lj", "ele", "bond", "angle", "tors", "impr", "total")
 
 
-def _run_ranks(workload, grid, nsteps, block):
+def _worker_ranks(workload, grid, d, nsteps, block, extra_env=None, timeout=600, check=False):
     world = grid[0] * grid[1] * grid[2]
+    cmd = [sys.executable, os.path.join(ROOT, "tests", "mp_worker.py"), workload, "%dx%dx%d" % grid, d, str(nsteps), str(block)]
+    return run_ranks([cmd] * world, [rank_env(r, world, d, extra_env) for r in range(world)], timeout=timeout, check=check)
+
+
+def _run_ranks(workload, grid, nsteps, block):
     with tempfile.TemporaryDirectory() as d:
-        procs = []
-        for rank in range(world):
-            env = dict(os.environ)
-            env.update({"RANK": str(rank), "WORLD_SIZE": str(world), "LOCAL_RANK": str(rank), "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "1",
-                        "DDCMI_RDZV_FILE": os.path.join(d, "port"), "DDCMI_TRANSPORT": "host"})
-            env.pop("DDCMI_RCCL_LOOPBACK", None)
-            procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "mp_worker.py"), workload, "%dx%dx%d" % grid, d, str(nsteps), str(block)],
-                                          env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
-        for p in procs:
-            o, e = p.communicate(timeout=600)
-            assert p.returncode == 0, (o[-1500:], e[-3000:])
-        return [dict(np.load(os.path.join(d, "rank%d.npz" % r))) for r in range(world)]
+        _worker_ranks(workload, grid, d, nsteps, block, check=True)
+        return [dict(np.load(os.path.join(d, "rank%d.npz" % r))) for r in range(grid[0] * grid[1] * grid[2])]
 
 
 def test_a_failing_rank_ends_the_rebuild_on_every_rank():
@@ -48,21 +43,12 @@ def test_a_failing_rank_ends_the_rebuild_on_every_rank():
     list build) used to leave the other ranks inside the next exchange until the transport's 300 s timeout.  Every rank
     must return an error from the same rebuild, at once, and say whose error it is."""
     import time
-    world = 2
     with tempfile.TemporaryDirectory() as d:
-        procs = []
         t0 = time.time()
-        for rank in range(world):
-            env = dict(os.environ)
-            env.update({"RANK": str(rank), "WORLD_SIZE": str(world), "LOCAL_RANK": str(rank), "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "1",
-                        "DDCMI_RDZV_FILE": os.path.join(d, "port"), "DDCMI_TRANSPORT": "host"})
-            env.pop("DDCMI_RCCL_LOOPBACK", None)
-            procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "mp_worker.py"), "water_fault", "2x1x1", d, "0", "1"],
-                                          env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
-        outs = [p.communicate(timeout=120) for p in procs]
+        res = _worker_ranks("water_fault", (2, 1, 1), d, 0, 1, timeout=120)
         assert time.time() - t0 < 100, "the ranks waited for each other"
-        assert [p.returncode for p in procs] == [3, 3], [(p.returncode, o[1][-800:]) for p, o in zip(procs, outs)]
-        errs = [o[1] for o in outs]
+        assert [r.returncode for r in res] == [3, 3], [(r.returncode, r.stderr[-800:]) for r in res]
+        errs = [r.stderr for r in res]
         # the rank that holds the bead (migration may have handed it to the neighbour first) says what is wrong, its peer is told
         # whose error it is -- or both learn of a bead "further than one domain" away in the same count round
         own = [("non-finite" in e) for e in errs]
@@ -76,19 +62,9 @@ def test_a_failing_rank_ends_the_rebuild_on_every_rank():
 
 
 def _preflight_ranks(grid, extra_env, timeout=120):
-    world = grid[0] * grid[1] * grid[2]
     with tempfile.TemporaryDirectory() as d:
-        procs = []
-        for rank in range(world):
-            env = dict(os.environ)
-            env.update({"RANK": str(rank), "WORLD_SIZE": str(world), "LOCAL_RANK": str(rank), "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "1",
-                        "DDCMI_RDZV_FILE": os.path.join(d, "port"), "DDCMI_TRANSPORT": "host"})
-            env.pop("DDCMI_RCCL_LOOPBACK", None)
-            env.update(extra_env)
-            procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "mp_worker.py"), "water_preflight", "%dx%dx%d" % grid, d, "0", "1"],
-                                          env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
-        outs = [p.communicate(timeout=timeout) for p in procs]
-        return [p.returncode for p in procs], [o[1] for o in outs]
+        res = _worker_ranks("water_preflight", grid, d, 0, 1, extra_env, timeout)
+    return [r.returncode for r in res], [r.stderr for r in res]
 
 
 @pytest.mark.parametrize("grid", [(2, 1, 1), (2, 2, 2)])

@@ -3,25 +3,16 @@ startup sample, eval / output after the checkpoint and before the snapshot, snap
 paircorrelation_output writes it -- checked against a numpy recomputation from the atoms files the same run wrote."""
 import glob
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from ddcmd_amd.analysis import PairCorrelation, parse_output
 from ddcmd_amd.deck import load_deck, units_convert
+from ranks import copy_deck, run_driver
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "ddcmd_amd", "bin", "ddcmi_md")
 RDF = "rdf ANALYSIS { type = PAIRCORRELATION; eval_rate = 10; outputrate = 50; delta_r = 0.1 Angstrom; length = 100; }\n"
-
-
-def _copy(tmp_path, which, name):
-    d = tmp_path / name
-    shutil.copytree(os.path.join(ROOT, "tests", "golden", which), str(d))
-    return d
 
 
 def _np_counts(s, rmin, dr, nbins):
@@ -49,35 +40,13 @@ def _np_counts(s, rmin, dr, nbins):
     return counts.reshape(-1, nbins), np.bincount(sp, minlength=ns)
 
 
-def _run(cwd, extra, world=1):
-    args = ["-o", "object.data", "-d", "data", "-x", extra]
-    if world == 1:
-        out = subprocess.run([EXE] + args, capture_output=True, text=True, timeout=600, cwd=str(cwd))
-        assert out.returncode == 0, out.stdout + out.stderr
-        return out
-    env = dict(os.environ, WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", DDCMI_TRANSPORT="host", DDCMI_SINGLE_DEVICE="1",
-               DDCMI_RDZV_FILE=os.path.join(str(cwd), "rdzv_port"))
-    procs = [subprocess.Popen([EXE] + args, cwd=str(cwd), env=dict(env, RANK=str(r), LOCAL_RANK=str(r)), stdout=subprocess.PIPE,
-                              stderr=subprocess.PIPE, text=True) for r in range(world)]
-    outs = []
-    for p in procs:
-        try:
-            outs.append(p.communicate(timeout=600))
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-        assert p.returncode == 0, outs[-1]
-    return outs
-
-
 @pytest.mark.parametrize("which", ["water_deck", "lipid_deck"])
 def test_driver_writes_paircorrelation_files(tmp_path, which):
     sim = "simulate SIMULATE { analysis = rdf; deltaloop = 100; maxloop = 100; printrate = 10; snapshotrate = 10; checkpointrate = 100000; }\n"
-    d = _copy(tmp_path, which, "with")
-    _run(d, sim + RDF)
-    d0 = _copy(tmp_path, which, "without")
-    _run(d0, sim.replace("analysis = rdf; ", ""))
+    d = copy_deck(tmp_path, which, "with")
+    run_driver(d, sim + RDF)
+    d0 = copy_deck(tmp_path, which, "without")
+    run_driver(d0, sim.replace("analysis = rdf; ", ""))
     assert open(str(d / "data"), "rb").read() == open(str(d0 / "data"), "rb").read()      # the analysis changes nothing of the run
     s0 = load_deck(str(d / "object.data"))
     dr = units_convert(0.1, "Angstrom", None)
@@ -112,10 +81,10 @@ def test_driver_writes_paircorrelation_files(tmp_path, which):
 
 def test_driver_two_ranks_write_the_same_files(tmp_path):
     sim = "simulate SIMULATE { analysis = rdf; deltaloop = 50; maxloop = 50; printrate = 10; snapshotrate = 10; checkpointrate = 100000; }\n"
-    d1 = _copy(tmp_path, "water_deck", "one")
-    _run(d1, sim + RDF)
-    d2 = _copy(tmp_path, "water_deck", "two")
-    _run(d2, sim + RDF, world=2)
+    d1 = copy_deck(tmp_path, "water_deck", "one")
+    run_driver(d1, sim + RDF)
+    d2 = copy_deck(tmp_path, "water_deck", "two")
+    run_driver(d2, sim + RDF, world=2)
     (a,) = glob.glob(str(d1 / "snapshot.*50" / "paircorrelation.dat"))
     (b,) = glob.glob(str(d2 / "snapshot.*50" / "paircorrelation.dat"))
     assert open(a).read() == open(b).read()
@@ -124,10 +93,10 @@ def test_driver_two_ranks_write_the_same_files(tmp_path):
 def test_unsupported_analysis_is_named_once_and_changes_nothing(tmp_path):
     sim = "simulate SIMULATE { deltaloop = 20; maxloop = 20; printrate = 10; snapshotrate = 100000; checkpointrate = 100000; %s}\n"
     w = "writeCharmm ANALYSIS { type = subsetWrite; outputrate = 10; }\n"
-    d = _copy(tmp_path, "water_deck", "with")
-    out = _run(d, sim % "analysis = writeCharmm; " + w)
-    d0 = _copy(tmp_path, "water_deck", "without")
-    _run(d0, sim % "")
+    d = copy_deck(tmp_path, "water_deck", "with")
+    (out,) = run_driver(d, sim % "analysis = writeCharmm; " + w)
+    d0 = copy_deck(tmp_path, "water_deck", "without")
+    run_driver(d0, sim % "")
     lines = [l for l in out.stderr.splitlines() if "writeCharmm" in l]
     assert len(lines) == 1 and "subsetWrite" in lines[0] and "not supported" in lines[0]
     assert open(str(d / "data"), "rb").read() == open(str(d0 / "data"), "rb").read()

@@ -18,6 +18,7 @@ import pytest
 import pyoracle
 import approach_systems as A
 from approach_worker import run_one_call
+from ranks import rank_env, run_ranks
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-6          # energies along a trajectory (tests/test_gpu_parity.py)
@@ -290,31 +291,22 @@ def test_pairs_across_the_faces_of_a_loopback_rank(monkeypatch):
     run_decomposed(s, a, b, lambda m: by_gid(m.download_particles()), "loopback")
 
 
-def start_ranks(d, pattern, extra_env):
-    """the two ranks of one_sided() as fresh processes over the host transport (as tests/test_gpu_multiproc.py starts its ranks)"""
-    procs = []
+def rank_launch(d, pattern, extra_env):
+    """commands and environments of the two ranks of one_sided() as fresh processes over the host transport"""
+    envs = []
     for rank in range(2):
-        env = dict(os.environ)
-        env.update({"RANK": str(rank), "WORLD_SIZE": "2", "LOCAL_RANK": str(rank), "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "1",
-                    "DDCMI_RDZV_FILE": os.path.join(d, "port"), "DDCMI_TRANSPORT": "host"})
-        for k in ("DDCMI_RCCL_LOOPBACK", "DDCMI_NO_SHELL_SKIP", "DDCMI_HALO_OVERLAP", "DDCMI_NO_DIRECT_HALO"):
+        env = rank_env(rank, 2, d)
+        for k in ("DDCMI_NO_SHELL_SKIP", "DDCMI_HALO_OVERLAP", "DDCMI_NO_DIRECT_HALO"):
             env.pop(k, None)
         env.update(extra_env)
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "approach_worker.py"), "rank", d, ",".join(str(k) for k in pattern)],
-                                      cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
-    return procs
+        envs.append(env)
+    return [[sys.executable, os.path.join(ROOT, "tests", "approach_worker.py"), "rank", d, ",".join(str(k) for k in pattern)]] * 2, envs
 
 
-def collect_ranks(d, procs, ncalls):
-    """the merged states by gid, one per download; any rank that fails or outlives the time limit ends the test with every process gone"""
-    try:
-        outs = [p.communicate(timeout=120) for p in procs]
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-    for p, (o, e) in zip(procs, outs):
-        assert p.returncode == 0 and "approach_worker ok" in o, (p.returncode, o[-1500:], e[-3000:])
+def collect_ranks(d, res, ncalls):
+    """the merged states by gid, one per download; any rank that failed ends the test"""
+    for r in res:
+        assert r.returncode == 0 and "approach_worker ok" in r.stdout, (r.returncode, r.stdout[-1500:], r.stderr[-3000:])
     recs = [dict(np.load(os.path.join(d, "rank%d.npz" % r))) for r in range(2)]
     assert all(str(rec["transport"][0]) == "host" for rec in recs)
     states = []
@@ -339,12 +331,9 @@ def test_movers_on_one_rank_only(calls, tmp_path):
     pattern = pattern_of(calls, int(s.updateRate) + 5)
     da, db = str(tmp_path / "a"), str(tmp_path / "b")
     os.mkdir(da); os.mkdir(db)
-    pa = start_ranks(da, pattern, {})
-    pb = start_ranks(db, pattern, {"DDCMI_NO_SHELL_SKIP": "1"})
-    try:
-        sa = collect_ranks(da, pa, len(pattern))
-    finally:
-        sb = collect_ranks(db, pb, len(pattern))
+    (ca, ea), (cb, eb) = rank_launch(da, pattern, {}), rank_launch(db, pattern, {"DDCMI_NO_SHELL_SKIP": "1"})
+    res = run_ranks(ca + cb, ea + eb, cwd=ROOT, timeout=120)      # both pairs side by side
+    sa, sb = collect_ranks(da, res[:2], len(pattern)), collect_ranks(db, res[2:], len(pattern))
     assert sa[0]["nloc"] == [18, 18] and np.array_equal(sa[0]["gid"], np.asarray(s.gid))
     n = 0
     for c, (x, y) in enumerate(zip(sa, sb)):

@@ -7,48 +7,17 @@ significant digits, so the float of (r_restart - corner) * cL is the record's or
 length."""
 import glob
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from ddcmd_amd.analysis import read_subset
 from ddcmd_amd.deck import load_deck
+from ranks import copy_deck, run_driver
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "ddcmd_amd", "bin", "ddcmi_md")
 SIM = "simulate SIMULATE { %sdeltaloop = 20; maxloop = 20; printrate = 5; snapshotrate = 10; checkpointrate = 100000; }\n"
 ALL = "w ANALYSIS { type = subsetWrite; format = binaryCharmm; outputrate = 10; }\n"
-
-
-def _copy(tmp_path, which, name):
-    d = tmp_path / name
-    shutil.copytree(os.path.join(ROOT, "tests", "golden", which), str(d))
-    return d
-
-
-def _run(cwd, extra, world=1):
-    args = ["-o", "object.data", "-d", "data"] + (["-x", extra] if extra else [])
-    if world == 1:
-        out = subprocess.run([EXE] + args, capture_output=True, text=True, timeout=600, cwd=str(cwd))
-        assert out.returncode == 0, out.stdout + out.stderr
-        return [(out.stdout, out.stderr)]
-    env = dict(os.environ, WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", DDCMI_TRANSPORT="host", DDCMI_SINGLE_DEVICE="1",
-               DDCMI_RDZV_FILE=os.path.join(str(cwd), "rdzv_port"))
-    procs = [subprocess.Popen([EXE] + args, cwd=str(cwd), env=dict(env, RANK=str(r), LOCAL_RANK=str(r)), stdout=subprocess.PIPE,
-                              stderr=subprocess.PIPE, text=True) for r in range(world)]
-    outs = []
-    for p in procs:
-        try:
-            outs.append(p.communicate(timeout=600))
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-        assert p.returncode == 0, outs[-1]
-    return outs
 
 
 def _frames(d, name="subset"):
@@ -72,8 +41,8 @@ def _restart_atoms(path):
 @pytest.fixture(scope="module")
 def runs(tmp_path_factory):
     t = tmp_path_factory.mktemp("subset")
-    plain, with_an = _copy(t, "water_deck", "plain"), _copy(t, "water_deck", "frames")
-    return plain, _run(plain, SIM % ""), with_an, _run(with_an, SIM % "analysis = w; " + ALL)
+    plain, with_an = copy_deck(t, "water_deck", "plain"), copy_deck(t, "water_deck", "frames")
+    return plain, run_driver(plain, SIM % ""), with_an, run_driver(with_an, SIM % "analysis = w; " + ALL)
 
 
 def test_frames_at_the_output_loops_hold_the_restart_snapshots_positions(runs):
@@ -116,10 +85,10 @@ def test_the_run_is_bit_identical_with_and_without_the_analysis(runs):
 
 
 def test_a_filter_selects_its_count(runs, tmp_path):
-    d = _copy(tmp_path, "water_deck", "filtered")
+    d = copy_deck(tmp_path, "water_deck", "filtered")
     s = load_deck(str(d / "object.data"))
     name = s.species_name[-1]
-    outs = _run(d, SIM % "analysis = w; " + "w ANALYSIS { type = subset_write; format = binaryCharmm; outputrate = 10; modulus = 3; species = %s; filename = third; }\n" % name)
+    outs = run_driver(d, SIM % "analysis = w; " + "w ANALYSIS { type = subset_write; format = binaryCharmm; outputrate = 10; modulus = 3; species = %s; filename = third; }\n" % name)
     assert not [l for l in outs[0][1].splitlines() if "not supported" in l]
     want = np.sort(s.gid[(s.gid % np.uint64(3) == 0) & (s.species == s.nspecies - 1)])
     frames = _frames(d, "third")
@@ -132,8 +101,8 @@ def test_a_filter_selects_its_count(runs, tmp_path):
 
 def test_two_ranks_write_the_record_set_of_one(runs, tmp_path):
     _, _, d1, _ = runs
-    d2 = _copy(tmp_path, "water_deck", "two")
-    outs = _run(d2, SIM % "analysis = w; " + ALL, world=2)
+    d2 = copy_deck(tmp_path, "water_deck", "two")
+    outs = run_driver(d2, SIM % "analysis = w; " + ALL, world=2)
     assert not [l for o in outs for l in o[1].splitlines() if "not supported" in l]
     s = load_deck(str(d2 / "object.data"))
     f1, f2 = _frames(d1), _frames(d2)
@@ -149,10 +118,10 @@ def test_two_ranks_write_the_record_set_of_one(runs, tmp_path):
 
 
 def test_the_shipped_waterbox_deck_runs_and_writes_nothing_in_ten_steps(tmp_path):
-    d = _copy(tmp_path, "ref_waterbox", "ref")
-    outs = _run(d, "simulate SIMULATE { analysis = writeCharmm; }\n")
+    d = copy_deck(tmp_path, "ref_waterbox", "ref")
+    outs = run_driver(d, "simulate SIMULATE { analysis = writeCharmm; }\n")
     assert not [l for l in outs[0][1].splitlines() if "not supported" in l]
     assert not _frames(d) and os.path.getsize(str(d / "data")) > 0      # outputrate = 10000 is never reached
-    d0 = _copy(tmp_path, "ref_waterbox", "ref_as_shipped")
-    _run(d0, "")
+    d0 = copy_deck(tmp_path, "ref_waterbox", "ref_as_shipped")
+    run_driver(d0, "")
     assert open(str(d0 / "data"), "rb").read() == open(str(d / "data"), "rb").read()

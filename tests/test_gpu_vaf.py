@@ -301,24 +301,14 @@ def test_records_through_rccl_loopback(monkeypatch):
 def test_records_between_two_processes_over_the_host_transport():
     """two real processes (tests/mp_vaf_worker.py), the migration records carried by the host-staged TCP transport: windows over
     rebuilds, beads change rank; the ranks' sums against the numpy reference and the one-domain run"""
-    import subprocess
     import sys
     import tempfile
     from ddcmd_amd.martini import MartiniHIP
-    root = os.path.dirname(HERE)
+    from ranks import rank_env, run_ranks
     nsamples, every, length = 12, 10, 4
     with tempfile.TemporaryDirectory() as d:
-        procs = []
-        for rank in range(2):
-            env = dict(os.environ)
-            env.update({"RANK": str(rank), "WORLD_SIZE": "2", "LOCAL_RANK": str(rank), "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "1",
-                        "DDCMI_RDZV_FILE": os.path.join(d, "port"), "DDCMI_TRANSPORT": "host"})
-            env.pop("DDCMI_RCCL_LOOPBACK", None)
-            procs.append(subprocess.Popen([sys.executable, os.path.join(root, "tests", "mp_vaf_worker.py"), "2x1x1", d, str(nsamples), str(every), str(length)],
-                                          env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
-        for p in procs:
-            o, e = p.communicate(timeout=600)
-            assert p.returncode == 0, (o[-1500:], e[-3000:])
+        cmd = [sys.executable, os.path.join(HERE, "mp_vaf_worker.py"), "2x1x1", d, str(nsamples), str(every), str(length)]
+        run_ranks([cmd] * 2, [rank_env(r, 2, d) for r in range(2)], timeout=600, check=True)
         ranks = [dict(np.load(os.path.join(d, "rank%d.npz" % r))) for r in range(2)]
     s = make_water_setup(12)
     by_gid = np.argsort(s.gid, kind="stable")

@@ -4,48 +4,17 @@ writes it (gate, header, the one-group / one-species rule, units, member counts)
 by a Python run of the same deck."""
 import glob
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from ddcmd_amd.analysis import VelocityAutocorrelation, parse_vaf_output
 from ddcmd_amd.deck import load_deck, units_convert
+from ranks import GOLDEN, copy_deck, run_driver, tree_files
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "ddcmd_amd", "bin", "ddcmi_md")
 VAF = "vaf ANALYSIS { type = VELOCITYAUTOCORRELATION; eval_rate = 5; length = 4; outputrate = %d; }\n"
 SIM = "simulate SIMULATE { %sdeltaloop = 80; maxloop = 80; printrate = 5; snapshotrate = 100000; checkpointrate = 100000; }\n"
-
-
-def _copy(tmp_path, which, name):
-    d = tmp_path / name
-    shutil.copytree(os.path.join(ROOT, "tests", "golden", which), str(d))
-    return d
-
-
-def _run(cwd, extra, world=1):
-    args = ["-o", "object.data", "-d", "data", "-x", extra]
-    if world == 1:
-        out = subprocess.run([EXE] + args, capture_output=True, text=True, timeout=600, cwd=str(cwd))
-        assert out.returncode == 0, out.stdout + out.stderr
-        return out
-    env = dict(os.environ, WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", DDCMI_TRANSPORT="host", DDCMI_SINGLE_DEVICE="1",
-               DDCMI_RDZV_FILE=os.path.join(str(cwd), "rdzv_port"))
-    procs = [subprocess.Popen([EXE] + args, cwd=str(cwd), env=dict(env, RANK=str(r), LOCAL_RANK=str(r)), stdout=subprocess.PIPE,
-                              stderr=subprocess.PIPE, text=True) for r in range(world)]
-    outs = []
-    for p in procs:
-        try:
-            outs.append(p.communicate(timeout=600))
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-        assert p.returncode == 0, outs[-1]
-    return outs
 
 
 def _python_files(deck, loops):
@@ -72,10 +41,10 @@ def _python_files(deck, loops):
 
 @pytest.mark.parametrize("which", ["water_deck", "lipid_deck"])
 def test_driver_writes_vaf_files(tmp_path, which):
-    d = _copy(tmp_path, which, "with")
-    _run(d, SIM % "analysis = vaf; " + VAF % 40)
-    d0 = _copy(tmp_path, which, "without")
-    _run(d0, SIM % "")
+    d = copy_deck(tmp_path, which, "with")
+    run_driver(d, SIM % "analysis = vaf; " + VAF % 40)
+    d0 = copy_deck(tmp_path, which, "without")
+    run_driver(d0, SIM % "")
     assert open(str(d / "data"), "rb").read() == open(str(d0 / "data"), "rb").read()      # the analysis changes nothing of the run
     s, want = _python_files(str(d / "object.data"), (40, 80))
     nblock = 1 + (s.ngroup if s.ngroup > 1 else 0) + (s.nspecies if s.nspecies > 1 else 0)
@@ -100,16 +69,16 @@ def test_driver_writes_vaf_files(tmp_path, which):
 
 
 def test_gate_shut_writes_no_file(tmp_path):
-    d = _copy(tmp_path, "water_deck", "gate")
-    _run(d, SIM % "analysis = vaf; " + VAF % 30)      # nsample * 4 * 5 is 20 at loop 30, 60 at loop 60: never the outputrate
+    d = copy_deck(tmp_path, "water_deck", "gate")
+    run_driver(d, SIM % "analysis = vaf; " + VAF % 30)      # nsample * 4 * 5 is 20 at loop 30, 60 at loop 60: never the outputrate
     assert glob.glob(str(d / "snapshot.*" / "vaf.dat")) == []
 
 
 def test_driver_two_ranks_write_the_same_file(tmp_path):
-    d1 = _copy(tmp_path, "water_deck", "one")
-    _run(d1, SIM % "analysis = vaf; " + VAF % 40)
-    d2 = _copy(tmp_path, "water_deck", "two")
-    _run(d2, SIM % "analysis = vaf; " + VAF % 40, world=2)
+    d1 = copy_deck(tmp_path, "water_deck", "one")
+    run_driver(d1, SIM % "analysis = vaf; " + VAF % 40)
+    d2 = copy_deck(tmp_path, "water_deck", "two")
+    run_driver(d2, SIM % "analysis = vaf; " + VAF % 40, world=2)
     for loop in (40, 80):
         (a,) = glob.glob(str(d1 / ("snapshot.*%d" % loop) / "vaf.dat"))
         (b,) = glob.glob(str(d2 / ("snapshot.*%d" % loop) / "vaf.dat"))
@@ -121,11 +90,6 @@ def test_driver_two_ranks_write_the_same_file(tmp_path):
         assert np.allclose(v1, v2, rtol=2e-6, atol=2e-6 * np.abs(v1).max()) and np.allclose(m1, m2, rtol=2e-6, atol=0)
 
 
-def _files(d):
-    """every file under d, as paths relative to it"""
-    return sorted(os.path.relpath(os.path.join(p, f), str(d)) for p, _, fs in os.walk(str(d)) for f in fs)
-
-
 def test_driver_mixed_list_matches_single_analysis_runs(tmp_path):
     """a list of three types -- VELOCITYAUTOCORRELATION, an unsupported one, PAIRCORRELATION -- against the runs of its two supported
     members alone: the run itself, the g(r) files and the vaf files are the same bytes, the unsupported one is named once and writes
@@ -134,10 +98,10 @@ def test_driver_mixed_list_matches_single_analysis_runs(tmp_path):
     sim = "simulate SIMULATE { %sdeltaloop = 100; maxloop = 100; printrate = 5; snapshotrate = 100000; checkpointrate = 100000; }\n"
     rdf = "rdf ANALYSIS { type = PAIRCORRELATION; eval_rate = 10; outputrate = 50; delta_r = 0.1 Angstrom; length = 100; }\n"
     other = "writeCharmm ANALYSIS { type = subsetWrite; outputrate = 10; }\n"
-    da, db, dc = (_copy(tmp_path, "water_deck", n) for n in ("mixed", "rdf", "vaf"))
-    out = _run(da, sim % "analysis = vaf writeCharmm rdf; " + VAF % 40 + other + rdf)
-    _run(db, sim % "analysis = rdf; " + rdf)
-    _run(dc, sim % "analysis = vaf; " + VAF % 40)
+    da, db, dc = (copy_deck(tmp_path, "water_deck", n) for n in ("mixed", "rdf", "vaf"))
+    (out,) = run_driver(da, sim % "analysis = vaf writeCharmm rdf; " + VAF % 40 + other + rdf)
+    run_driver(db, sim % "analysis = rdf; " + rdf)
+    run_driver(dc, sim % "analysis = vaf; " + VAF % 40)
     data = [open(str(d / "data"), "rb").read() for d in (da, db, dc)]
     assert len(data[0]) > 0 and data[0] == data[1] == data[2]
     for single, name, loops in ((db, "paircorrelation.dat", (50, 100)), (dc, "vaf.dat", (40, 80))):
@@ -146,7 +110,7 @@ def test_driver_mixed_list_matches_single_analysis_runs(tmp_path):
             (b,) = glob.glob(str(single / ("snapshot.*%d" % loop) / name))
             ta, tb = open(a, "rb").read(), open(b, "rb").read()
             assert len(ta) > 0 and ta == tb, (name, loop)
-    written = sorted(set(_files(da)) - set(_files(os.path.join(ROOT, "tests", "golden", "water_deck"))))
+    written = sorted(set(tree_files(da)) - set(tree_files(os.path.join(GOLDEN, "water_deck"))))
     assert written == ["data", "snapshot.%012d/vaf.dat" % 40, "snapshot.%012d/paircorrelation.dat" % 50, "snapshot.%012d/vaf.dat" % 80,
                        "snapshot.%012d/paircorrelation.dat" % 100]      # no other analysis file
     lines = [l for l in out.stderr.splitlines() if "writeCharmm" in l]

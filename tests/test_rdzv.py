@@ -1,13 +1,12 @@
 """CPU: the process rendezvous of libddcmi (host/rdzv.c) between real processes --
 what bench.py and the multi-rank driver use in place of MPI / torch.distributed."""
+import json
 import os
 import sys
-import subprocess
 import tempfile
-import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from ranks import ROOT, run_ranks
 
 WORKER = r'''
 import os, sys, json
@@ -55,18 +54,9 @@ print("RESULT " + json.dumps(out), flush=True)
 
 
 def _launch(world, env_extra):
-    procs = []
-    for rank in range(world):
-        env = dict(os.environ)
-        env.update({"RANK": str(rank), "WORLD_SIZE": str(world), "MASTER_ADDR": "127.0.0.1"})
-        env.update(env_extra)
-        procs.append(subprocess.Popen([sys.executable, "-c", WORKER % {"root": ROOT}], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
-    res = []
-    for p in procs:
-        o, e = p.communicate(timeout=180)
-        assert p.returncode == 0, e[-2000:]
-        import json
-        res.append(json.loads([l for l in o.splitlines() if l.startswith("RESULT ")][-1][7:]))
+    envs = [dict(os.environ, RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", **env_extra) for rank in range(world)]
+    res = [json.loads([l for l in r.stdout.splitlines() if l.startswith("RESULT ")][-1][7:])
+           for r in run_ranks([[sys.executable, "-c", WORKER % {"root": ROOT}]] * world, envs, timeout=180, check=True)]
     return sorted(res, key=lambda d: d["rank"])
 
 
