@@ -1208,13 +1208,36 @@ extern "C" int ddcmi_constraint_stats(ddcmi_ctx *ctx, int *max_sweeps, int *unco
    return DDCMI_OK;
 }
 
+/* The three molecular-virial kernels leave one partial sum per workgroup -- the waves' sums added in wave order, a plain store --
+ * and k_mol_sum adds the workgroups' in workgroup order: no floating-point atomics, the barostat's pressure repeats bit for bit
+ * (the scheme of k_reduce_gather and of the census frame). */
+__device__ __forceinline__ void mol_block_store(const double (&acc)[3], double *__restrict__ part /* [gridDim.x][3] */)
+{
+   __shared__ double sh[4][3];
+#pragma unroll
+   for (int c = 0; c < 3; c++)
+   {
+      double w = wsum(acc[c]);
+      if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][c] = w;
+   }
+   __syncthreads();
+   if (threadIdx.x < 3) part[3 * (size_t)blockIdx.x + threadIdx.x] = ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
+}
+__global__ void k_mol_sum(int nblk, const double *__restrict__ part, double *__restrict__ out)
+{
+   const int c = threadIdx.x;
+   if (c >= 3) return;
+   double s = 0.0;
+   for (int b = 0; b < nblk; b++) s += part[3 * (size_t)b + c];
+   out[c] = s;
+}
 /* molecularVirial (molecularPressure.c:23-56): sum over the beads of every molecule of (r - R) f on the
  * diagonal, R = the molecule's centre of mass; images are resolved relative to the molecule's first
  * listed atom (the reference uses its ownership species; any atom gives the same numbers while a
  * molecule is smaller than half the box).  One lane per molecule of two or more beads. */
 __global__ __launch_bounds__(256) void k_mol_virial(int nmol, const int *__restrict__ mol_off, const int *__restrict__ atoms, const int *__restrict__ slot, BoxArgs box,
                                                     const double4 *__restrict__ pos, const int *__restrict__ species, const double *__restrict__ mass,
-                                                    const double *__restrict__ fx, const double *__restrict__ fy, const double *__restrict__ fz, double *out)
+                                                    const double *__restrict__ fx, const double *__restrict__ fy, const double *__restrict__ fz, double *__restrict__ part)
 {
    const int m = blockIdx.x * 256 + threadIdx.x;
    double acc[3] = {0, 0, 0};
@@ -1239,12 +1262,7 @@ __global__ __launch_bounds__(256) void k_mol_virial(int nmol, const int *__restr
          acc[0] += (x - Rx) * fx[s]; acc[1] += (y - Ry) * fy[s]; acc[2] += (z - Rz) * fz[s];
       }
    }
-#pragma unroll
-   for (int k = 0; k < 3; k++)
-   {
-      double w = wsum(acc[k]);
-      if ((threadIdx.x & 63) == 0 && w != 0.0) atomicAdd(out + k, w);
-   }
+   mol_block_store(acc, part);
 }
 
 /* The same for molecules named by gid (decomposed runs).  A rank sums over the atoms it OWNS, positions taken as nearest
@@ -1255,7 +1273,7 @@ __global__ __launch_bounds__(256) void k_mol_virial(int nmol, const int *__restr
 __global__ __launch_bounds__(256) void k_mol_virial_gid(int nmol, int nown, const int *__restrict__ mol_off, const int *__restrict__ slot, const int *__restrict__ split,
                                                         const double *__restrict__ info, const double *__restrict__ mtot, BoxArgs box,
                                                         const double4 *__restrict__ pos, const double *__restrict__ mass,
-                                                        const double *__restrict__ fx, const double *__restrict__ fy, const double *__restrict__ fz, double *red, double *out)
+                                                        const double *__restrict__ fx, const double *__restrict__ fy, const double *__restrict__ fz, double *red, double *__restrict__ part)
 {
    const int m = blockIdx.x * 256 + threadIdx.x;
    double acc[3] = {0, 0, 0};
@@ -1294,12 +1312,7 @@ __global__ __launch_bounds__(256) void k_mol_virial_gid(int nmol, int nown, cons
          }
       }
    }
-#pragma unroll
-   for (int c = 0; c < 3; c++)
-   {
-      double w = wsum(acc[c]);
-      if ((threadIdx.x & 63) == 0 && w != 0.0) atomicAdd(out + c, w);
-   }
+   mol_block_store(acc, part);
 }
 /* rebuild: mol_info[4m] = 1 if this rank owns an atom of molecule m, [4m+1..3] = position of its first listed atom if
  * this rank owns it; summed over the ranks that gives {owning ranks, anchor} */
@@ -1336,7 +1349,7 @@ __global__ void k_groups_check(int ngroups, int nown, const int *__restrict__ at
    if (mine && missing) atomicAdd(&flags[0], 1);
 }
 /* sum over the split molecules of (P/M) o F from the all-reduced {P, F} */
-__global__ __launch_bounds__(256) void k_mol_split_term(int nmol, const int *__restrict__ split, const double *__restrict__ mtot, const double *__restrict__ red, double *out)
+__global__ __launch_bounds__(256) void k_mol_split_term(int nmol, const int *__restrict__ split, const double *__restrict__ mtot, const double *__restrict__ red, double *__restrict__ part)
 {
    const int m = blockIdx.x * 256 + threadIdx.x;
    double acc[3] = {0, 0, 0};
@@ -1346,12 +1359,7 @@ __global__ __launch_bounds__(256) void k_mol_split_term(int nmol, const int *__r
       const double iM = 1.0 / mtot[m];
       for (int c = 0; c < 3; c++) acc[c] = (red[6 * k + c] * iM) * red[6 * k + 3 + c];
    }
-#pragma unroll
-   for (int c = 0; c < 3; c++)
-   {
-      double w = wsum(acc[c]);
-      if ((threadIdx.x & 63) == 0 && w != 0.0) atomicAdd(out + c, w);
-   }
+   mol_block_store(acc, part);
 }
 
 extern "C" int ddcmi_set_molecule_lists_gid(ddcmi_ctx *ctx, long nmol_total, int nmulti, const int *mol_off, const uint64_t *mol_atom_gid, const double *mol_mass)
@@ -1416,8 +1424,10 @@ int ddcmi_mol_split_term(ddcmi_ctx *ctx, double out[3])
    out[0] = out[1] = out[2] = 0.0;
    if (ctx->nsplit == 0) return DDCMI_OK;
    double *d = ctx->d_results + R_SCR_MOLV + 4;
-   HIPCHK(ctx, hipMemsetAsync(d, 0, 3 * sizeof(double), ctx->stream));
-   hipLaunchKernelGGL(k_mol_split_term, dim3(cdiv(ctx->nmol_multi, 256)), dim3(256), 0, ctx->stream, ctx->nmol_multi, ctx->mol_split.p, ctx->mol_mtot.p, ctx->mol_red.p, d);
+   const int nblk = cdiv(ctx->nmol_multi, 256);
+   ENSURE(ctx, ctx->mol_part, 3 * (size_t)nblk + 8);
+   hipLaunchKernelGGL(k_mol_split_term, dim3(nblk), dim3(256), 0, ctx->stream, ctx->nmol_multi, ctx->mol_split.p, ctx->mol_mtot.p, ctx->mol_red.p, ctx->mol_part.p);
+   hipLaunchKernelGGL(k_mol_sum, dim3(1), dim3(64), 0, ctx->stream, nblk, ctx->mol_part.p, d);
    HIPCHK(ctx, hipMemcpyAsync(out, d, 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
    return DDCMI_OK;
@@ -1454,15 +1464,19 @@ int ddcmi_launch_mol_virial(ddcmi_ctx *ctx)
    box.L[0] = ctx->h[0]; box.L[1] = ctx->h[4]; box.L[2] = ctx->h[8];
    for (int a = 0; a < 3; a++) box.Linv[a] = 1.0 / box.L[a];
    box.pbc = ctx->pbc;
+   const int nblk = cdiv(ctx->nmol_multi, 256);
+   ENSURE(ctx, ctx->mol_part, 3 * (size_t)nblk + 8);
    if (ctx->mol_gid)
    {
       if (ctx->nsplit > 0) HIPCHK(ctx, hipMemsetAsync(ctx->mol_red.p, 0, 6 * (size_t)ctx->nsplit * sizeof(double), ctx->stream));
       hipLaunchKernelGGL(k_mol_virial_gid, dim3(cdiv(ctx->nmol_multi, 256)), dim3(256), 0, ctx->stream, ctx->nmol_multi, ctx->nloc, ctx->mol_off.p, ctx->mol_slot.p, ctx->mol_split.p,
-                         ctx->mol_info.p, ctx->mol_mtot.p, box, ctx->pos.p, ctx->d_mass.p, ctx->fx.p, ctx->fy.p, ctx->fz.p, ctx->mol_red.p, ctx->d_results + R_SCR_MOLV);
+                         ctx->mol_info.p, ctx->mol_mtot.p, box, ctx->pos.p, ctx->d_mass.p, ctx->fx.p, ctx->fy.p, ctx->fz.p, ctx->mol_red.p, ctx->mol_part.p);
+      hipLaunchKernelGGL(k_mol_sum, dim3(1), dim3(64), 0, ctx->stream, nblk, ctx->mol_part.p, ctx->d_results + R_SCR_MOLV);
       return DDCMI_OK;
    }
    { int rcs = ddcmi_ensure_slots(ctx); if (rcs) return rcs; }
    hipLaunchKernelGGL(k_mol_virial, dim3(cdiv(ctx->nmol_multi, 256)), dim3(256), 0, ctx->stream, ctx->nmol_multi, ctx->mol_off.p, ctx->mol_atoms.p, ctx->slot_of_orig.p, box,
-                      ctx->pos.p, ctx->species.p, ctx->d_mass.p, ctx->fx.p, ctx->fy.p, ctx->fz.p, ctx->d_results + R_SCR_MOLV);
+                      ctx->pos.p, ctx->species.p, ctx->d_mass.p, ctx->fx.p, ctx->fy.p, ctx->fz.p, ctx->mol_part.p);
+   hipLaunchKernelGGL(k_mol_sum, dim3(1), dim3(64), 0, ctx->stream, nblk, ctx->mol_part.p, ctx->d_results + R_SCR_MOLV);
    return DDCMI_OK;
 }

@@ -287,7 +287,7 @@ struct ddcmi_ctx
     * atom was then: the common reference for nearest images); mol_split[m] = index among the split ones or -1;
     * mol_red[6k..] = this rank's {sum m x, sum f} of split molecule k, all-reduced every step the barostat acts */
    int nsplit = 0;
-   dbuf<double> mol_mtot, mol_info, mol_red; dbuf<int> mol_split;
+   dbuf<double> mol_mtot, mol_info, mol_red, mol_part /* [workgroup][3]: the virial kernels' partial sums */; dbuf<int> mol_split;
    double baro_sums[12] = {0};         /* this step's {virial xx yy zz, molecular term xx yy zz, beads of multi... } before / after the all-reduce */
    /* molecules of more than one bead (molecular virial of the barostat), caller-order atoms */
    long nmol_total = 0; int nmol_multi = 0; bool molv_valid = false;   /* R_SCR_MOLV belongs to the forces now in fx */

@@ -405,7 +405,8 @@ def molecule_lists(s):
 class MartiniHIP(object):
     """One device context running the Martini hot path for a Setup."""
 
-    def __init__(self, setup, device=0, upload=True, bonded_by_gid=False, constraints=False, test_api=False):
+    def __init__(self, setup, device=0, upload=True, bonded_by_gid=False, constraints=False, test_api=False, constraint_groups=None):
+        # constraint_groups: (pair_off, pairI, pairJ, dist) over caller-order atom indices, in place of expand_constraints(setup)
         # test_api: the context lives in libddcmi_test.so (same objects + the entry points of include/ddcmi_test.h)
         self.lib = _lib.load_test_library() if test_api else _lib.load_library()
         _declare(self.lib)
@@ -456,8 +457,12 @@ class MartiniHIP(object):
         if float(getattr(s, "npt_beta", 0.0)) > 0.0:      # INTEGRATOR type=NGLFCONSTRAINT: barostat on the molecular pressure
             self.set_barostat(float(s.npt_T), float(s.npt_P0), float(s.npt_beta), float(s.npt_tau), isotropic=bool(getattr(s, "npt_isotropic", 0)),
                               by_gid=bonded_by_gid)
-        if constraints:                                   # INTEGRATOR type=NGLFCONSTRAINT: velocity constraints
-            self._cons = expand_constraints(s)
+        if constraints or constraint_groups is not None:  # INTEGRATOR type=NGLFCONSTRAINT: velocity constraints
+            if constraint_groups is None:
+                self._cons = expand_constraints(s)
+            else:
+                po, pi, pj, dd = constraint_groups
+                self._cons = (i32(po), i32(pi), i32(pj), f64(dd))
             po, pi, pj, dd = self._cons
             if bonded_by_gid:                             # decomposed runs: the groups' atoms named by gid
                 gids = np.asarray(s.gid, dtype=np.uint64)
@@ -831,8 +836,9 @@ class DomainMixin(object):
 class MartiniRank(MartiniHIP, DomainMixin):
     """One rank of a decomposed run: uploads only the beads `index` selects."""
 
-    def __init__(self, setup, index, device=0, constraints=False, test_api=False):
-        MartiniHIP.__init__(self, setup, device=device, upload=False, bonded_by_gid=True, constraints=constraints, test_api=test_api)
+    def __init__(self, setup, index, device=0, constraints=False, test_api=False, constraint_groups=None):
+        MartiniHIP.__init__(self, setup, device=device, upload=False, bonded_by_gid=True, constraints=constraints, test_api=test_api,
+                            constraint_groups=constraint_groups)
         self.index = np.asarray(index)
 
     def upload_local(self):
@@ -882,12 +888,13 @@ class MartiniGroup(object):
     """px*py*pz domains emulated inside one process on one GPU (device copies
     instead of RCCL): exercises migration, halo tables and per-step halo refresh."""
 
-    def __init__(self, setup, grid, device=0, constraints=False):
+    def __init__(self, setup, grid, device=0, constraints=False, constraint_groups=None):
         self.s = setup
         self.grid = tuple(grid)
         self.n = grid[0] * grid[1] * grid[2]
         owner = domain_of(setup, grid)
-        self.ranks = [MartiniRank(setup, select_rank(setup, owner, r), device=device, constraints=constraints, test_api=True) for r in range(self.n)]
+        self.ranks = [MartiniRank(setup, select_rank(setup, owner, r), device=device, constraints=constraints, test_api=True,
+                                  constraint_groups=constraint_groups) for r in range(self.n)]
         self.lib = self.ranks[0].lib
         _declare_domains(self.lib)
         self.arr = (ctypes.c_void_p * self.n)(*[r.ctx for r in self.ranks])
