@@ -154,7 +154,76 @@ __device__ __forceinline__ double wave_reduce_dpp(double v)
    return Op::f(b, a);
 }
 __device__ __forceinline__ double wave_sum_dpp(double v) { return wave_reduce_dpp<WaveSum>(v); }
-/* the first half of it: every lane gets the sum over its ROW of 16 lanes (four DPP butterflies, no readlane) */
+/* N sums over the wave at once, transposed: lane k (k < N) gets what wave_sum_dpp(v[k]) gives, bit for bit; the other lanes get the sum of
+ * column (lane & 15) where that is below N and nothing of use else.  After a butterfly step both lanes of a pair hold the same partial sum, so
+ * of two columns the lane whose bit is clear carries the first onward and its partner the second: one add per PAIR of columns and step
+ * (N = 8: 4 + 2 + 1 + 1 adds inside the rows instead of 32).  Every column sees the additions of wave_reduce_dpp<WaveSum> with the same
+ * operands -- which lane performs a + b, and whether as a + b or b + a, changes no bit of a sum (a NaN's payload apart) -- in the same tree:
+ * partner lane ^ 1, ^ 2, then the other quad of the 8 and the other half of the row (row_half_mirror and row_mirror there, where the lanes of
+ * a quad / of 8 hold one value; the columns lie across them here, hence lane ^ 4 by row_shl / row_shr 4 and lane ^ 8 by row_ror 8), then
+ * (r1 + r0) + (r3 + r2) over the rows of 16.  The rows meet by v_permlane16_swap / v_permlane32_swap (gfx950) instead of v_readlane: the
+ * row sums are different values in the 16 lanes of a row now, and the swaps move whole rows at once, in the VALU like DPP. */
+template <int CTRL>
+__device__ __forceinline__ double dpp_move_z(double v)      /* dpp_move; a lane whose control names no source lane reads zero (such a lane never uses what it read) */
+{
+   const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, true);
+   const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, true);
+   return __hiloint2double(hi, lo);
+}
+/* one step for two columns: DN brings the partner's value to the lanes with the step's bit clear (low), UP to the others */
+template <int DN, int UP>
+__device__ __forceinline__ double wave_multi_pair(double a, double b, bool low)
+{
+   const double own = low ? a : b;
+   if (DN == UP) return own + dpp_move_z<DN>(low ? b : a);      /* (one control serves both directions: every lane sends what its partner keeps) */
+   const double ga = dpp_move_z<DN>(a), gb = dpp_move_z<UP>(b);      /* (both moves by every lane, then the choice: a move inside a branch finds its source lane switched off) */
+   return own + (low ? ga : gb);
+}
+/* ... for a column without a partner column: the plain butterfly step */
+template <int DN, int UP>
+__device__ __forceinline__ double wave_multi_single(double a, bool low)
+{
+   if (DN == UP) return a + dpp_move_z<DN>(a);
+   const double ga = dpp_move_z<DN>(a), gb = dpp_move_z<UP>(a);
+   return a + (low ? ga : gb);
+}
+template <int DN, int UP, int M, int NW>
+__device__ __forceinline__ void wave_multi_step(double (&w)[NW], bool low)
+{
+#pragma unroll
+   for (int j = 0; j < (M + 1) / 2; j++)
+   {
+      if (2 * j + 1 < M) w[j] = wave_multi_pair<DN, UP>(w[2 * j], w[2 * j + 1], low);
+      else w[j] = wave_multi_single<DN, UP>(w[2 * j], low);
+   }
+}
+template <int N>
+__device__ __forceinline__ double wave_sum_multi_dpp(const double (&v)[N], int lane)
+{
+   static_assert(N >= 1 && N <= 16, "one column per lane of a row");
+   constexpr int M1 = (N + 1) / 2, M2 = (M1 + 1) / 2, M3 = (M2 + 1) / 2;
+   double w[N];
+#pragma unroll
+   for (int k = 0; k < N; k++) w[k] = v[k];
+   wave_multi_step<0xB1, 0xB1, N>(w, !(lane & 1));         /* quad_perm [1,0,3,2] */
+   wave_multi_step<0x4E, 0x4E, M1>(w, !(lane & 2));        /* quad_perm [2,3,0,1] */
+   wave_multi_step<0x104, 0x114, M2>(w, !(lane & 4));      /* row_shl 4 / row_shr 4 */
+   wave_multi_step<0x128, 0x128, M3>(w, !(lane & 8));      /* row_ror 8 */
+   /* the rows: a swap of a register with its own copy leaves {r0 r0 r2 r2} in one and {r1 r1 r3 r3} in the other, then the two halves likewise */
+   double s = w[0];
+   {
+      const auto lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(s), (unsigned)__double2loint(s), false, false);
+      const auto hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(s), (unsigned)__double2hiint(s), false, false);
+      s = __hiloint2double((int)hi[0], (int)lo[0]) + __hiloint2double((int)hi[1], (int)lo[1]);
+   }
+   {
+      const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(s), (unsigned)__double2loint(s), false, false);
+      const auto hi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(s), (unsigned)__double2hiint(s), false, false);
+      s = __hiloint2double((int)hi[0], (int)lo[0]) + __hiloint2double((int)hi[1], (int)lo[1]);
+   }
+   return s;
+}
+/* the first half of wave_sum_dpp: every lane gets the sum over its ROW of 16 lanes (four DPP butterflies, no readlane) */
 __device__ __forceinline__ double row_sum_dpp(double v)
 {
    v += dpp_move<0xB1>(v);
@@ -202,6 +271,48 @@ __device__ __forceinline__ void block_reduce_store(double (&v)[NV], double *out)
       for (int q = 1; q < NW; q++) a += s_red[q][k];
       out[k] = a;
    }
+}
+
+/* ddcmi_debug_wave_reduce (include/ddcmi_test.h): one wave per set of 64 x N doubles; column k by wave_sum_dpp and all columns by
+ * wave_sum_multi_dpp<N>, for the tests to hold the bits of the two against each other */
+template <int N>
+__global__ __launch_bounds__(64) void k_debug_wave_reduce(const double *__restrict__ in, double *__restrict__ single, double *__restrict__ multi)
+{
+   const int lane = threadIdx.x;
+   const double *set = in + (size_t)blockIdx.x * 64 * N;
+   double v[N];
+#pragma unroll
+   for (int k = 0; k < N; k++) v[k] = set[lane * N + k];
+#pragma unroll
+   for (int k = 0; k < N; k++)
+   {
+      const double s = wave_sum_dpp(v[k]);
+      if (lane == k) single[(size_t)blockIdx.x * N + k] = s;
+   }
+   const double m = wave_sum_multi_dpp<N>(v, lane);
+   if (lane < N) multi[(size_t)blockIdx.x * N + lane] = m;
+}
+template <int N>
+static int debug_wave_reduce_launch(int n, int nsets, const double *in, double *single, double *multi)
+{
+   if constexpr (N < 16) { if (n != N) return debug_wave_reduce_launch<N + 1>(n, nsets, in, single, multi); }
+   const size_t nin = (size_t)nsets * 64 * N, nout = (size_t)nsets * N;
+   double *d = nullptr;
+   if (hipMalloc((void **)&d, (nin + 2 * nout) * sizeof(double)) != hipSuccess) return DDCMI_ENOMEM;
+   int rc = DDCMI_ENODEVICE;
+   if (hipMemcpy(d, in, nin * sizeof(double), hipMemcpyHostToDevice) == hipSuccess)
+   {
+      hipLaunchKernelGGL(k_debug_wave_reduce<N>, dim3(nsets), dim3(64), 0, 0, d, d + nin, d + nin + nout);
+      if (hipGetLastError() == hipSuccess && hipMemcpy(single, d + nin, nout * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess &&
+          hipMemcpy(multi, d + nin + nout, nout * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess) rc = DDCMI_OK;
+   }
+   (void)hipFree(d);
+   return rc;
+}
+extern "C" int ddcmi_debug_wave_reduce(int n, int nsets, const double *in, double *single, double *multi)
+{
+   if (n < 1 || n > 16 || nsets < 1 || nsets > 65535 || !in || !single || !multi) return DDCMI_EINVAL;
+   return debug_wave_reduce_launch<1>(n, nsets, in, single, multi);
 }
 
 /* backInBox_fast: PreduceOrthorhombicB7_OneLatticeReduction (preduce.c:147-160) */

@@ -103,6 +103,10 @@ __global__ __launch_bounds__(NB_BLOCK, WPE) void k_nonbond(GridParams gp, NbTile
    const int item = mine ? ta.perm[slot] : 0;
    const int t = item & 0xffffff, part = (item >> 24) & 7, nparts = ((item >> 27) & 7) + 1;
    double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};   /* vLJ, vEle, xx,yy,zz,xy,xz,yz */
+   /* the eight sums of acc[] at the end go through wave_sum_multi_dpp in one pass, except in the one instantiation where that costs a
+    * register the 128 do not have (charged, packed entries with the shift bit, fused, one-level table: one more spilled, 12 -> 16 bytes of
+    * scratch): it keeps the eight wave_sum_dpp calls.  The seven kinetic sums of the fused epilogue take the one pass everywhere. */
+   constexpr bool ACC_MULTI = !(HAS_Q && PACKED && SHBIT && FUSE && !LVL);
    float wg_v2 = 0.0f;                        /* (lean step: the workgroup's largest |v|^2, thread 64 + 7) */
    /* the last shell this launch walks (NbTileArgs::disp) */
    int smax = NSHELL - 1;
@@ -567,13 +571,7 @@ __global__ __launch_bounds__(NB_BLOCK, WPE) void k_nonbond(GridParams gp, NbTile
             }
             /* the wave's row of kinetic sums (only this wave touches it; the rows are added in index order at the end) */
             double *ke_row = (double *)((char *)smem + fa.ke_off) + (threadIdx.x >> 6) * 8;
-            double mine = 0.0;
-#pragma unroll
-            for (int k = 0; k < 7; k++)
-            {
-               const double sv = wave_sum_dpp(ke[k]);      /* (uniform over the wave) */
-               if (lane == k) mine = sv;
-            }
+            double mine = wave_sum_multi_dpp<7>(ke, lane);      /* (lane k < 7: the wave's sum of ke[k], the bits of wave_sum_dpp) */
             {
                /* the wave's largest |v|^2 (non-negative floats order like their bit patterns) */
                int vb = __float_as_int(v2max);
@@ -593,11 +591,19 @@ __global__ __launch_bounds__(NB_BLOCK, WPE) void k_nonbond(GridParams gp, NbTile
       __syncthreads();
       double *s_red = (double *)smem;
       const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-      for (int k = 0; k < 8; k++)
+      if (ACC_MULTI)
       {
-         double sv = wave_sum_dpp(acc[k]);
-         if (lane == 0) s_red[w * 8 + k] = sv;
+         const double sv = wave_sum_multi_dpp<8>(acc, lane);      /* (lane k < 8: the wave's sum of acc[k]) */
+         if (lane < 8) s_red[w * 8 + lane] = sv;
+      }
+      else
+      {
+#pragma unroll
+         for (int k = 0; k < 8; k++)
+         {
+            double sv = wave_sum_dpp(acc[k]);
+            if (lane == 0) s_red[w * 8 + k] = sv;
+         }
       }
       __syncthreads();
       if (threadIdx.x < 8)

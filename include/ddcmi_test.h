@@ -5,7 +5,8 @@
  *   ddcmi_group_*              in-process emulation of a px*py*pz decomposition on ONE GPU (the multi-domain path without RCCL)
  *   ddcmi_plan_*               the host logic of the halo exchange / domain directions, callable without a GPU (world-2 CPU tests)
  *   ddcmi_debug_branch_census  which rarely taken dihedral branches a test's geometry drives
- *   ddcmi_debug_bonded_layout  what the bonded kernels' lane layout decided for a test's term lists */
+ *   ddcmi_debug_bonded_layout  what the bonded kernels' lane layout decided for a test's term lists
+ *   ddcmi_debug_wave_reduce    the transposed wave reduction of several sums against the one-sum reduction, on the test's own numbers */
 #ifndef DDCMI_TEST_H
 #define DDCMI_TEST_H
 #include "ddcmi.h"
@@ -80,6 +81,11 @@ int ddcmi_group_subset_records(ddcmi_ctx **ctxs, int n, const ddcmi_subset_filte
 int ddcmi_debug_lean_history(ddcmi_ctx *ctx, int *nsteps, double *sums);
 /* the displacement bound of the shell-limited walk: the word the reduction launches add to, and the lean steps' words since the rebuild (largest |v|^2 of each; ring[32]) */
 int ddcmi_debug_disp(ddcmi_ctx *ctx, double *disp, float *ring, int *nring);
+
+/* the wave reductions of the pair kernel's epilogue against each other, on the current device: nsets sets of in[64][n] doubles (lane-major, 1 <= n <= 16,
+ * nsets <= 65535), one 64-thread workgroup each; single[set][k] = wave_sum_dpp of column k, multi[set][k] = what wave_sum_multi_dpp<n> of all
+ * columns hands lane k.  The two must agree bit for bit. [sync] */
+int ddcmi_debug_wave_reduce(int n, int nsets, const double *in, double *single, double *multi);
 
 /* roctx ranges opened so far (DDCMI_ROCTX=1: MDSTEP, DDCENERGY, CHARMM_NONBOND ... named like ptiming.h's regions; 0 without the variable) */
 long ddcmi_debug_roctx_ranges(void);
