@@ -82,7 +82,7 @@ c_u64_p = ctypes.POINTER(ctypes.c_uint64)
 c_char_pp = ctypes.POINTER(ctypes.c_char_p)
 
 
-AN_NONE, AN_PAIRCORRELATION, AN_VAF, AN_VCMWRITE, AN_ZDENSITY, AN_KDIST, AN_DSF, AN_SUBSETWRITE = range(8)      # enum ddcmi_analysis_kind
+AN_NONE, AN_PAIRCORRELATION, AN_VAF, AN_VCMWRITE, AN_ZDENSITY, AN_KDIST, AN_DSF, AN_SUBSETWRITE, AN_COARSEGRAIN = range(9)      # enum ddcmi_analysis_kind
 
 
 class CKdistGroup(ctypes.Structure):
@@ -102,7 +102,8 @@ class CAnalysis(ctypes.Structure):
                 ("sw_idmin", ctypes.c_uint64), ("sw_idmax", ctypes.c_uint64), ("sw_nid", ctypes.c_int), ("sw_idlist", c_u64_p),
                 ("sw_nspecies", ctypes.c_int), ("sw_species", c_char_pp),
                 ("sw_rmin", ctypes.c_double * 3), ("sw_rmax", ctypes.c_double * 3), ("sw_vmin", ctypes.c_double * 3), ("sw_vmax", ctypes.c_double * 3),
-                ("sw_given", ctypes.c_int)]
+                ("sw_given", ctypes.c_int),
+                ("cg_n", ctypes.c_int * 3), ("cg_output_mode", ctypes.c_int), ("cg_nfiles", ctypes.c_int), ("cg_smear_string", ctypes.c_char_p)]
 
 
 class CSetup(ctypes.Structure):

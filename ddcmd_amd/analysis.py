@@ -1,4 +1,4 @@
-"""ANALYSIS types PAIRCORRELATION, VELOCITYAUTOCORRELATION, vcmWrite, zdensity, KINETICENERGYDISTN, DSF and subsetWrite on the host side.
+"""ANALYSIS types PAIRCORRELATION, VELOCITYAUTOCORRELATION, vcmWrite, zdensity, KINETICENERGYDISTN, DSF, subsetWrite and COARSEGRAIN on the host side.
 PairCorrelation: accumulation of the device's pair counts into g(r) and the output file, as paircorrelation_eval_geom /
 paircorrelation_output (paircorrelation.c) do.  The counting itself is ddcmi_pair_correlation (Martini*.pair_correlation); nothing
 here searches pairs.
@@ -10,7 +10,10 @@ KineticEnergyDistn: the accumulation and the two files of kineticEnergyDistn.c f
 DynamicStructureFactor: the wave vectors, the buffer and the file text of dsf.c from the device's charge-density modes
 (Martini*.charge_density_modes).
 SubsetWrite: the pinfo tables of pinfo.c, the header of write_fileheader (io.c) and the file of subsetWriteBinaryCharmm
-(subsetWrite.c) around the device's packed records (Martini*.subset_records); read_subset reads such a file back."""
+(subsetWrite.c) around the device's packed records (Martini*.subset_records); read_subset reads such a file back.
+CoarseGrain: the table keyed by (label, species) that accumulates the device's evaluations (Martini*.coarsegrain) and the cgrid file
+of coarsegrain_output (coarsegrain.c:449-573); read_cgrid reads such a file back and verifies every record's checksum."""
+import zlib
 import os
 import time as _time
 
@@ -580,3 +583,191 @@ def read_subset(path):
     if len(raw) - off != hdr["nrecord"] * hdr["lrec"]:
         raise ValueError("%s: %d bytes behind the header, nrecord * lrec = %d" % (path, len(raw) - off, hdr["nrecord"] * hdr["lrec"]))
     return hdr, np.frombuffer(raw, SUBSET_RECORD, count=hdr["nrecord"], offset=off).copy()
+
+
+CG_RECORD = np.dtype([("label", "<i8"), ("species", "<i4"), ("pad", "<i4"), ("n", "<f8"), ("mass", "<f8"), ("K", "<f8", (3,)), ("p", "<f8", (3,))])      # struct ddcmi_cg_record
+_CG_SUMS = ("n", "mass", "K", "p")
+_CG_NAMES = {1: "checksum label species_index number_particles mass  Kx Ky Kz U virial px py pz",
+             2: "checksum label species_index number_particles mass  Kx Ky Kz U virial px py pz vir_xx vir_yy vir_zz vir_xy vir_xz vir_yz"}
+_CG_UNITS = {1: "1 1 1 1 amu eV eV eV eV eV amu*Angstrom/fs amu*Angstrom/fs amu*Angstrom/fs",
+             2: "1 1 1 1 amu eV eV eV eV eV amu*Angstrom/fs amu*Angstrom/fs amu*Angstrom/fs eV eV eV eV eV eV"}
+
+
+def b_field_size(top):
+    """bFieldSize: the fewest whole bytes that hold the unsigned integer `top` (at least one)"""
+    nbytes = 1
+    while int(top) >> (8 * nbytes):
+        nbytes += 1
+    return nbytes
+
+
+def merge_cg_records(blocks):
+    """the blocks of CG_RECORD (each ascending in (label, species)) merged in the order given: one entry per key in ascending order, an entry
+    of several blocks the sum of theirs, added block after block"""
+    out = np.zeros(0, CG_RECORD)
+    for blk in blocks:
+        blk = np.asarray(blk, CG_RECORD)
+        if len(blk) == 0:
+            continue
+        if len(out) == 0:
+            out = blk.copy()
+            continue
+        both = np.concatenate([out, blk])
+        order = np.lexsort((np.concatenate([np.zeros(len(out), np.int8), np.ones(len(blk), np.int8)]), both["species"], both["label"]))      # stable: out's entry first
+        both = both[order]
+        first = np.ones(len(both), bool)
+        first[1:] = (both["label"][1:] != both["label"][:-1]) | (both["species"][1:] != both["species"][:-1])
+        merged = both[first].copy()
+        dup = np.flatnonzero(~first)      # a key of both: its second entry (blk's) sits right behind its first (out's)
+        at = np.cumsum(first)[dup] - 1
+        for f in _CG_SUMS:
+            merged[f][at] = both[f][dup - 1] + both[f][dup]
+        out = merged
+    return out
+
+
+class CoarseGrain(object):
+    """one COARSEGRAIN analysis (coarsegrain.c).  add(records) takes one evaluation -- the records of Martini.coarsegrain, or a list of
+    the ranks' records, merged in rank order -- into the table keyed by (label, species) and counts nsteps; clear() empties both;
+    file_bytes(...) is the cgrid file of the table: header(...) and one record per entry in ascending (label, species): a u4 CRC-32 of the
+    bytes behind it (native byte order), label and species_index as unsigned integers of b_field_size(nx ny nz - 1) and
+    b_field_size(nspecies - 1) bytes, most significant byte first, and the f4 fields (float)(sum * convert * (1.0 / nsteps)) multiplied
+    left to right in double; U, virial and the virial tensor are 0.0f.  output_mode 1: 13 fields, 2: 19 fields."""
+
+    def __init__(self, nx, ny, nz, species_names, filename="cgrid", output_mode=2, smear_radius=0.0, smear_method="impulse", eval_rate=0, outputrate=0):
+        if min(int(nx), int(ny), int(nz)) < 1:
+            raise ValueError("nx = %d, ny = %d, nz = %d: each must be at least 1" % (nx, ny, nz))
+        if int(output_mode) not in (1, 2):
+            raise ValueError("outputMode = %d: 1 or 2 (3 divides by the species' charge and is not supported)" % output_mode)
+        self.nx, self.ny, self.nz = int(nx), int(ny), int(nz)
+        self.species_names = list(species_names)
+        self.filename, self.output_mode = filename, int(output_mode)
+        self.smear_radius, self.smear_string = float(smear_radius), str(smear_method)
+        self.smear_method = "hat" if self.smear_string.lower() == "hat" else "impulse"
+        self.eval_rate, self.outputrate = int(eval_rate), int(outputrate)
+        self.label_bytes = b_field_size(self.nx * self.ny * self.nz - 1)
+        self.species_bytes = b_field_size(max(len(self.species_names), 1) - 1)
+        self.nf4 = 10 if self.output_mode == 1 else 16      # the f4 fields behind checksum, label and species_index
+        self.lrec = 4 + self.label_bytes + self.species_bytes + 4 * self.nf4
+        self.clear()
+
+    def args(self):
+        """the arguments of Martini*.coarsegrain"""
+        return dict(nx=self.nx, ny=self.ny, nz=self.nz, smear_radius=self.smear_radius, smear_method=self.smear_method)
+
+    def clear(self):
+        self.table, self.nsteps = np.zeros(0, CG_RECORD), 0
+
+    def add(self, records):
+        blocks = [records] if isinstance(records, np.ndarray) else list(records)
+        self.table = merge_cg_records([self.table] + blocks)
+        self.nsteps += 1
+
+    def misc_info(self):
+        t = "nx = %d; ny = %d; nz=%d; smearRadius=%f; smearMethod=%s;\n       ouputrate=%d; eval_rate=%d; species=" % (
+            self.nx, self.ny, self.nz, units_convert(self.smear_radius, None, "l"), self.smear_string, self.outputrate, self.eval_rate)
+        return t + "".join(" " + n for n in self.species_names) + ";" + "\n  nSamples = %d;" % self.nsteps
+
+    def header(self, nrecord, loop, time, h, version="", create_time=None):
+        """write_fileheader (io.c:352-404) for class cgrid: time and h in internal units"""
+        h = np.asarray(h, np.float64).reshape(-1) * units_convert(1.0, None, "l")
+        stamp = create_time or _time.strftime("%Y-%m-%d-%H:%M:%S", _time.localtime())
+        key = int(np.frombuffer(b"1234", "<i4")[0])
+        t = "cgrid FILEHEADER {type=MULTILINE; datatype=FIXRECORDBINARY; checksum=CRC32; create_time=%s; run_id=0x%08x;\n" % (stamp, 0)
+        t += "code_version=%s; srcpath=libddcmi;\n" % version
+        t += "loop=%d; time=%f fs;\n" % (loop, units_convert(time, None, "t"))
+        t += "nfiles=1; nrecord=%d; lrec=%d; nfields=%d; endian_key=%d;\n" % (nrecord, self.lrec, self.nf4 + 3, key)
+        t += "field_names=%s;\n" % _CG_NAMES[self.output_mode]
+        t += "field_types=u4 b%d b%d%s;\n" % (self.label_bytes, self.species_bytes, " f4" * self.nf4)
+        t += "field_units=%s;\n" % _CG_UNITS[self.output_mode]
+        t += "reducedcorner=%21.14f %21.14f %21.14f;\n" % (-0.5, -0.5, -0.5)
+        t += "h=%21.14f %21.14f %21.14f\n  %21.14f %21.14f %21.14f\n  %21.14f %21.14f %21.14f Ang;\n" % tuple(h)
+        t += self.misc_info() + "\n"
+        return t + "}\n \n\n"
+
+    def fields(self):
+        """the table's f4 fields [entry, nf4], in the file's order"""
+        tab, inv = self.table, 1.0 / (self.nsteps * 1.0)
+        mc, ec, pc = units_convert(1.0, None, "amu"), units_convert(1.0, None, "eV"), units_convert(1.0, None, "amu*Angstrom/fs")
+        v = np.zeros((len(tab), self.nf4), np.float32)
+        v[:, 0] = (tab["n"] * inv).astype(np.float32)
+        v[:, 1] = (tab["mass"] * mc * inv).astype(np.float32)
+        v[:, 2:5] = (tab["K"] * ec * inv).astype(np.float32)
+        v[:, 7:10] = (tab["p"] * pc * inv).astype(np.float32)      # [5], [6]: U, virial; [10:]: the virial tensor
+        return v
+
+    def record_bytes(self):
+        tab, lb, sb = self.table, self.label_bytes, self.species_bytes
+        rec = np.zeros((len(tab), self.lrec), np.uint8)
+        for k in range(lb):
+            rec[:, 4 + k] = (tab["label"].astype(np.uint64) >> np.uint64(8 * (lb - 1 - k))).astype(np.uint8)
+        for k in range(sb):
+            rec[:, 4 + lb + k] = (tab["species"].astype(np.uint64) >> np.uint64(8 * (sb - 1 - k))).astype(np.uint8)
+        rec[:, 4 + lb + sb:] = np.ascontiguousarray(self.fields()).view(np.uint8).reshape(len(tab), 4 * self.nf4)
+        crc = np.array([zlib.crc32(row[4:].tobytes()) & 0xffffffff for row in rec], np.uint32)
+        rec[:, :4] = crc.view(np.uint8).reshape(len(tab), 4)
+        return rec.tobytes()
+
+    def file_bytes(self, loop, time, h, version="", create_time=None):
+        if self.nsteps < 1:
+            raise ValueError("no evaluation since the last clear: nSamples = 0")
+        return self.header(len(self.table), loop, time, h, version, create_time).encode() + self.record_bytes()
+
+    def write(self, directory, loop, time, h, version=""):
+        """<directory>/<filename>#000000, under a temporary name first; clears; returns the path"""
+        path = os.path.join(directory, self.filename + "#000000")
+        with open(path + ".tmp", "wb") as f:
+            f.write(self.file_bytes(loop, time, h, version))
+        os.rename(path + ".tmp", path)
+        self.clear()
+        return path
+
+
+def read_cgrid(path):
+    """(header dict, records) of a cgrid file: the header's keys as read_subset gives them, with nSamples, nx, ny, nz as int, and a
+    structured array {checksum u4, label u8, species_index u8, then the f4 fields by their names}; a record whose CRC-32 does not match its
+    checksum field is a ValueError"""
+    raw = open(path, "rb").read()
+    end = raw.index(b"\n}\n")
+    text = raw[:end].decode()
+    off = end + 1 + len(b"}\n \n\n")
+    if raw[end + 1:off] != b"}\n \n\n":
+        raise ValueError("%s: the header does not end as write_fileheader ends it" % path)
+    name, rest = text.split(" FILEHEADER {", 1)
+    hdr = {"name": name.strip()}
+    for item in rest.split(";"):
+        if "=" not in item:
+            continue
+        k, v = item.split("=", 1)
+        hdr[k.strip()] = v.strip()
+    for k in ("nrecord", "lrec", "nfields", "nfiles", "loop", "endian_key", "nSamples", "nx", "ny", "nz"):
+        hdr[k] = int(hdr[k])
+    for k in ("species", "field_names", "field_types", "field_units"):
+        hdr[k] = hdr.get(k, "").split()
+    hdr["h"] = [float(x) for x in hdr["h"].split()[:9]]
+    names, types = hdr["field_names"], hdr["field_types"]
+    if hdr["name"] != "cgrid" or hdr["datatype"] != "FIXRECORDBINARY" or hdr["checksum"] != "CRC32" or len(names) != hdr["nfields"] or len(types) != hdr["nfields"]:
+        raise ValueError("%s: not a cgrid file" % path)
+    if types[0] != "u4" or types[1][0] != "b" or types[2][0] != "b" or any(t != "f4" for t in types[3:]):
+        raise ValueError("%s: field_types = %s" % (path, " ".join(types)))
+    lb, sb = int(types[1][1:]), int(types[2][1:])
+    lrec, nrec = hdr["lrec"], hdr["nrecord"]
+    if lrec != 4 + lb + sb + 4 * (len(types) - 3):
+        raise ValueError("%s: lrec = %d does not fit field_types = %s" % (path, lrec, " ".join(types)))
+    if len(raw) - off != nrec * lrec:
+        raise ValueError("%s: %d bytes behind the header, nrecord * lrec = %d" % (path, len(raw) - off, nrec * lrec))
+    body = np.frombuffer(raw, np.uint8, count=nrec * lrec, offset=off).reshape(nrec, lrec)
+    out = np.zeros(nrec, np.dtype([("checksum", "<u4"), ("label", "<u8"), ("species_index", "<u8")] + [(n, "<f4") for n in names[3:]]))
+    out["checksum"] = np.ascontiguousarray(body[:, :4]).view(np.uint32).reshape(nrec)
+    for k in range(lb):
+        out["label"] = (out["label"] << np.uint64(8)) | body[:, 4 + k].astype(np.uint64)
+    for k in range(sb):
+        out["species_index"] = (out["species_index"] << np.uint64(8)) | body[:, 4 + lb + k].astype(np.uint64)
+    f4 = np.ascontiguousarray(body[:, 4 + lb + sb:]).view(np.float32).reshape(nrec, len(names) - 3)
+    for q, n in enumerate(names[3:]):
+        out[n] = f4[:, q]
+    for k in range(nrec):
+        crc = zlib.crc32(body[k, 4:].tobytes()) & 0xffffffff
+        if crc != int(out["checksum"][k]):
+            raise ValueError("%s: record %d: checksum %08x, CRC-32 of its bytes %08x" % (path, k, int(out["checksum"][k]), crc))
+    return hdr, out

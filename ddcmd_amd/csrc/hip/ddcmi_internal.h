@@ -375,6 +375,9 @@ struct ddcmi_ctx
    dbuf<double> census_part;      /* the census passes (ddcmi_census_frame.inl): the pass's per-workgroup sums and, behind them, its result */
    /* subsetWrite's frames (ddcmi_subset.inl): the filter's tables with the workgroups' counts and offsets, the idList, the packed records */
    dbuf<unsigned> subset_tab; dbuf<unsigned long long> subset_ids, subset_rec;
+   /* COARSEGRAIN (ddcmi_coarsegrain.inl): the sort's (key, value) pairs, source and destination; its digit counts and their scan; the
+    * workgroups' head counts and offsets; the segment table; the records */
+   dbuf<unsigned> cg_key, cg_val, cg_cnt, cg_seg; dbuf<int> cg_hist; dbuf<unsigned long long> cg_rec;
    /* what is not a dbuf or an hbuf; those free themselves after this */
    ~ddcmi_ctx()
    {

@@ -798,6 +798,201 @@ static void sw_free(void *state)
    free(p->include); free(p->gterm); free(p->sterm); free(p->ugname); free(p->usname); free(p->info); free(p);
 }
 
+/* ANALYSIS type COARSEGRAIN (coarsegrain.c: parms :80-119, eval :242-448, output :449-583, clear :585-597; matched by its head in any
+ * case, analysis.c:162): per (grid cell, species) the sums {number, mass, K, momentum} of the beads, averaged over the evaluations of an
+ * output window.  Every evaluation comes from the device (ddcmi_coarsegrain: this rank's non-empty entries in ascending (label, species)
+ * order) and is merged into the rank's own table, which stays in that order; nsteps counts them.  At outputrate the ranks' tables are
+ * gathered on rank 0 (the transport subsetWrite uses) and merged in rank order, duplicate keys added; rank 0 writes
+ * snapshot.<loop>/<filename>#000000 -- the FILEHEADER of class cgrid, then one record per entry in ascending (label, species) (the
+ * reference's order is its hash table's) -- under a temporary name and renames it; table and nsteps are cleared.  The startup sample is
+ * cleared as well.  One file whatever nfiles says.  A record: u4 CRC-32 of the bytes behind it in native byte order; label and
+ * species_index as unsigned integers of the fewest whole bytes that hold nx ny nz - 1 and nspecies - 1, MOST SIGNIFICANT BYTE FIRST
+ * (bFieldPack lives in the reference's util submodule, which is not part of the reference tree: the order is fixed here); the f4
+ * fields (float)(sum * convert * (1.0 / nsteps)), multiplied left to right in double.  U, virial and the virial tensor are per-atom
+ * arrays the Martini path never fills: 0.0f.  Refused at load: nx, ny or nz < 1 (the reference divides by zero), no field_units key
+ * (the reference aborts), outputMode outside 1 to 3, more keys than DDCMI_CG_MAX_KEYS (deck.c); outputMode = 3 divides by the species'
+ * charge: deck.c leaves such an object unsupported. */
+typedef struct { int nsteps; int64_t n, cap; ddcmi_cg_record *tab; char *info; } CGSTATE;
+static void cg_parms(const OBJECT *obj, ddcmi_analysis *an, char *msg, int msglen)
+{
+   object_get(obj, "nx", &an->cg_n[0], INT, 1, "0");
+   object_get(obj, "ny", &an->cg_n[1], INT, 1, "0");
+   object_get(obj, "nz", &an->cg_n[2], INT, 1, "0");
+   object_get(obj, "outputMode", &an->cg_output_mode, INT, 1, "2");
+   object_get(obj, "nfiles", &an->cg_nfiles, INT, 1, "0");
+   object_get(obj, "smearRadius", &an->smear_radius, WITH_UNITS, 1, "0", "l", NULL);
+   object_get(obj, "smearMethod", &an->cg_smear_string, STRING, 1, "impulse");
+   if (!an->cg_smear_string) an->cg_smear_string = strdup("");
+   an->smear_method = strcasecmp(an->cg_smear_string, "hat") == 0;      /* anything else is impulse */
+   if (an->cg_n[0] < 1 || an->cg_n[1] < 1 || an->cg_n[2] < 1)
+      snprintf(msg, msglen, "ANALYSIS %s: nx = %d, ny = %d, nz = %d: each must be at least 1", an->name, an->cg_n[0], an->cg_n[1], an->cg_n[2]);
+   else if (!object_testforkeyword(obj, "field_units")) snprintf(msg, msglen, "ANALYSIS %s: no field_units key", an->name);
+   else if (an->cg_output_mode < 1 || an->cg_output_mode > 3) snprintf(msg, msglen, "ANALYSIS %s: outputMode = %d (1, 2 or 3)", an->name, an->cg_output_mode);
+   else if (!isfinite(an->smear_radius)) snprintf(msg, msglen, "ANALYSIS %s: smearRadius = %g: not finite", an->name, an->smear_radius);
+   else if ((double)an->cg_n[0] * an->cg_n[1] * an->cg_n[2] > (double)DDCMI_CG_MAX_KEYS)
+      snprintf(msg, msglen, "ANALYSIS %s: %d x %d x %d cells, the device takes at most %d keys", an->name, an->cg_n[0], an->cg_n[1], an->cg_n[2], DDCMI_CG_MAX_KEYS);
+}
+static void *cg_init(SIMULATE *simulate, const ddcmi_analysis *an)
+{
+   const ddcmi_setup *s = simulate->setup;
+   CGSTATE *p = zalloc(1, sizeof(CGSTATE));
+   size_t len = 256 + strlen(an->cg_smear_string);
+   for (int j = 0; j < s->nspecies; j++) len += strlen(s->species_name[j]) + 1;
+   p->info = zalloc(len, 1);
+   snprintf(p->info, len, "nx = %d; ny = %d; nz=%d; smearRadius=%f; smearMethod=%s;\n       ouputrate=%d; eval_rate=%d; species=", an->cg_n[0], an->cg_n[1], an->cg_n[2],
+            units_convert(an->smear_radius, NULL, "l"), an->cg_smear_string, an->outputrate, an->eval_rate);      /* (the reference's spelling) */
+   for (int j = 0; j < s->nspecies; j++) { strcat(p->info, " "); strcat(p->info, s->species_name[j]); }
+   strcat(p->info, ";");
+   return p;
+}
+static void cg_clear(SIMULATE *simulate, const ddcmi_analysis *an, void *state) { (void)simulate; (void)an; CGSTATE *p = state; p->n = 0; p->nsteps = 0; }
+static int cg_less(const ddcmi_cg_record *a, const ddcmi_cg_record *b) { return a->label < b->label || (a->label == b->label && a->species < b->species); }
+/* tab[n] += add[m], both ascending in (label, species); an entry of both is tab's plus add's, field by field */
+static void cg_merge(CGSTATE *p, const ddcmi_cg_record *add, int64_t m)
+{
+   if (m <= 0) return;
+   ddcmi_cg_record *out = zalloc((size_t)(p->n + m), sizeof(ddcmi_cg_record));
+   int64_t i = 0, j = 0, k = 0;
+   while (i < p->n || j < m)
+   {
+      if (j >= m || (i < p->n && cg_less(&p->tab[i], &add[j]))) out[k++] = p->tab[i++];
+      else if (i >= p->n || cg_less(&add[j], &p->tab[i])) out[k++] = add[j++];
+      else
+      {
+         ddcmi_cg_record r = p->tab[i++];
+         const ddcmi_cg_record *o = &add[j++];
+         r.n += o->n; r.mass += o->mass;
+         for (int a = 0; a < 3; a++) { r.K[a] += o->K[a]; r.p[a] += o->p[a]; }
+         out[k++] = r;
+      }
+   }
+   free(p->tab);
+   p->tab = out; p->n = k; p->cap = k;
+}
+static void cg_eval(SIMULATE *simulate, const ddcmi_analysis *an, void *state)
+{
+   CGSTATE *p = state;
+   ddcmi_ctx *ctx = simulate->accelerator->parms;
+   const char *where = "coarsegrain_eval";
+   const int ns = simulate->setup->nspecies;
+   int64_t n = 0, got = 0;
+   if (ddcmi_coarsegrain(ctx, an->cg_n[0], an->cg_n[1], an->cg_n[2], ns, an->smear_radius, an->smear_method, 0, NULL, &n) != DDCMI_OK) die(where, ddcmi_last_error(ctx));
+   p->nsteps++;
+   if (n <= 0) return;
+   ddcmi_cg_record *rec = zalloc((size_t)n, sizeof(ddcmi_cg_record));
+   if (ddcmi_coarsegrain(ctx, an->cg_n[0], an->cg_n[1], an->cg_n[2], ns, an->smear_radius, an->smear_method, n, rec, &got) != DDCMI_OK) die(where, ddcmi_last_error(ctx));
+   if (got != n) die(where, "the grid held another number of entries the second time");
+   cg_merge(p, rec, n);
+   free(rec);
+}
+static int cg_field_size(uint64_t max) { int b = 1; while (b < 8 && (max >> (8 * b)) != 0) b++; return b; }      /* bFieldSize */
+static void cg_pack_b(unsigned char *dst, int size, uint64_t v) { for (int k = 0; k < size; k++) dst[k] = (unsigned char)(v >> (8 * (size - 1 - k))); }
+static void cg_output(SIMULATE *simulate, const ddcmi_analysis *an, void *state)
+{
+   CGSTATE *p = state;
+   ddcmi_ctx *ctx = simulate->accelerator->parms;
+   const ddcmi_setup *s = simulate->setup;
+   const char *where = "coarsegrain_output";
+   /* the ranks' tables on rank 0, one block behind the other in rank order */
+   const int64_t n = p->n;
+   int64_t *cnt = zalloc(par.world, sizeof(int64_t));
+   cnt[0] = n;
+   if (par.world > 1 && ddcmi_rdzv_allgather(par.rdzv, &n, cnt, sizeof(int64_t)) != DDCMI_OK) die(where, ddcmi_rdzv_last_error(par.rdzv));
+   if (par.world > 1 && par.rank != 0)
+   {
+      const int peer = 0; const void *sb = p->tab; const size_t sbytes = sizeof(ddcmi_cg_record) * (size_t)n;
+      if (ddcmi_rdzv_exchange(par.rdzv, n > 0 ? 1 : 0, &peer, &sb, &sbytes, 0, NULL, NULL, NULL) != DDCMI_OK) die(where, ddcmi_rdzv_last_error(par.rdzv));
+   }
+   else if (par.world > 1)
+   {
+      int64_t tot = 0;
+      for (int r = 1; r < par.world; r++) tot += cnt[r];
+      ddcmi_cg_record *rec = zalloc((size_t)tot + 1, sizeof(ddcmi_cg_record));
+      int *peer = zalloc(par.world, sizeof(int)); void **rb = zalloc(par.world, sizeof(void *)); size_t *rbytes = zalloc(par.world, sizeof(size_t));
+      int nr = 0; size_t off = 0;
+      for (int r = 1; r < par.world; r++)
+      {
+         if (cnt[r] > 0) { peer[nr] = r; rb[nr] = rec + off; rbytes[nr] = sizeof(ddcmi_cg_record) * (size_t)cnt[r]; nr++; }
+         off += (size_t)cnt[r];
+      }
+      if (ddcmi_rdzv_exchange(par.rdzv, 0, NULL, NULL, NULL, nr, peer, rb, rbytes) != DDCMI_OK) die(where, ddcmi_rdzv_last_error(par.rdzv));
+      off = 0;
+      for (int r = 1; r < par.world; r++) { cg_merge(p, rec + off, cnt[r]); off += (size_t)cnt[r]; }      /* rank order */
+      free(peer); free(rb); free(rbytes); free(rec);
+   }
+   if (par.rank == 0)
+   {
+      const int mode = an->cg_output_mode, nf4 = mode == 1 ? 10 : 16, nfields = nf4 + 3;      /* the f4 fields behind checksum, label and species_index */
+      const int lb = cg_field_size((uint64_t)an->cg_n[0] * an->cg_n[1] * an->cg_n[2] - 1), sb = cg_field_size((uint64_t)s->nspecies - 1);
+      const int lrec = 4 + lb + sb + 4 * nf4;
+      char name[700], tmpname[720], dir[512], path[1300], tmppath[1300];
+      snprintf(name, sizeof(name), "%s#000000", an->filename);
+      snprintf(tmpname, sizeof(tmpname), "%s.tmp", name);
+      FILE *f = snapshot_fopen(simulate, tmpname, where);
+      time_t now = time(NULL);
+      char stamp[64];
+      strftime(stamp, sizeof(stamp), "%Y-%m-%d-%H:%M:%S", localtime(&now));
+      int key;
+      memcpy(&key, "1234", 4);
+      double h[9];
+      if (ddcmi_get_box(ctx, h) != DDCMI_OK) die(where, ddcmi_last_error(ctx));
+      const double cLen = units_convert(1.0, NULL, "l");
+      /* write_fileheader */
+      fprintf(f, "cgrid FILEHEADER {type=MULTILINE; datatype=FIXRECORDBINARY; checksum=CRC32; create_time=%s; run_id=0x%08x;\n", stamp, 0u);
+      fprintf(f, "code_version=%s; srcpath=libddcmi;\n", ddcmi_version());
+      fprintf(f, "loop=%" PRId64 "; time=%f fs;\n", simulate->loop, units_convert(simulate->time, NULL, "t"));
+      fprintf(f, "nfiles=1; nrecord=%" PRIu64 "; lrec=%d; nfields=%d; endian_key=%d;\n", (uint64_t)p->n, lrec, nfields, key);
+      if (mode == 1)
+      {
+         fprintf(f, "field_names=checksum label species_index number_particles mass  Kx Ky Kz U virial px py pz;\n");
+         fprintf(f, "field_types=u4 b%1u b%1u f4 f4 f4 f4 f4 f4 f4 f4 f4 f4;\n", (unsigned)lb, (unsigned)sb);
+         fprintf(f, "field_units=1 1 1 1 amu eV eV eV eV eV amu*Angstrom/fs amu*Angstrom/fs amu*Angstrom/fs;\n");
+      }
+      else
+      {
+         fprintf(f, "field_names=checksum label species_index number_particles mass  Kx Ky Kz U virial px py pz vir_xx vir_yy vir_zz vir_xy vir_xz vir_yz;\n");
+         fprintf(f, "field_types=u4 b%1u b%1u f4 f4 f4 f4 f4 f4 f4 f4 f4 f4 f4 f4 f4 f4 f4 f4;\n", (unsigned)lb, (unsigned)sb);
+         fprintf(f, "field_units=1 1 1 1 amu eV eV eV eV eV amu*Angstrom/fs amu*Angstrom/fs amu*Angstrom/fs eV eV eV eV eV eV;\n");
+      }
+      fprintf(f, "reducedcorner=%21.14f %21.14f %21.14f;\n", -0.5, -0.5, -0.5);
+      fprintf(f, "h=%21.14f %21.14f %21.14f\n  %21.14f %21.14f %21.14f\n  %21.14f %21.14f %21.14f Ang;\n",
+              h[0] * cLen, h[1] * cLen, h[2] * cLen, h[3] * cLen, h[4] * cLen, h[5] * cLen, h[6] * cLen, h[7] * cLen, h[8] * cLen);
+      fprintf(f, "%s\n  nSamples = %d;\n", p->info, p->nsteps);
+      fprintf(f, "}\n \n\n");
+      const double mass_convert = units_convert(1.0, NULL, "amu"), energy_convert = units_convert(1.0, NULL, "eV");
+      const double momentum_convert = units_convert(1.0, NULL, "amu*Angstrom/fs");
+      const double nstepsInv = 1.0 / (p->nsteps * 1.0);
+      unsigned char *line = zalloc((size_t)lrec, 1);
+      for (int64_t k = 0; k < p->n; k++)
+      {
+         const ddcmi_cg_record *e = &p->tab[k];
+         float v[16];
+         int q = 0;
+         memset(v, 0, sizeof(v));
+         v[q++] = (float)(e->n * nstepsInv);
+         v[q++] = (float)(e->mass * mass_convert * nstepsInv);
+         for (int a = 0; a < 3; a++) v[q++] = (float)(e->K[a] * energy_convert * nstepsInv);
+         q += 2;      /* U, virial */
+         for (int a = 0; a < 3; a++) v[q++] = (float)(e->p[a] * momentum_convert * nstepsInv);
+         cg_pack_b(line + 4, lb, (uint64_t)e->label);
+         cg_pack_b(line + 4 + lb, sb, (uint64_t)e->species);
+         memcpy(line + 4 + lb + sb, v, 4 * (size_t)nf4);
+         const uint32_t crc = ddcmi_crc32(line + 4, (size_t)lrec - 4);
+         memcpy(line, &crc, 4);
+         if (fwrite(line, (size_t)lrec, 1, f) != 1) die(where, "cannot write the records");
+      }
+      free(line);
+      if (fclose(f) != 0) die(where, "cannot write the output file");
+      snprintf(dir, sizeof(dir), "snapshot.%012" PRId64, simulate->loop);
+      snprintf(path, sizeof(path), "%s/%s", dir, name);
+      snprintf(tmppath, sizeof(tmppath), "%s/%s", dir, tmpname);
+      if (rename(tmppath, path) != 0) die(where, "cannot rename the output file");
+   }
+   free(cnt);
+   cg_clear(simulate, an, p);
+}
+static void cg_free(void *state) { CGSTATE *p = state; free(p->tab); free(p->info); free(p); }
+
 /* ------------------------------------------------------------------------- */
 static const char *const dsf_heads[] = {"DynamicStructureFactor", "Dynamic_Structure_Factor", NULL};
 static const ANALYSIS_TYPE types[] = {      /* indexed by enum ddcmi_analysis_kind; DDCMI_AN_NONE has no row */
@@ -808,6 +1003,7 @@ static const ANALYSIS_TYPE types[] = {      /* indexed by enum ddcmi_analysis_ki
    [DDCMI_AN_KDIST] = {"KINETICENERGYDISTN", DDCMI_AN_KDIST, "kinetic.data", kd_parms, kd_init, kd_eval, kd_output, kd_clear, kd_free},
    [DDCMI_AN_DSF] = {"DSF", DDCMI_AN_DSF, "rho_k.data", dsf_parms, dsf_init, dsf_eval, dsf_output, NULL, dsf_free, 0, NULL, dsf_heads},
    [DDCMI_AN_SUBSETWRITE] = {"subsetWrite", DDCMI_AN_SUBSETWRITE, "subset", sw_parms, sw_init, sw_eval, sw_output, NULL, sw_free, 1, "subset_write"},
+   [DDCMI_AN_COARSEGRAIN] = {"COARSEGRAIN", DDCMI_AN_COARSEGRAIN, "cgrid", cg_parms, cg_init, cg_eval, cg_output, cg_clear, cg_free},
 };
 const ANALYSIS_TYPE *analysis_type_find(const char *type_name)
 {

@@ -566,6 +566,14 @@ ddcmi_setup *ddcmi_deck_load_with(const char *object_file, const char *restart_f
                if (!format || strcmp(format, "binaryCharmm") != 0) row = NULL;
                free(format);
             }
+            if (row && row->type == DDCMI_AN_COARSEGRAIN)
+            {
+               /* COARSEGRAIN with outputMode = 3 (E = f / q, ESpotential) divides by the species' charge, zero for most Martini beads:
+                * such an object stays unsupported */
+               int mode = 2;
+               object_get(ao, "outputMode", &mode, INT, 1, "2");
+               if (mode == 3) row = NULL;
+            }
             if (!row) continue;
             an->type = row->type;
             an->filename = get_string(ao, "filename", row->filename);
@@ -800,6 +808,16 @@ ddcmi_setup *ddcmi_deck_load_with(const char *object_file, const char *restart_f
          int found = 0;
          for (int i = 0; i < s->nspecies; i++) found |= strcmp(an->dsf_species, s->species_name[i]) == 0;
          if (!found) FAIL("ANALYSIS %s: species = %s, and the system has no species of that name", an->name, an->dsf_species);
+      }
+      /* ANALYSIS COARSEGRAIN: its (cell, species) keys fit the device's sort key */
+      for (int a = 0; a < s->nanalysis; a++)
+      {
+         const ddcmi_analysis *an = &s->analysis[a];
+         if (an->type != DDCMI_AN_COARSEGRAIN) continue;
+         const double nkeys = (double)an->cg_n[0] * an->cg_n[1] * an->cg_n[2] * s->nspecies;
+         if (nkeys > (double)DDCMI_CG_MAX_KEYS)
+            FAIL("ANALYSIS %s: %d x %d x %d cells x %d species = %.0f keys, the device takes at most %d", an->name, an->cg_n[0], an->cg_n[1], an->cg_n[2], s->nspecies,
+                 nkeys, DDCMI_CG_MAX_KEYS);
       }
       /* ANALYSIS subsetWrite: its species are the system's (species_find returns NULL and the reference dereferences it,
        * subsetWrite.c:101-102); the bounds the deck leaves out (subsetWrite.c:119-139); the pinfo field (its assert, :419) */
@@ -1137,7 +1155,7 @@ void ddcmi_setup_free(ddcmi_setup *s)
       for (int g = 0; g < an->ndist; g++) { free(an->dist[g].name); free(an->dist[g].species); }
       free(an->dist); free(an->name); free(an->type_name); free(an->filename); free(an->m); free(an->dsf_species);
       for (int k = 0; k < an->sw_nspecies; k++) free(an->sw_species[k]);
-      free(an->sw_species); free(an->sw_idlist); free(an->sw_length_unit);
+      free(an->sw_species); free(an->sw_idlist); free(an->sw_length_unit); free(an->cg_smear_string);
    }
    free(s->analysis);
    free(s->u_pressure); free(s->u_volume); free(s->u_temperature); free(s->u_energy); free(s->u_time); free(s->u_length);

@@ -19,7 +19,7 @@ enum { DDCMI_GROUP_FREE = 0, DDCMI_GROUP_BERENDSEN = 1, DDCMI_GROUP_LANGEVIN = 2
 
 /* one ANALYSIS object (analysis_init, analysis.c:120-160).  type: the row of host/analysis.c's table that evaluates it; DDCMI_AN_NONE is any
  * other type (not supported: the driver names it once on stderr) */
-enum ddcmi_analysis_kind { DDCMI_AN_NONE = 0, DDCMI_AN_PAIRCORRELATION, DDCMI_AN_VAF, DDCMI_AN_VCMWRITE, DDCMI_AN_ZDENSITY, DDCMI_AN_KDIST, DDCMI_AN_DSF, DDCMI_AN_SUBSETWRITE };
+enum ddcmi_analysis_kind { DDCMI_AN_NONE = 0, DDCMI_AN_PAIRCORRELATION, DDCMI_AN_VAF, DDCMI_AN_VCMWRITE, DDCMI_AN_ZDENSITY, DDCMI_AN_KDIST, DDCMI_AN_DSF, DDCMI_AN_SUBSETWRITE, DDCMI_AN_COARSEGRAIN };
 /* one BIN object of a KINETICENERGYDISTN analysis (kineticEnergyDistn.c:58-83): the histogram of one species' kinetic energies */
 typedef struct ddcmi_kdist_group { char *name, *species; double emin, emax; int nbins; } ddcmi_kdist_group;      /* internal energy units; nbins >= 1, emax > emin */
 typedef struct ddcmi_analysis
@@ -49,6 +49,11 @@ typedef struct ddcmi_analysis
    char **sw_species;
    double sw_rmin[3], sw_rmax[3], sw_vmin[3], sw_vmax[3];
    int sw_given;                /* bit 2 a + q of x, y, z and 6 + 2 a + q of vx, vy, vz: the deck has the key (q = 0 min, 1 max) */
+   /* from here on COARSEGRAIN only (coarsegrain.c:80-119), zero otherwise; its smearRadius / smearMethod are smear_radius / smear_method above */
+   int cg_n[3];                 /* nx, ny, nz: each >= 1 */
+   int cg_output_mode;          /* outputMode 1 (13 fields) or 2 (19 fields, the default); an object with 3 stays unsupported */
+   int cg_nfiles;               /* nfiles is read and ignored: one file */
+   char *cg_smear_string;       /* smearMethod as the deck spells it (the file's misc_info echoes it) */
 } ddcmi_analysis;
 
 typedef struct ddcmi_setup

@@ -181,7 +181,7 @@ def load_deck(object_file, restart_file=None, extra_objects=None):
         s.integrator_type = c.integrator_type.decode()
         s.accelerator_type = c.accelerator_type.decode()
         s.units = {k: getattr(c, "u_" + k).decode() for k in ("pressure", "volume", "temperature", "energy", "time", "length")}
-        # SIMULATE analysis = ...: one dict per ANALYSIS object, in list order (types PAIRCORRELATION, VELOCITYAUTOCORRELATION, vcmWrite, zdensity, KINETICENERGYDISTN, DSF and subsetWrite with format = binaryCharmm, with their parameters, internal units)
+        # SIMULATE analysis = ...: one dict per ANALYSIS object, in list order (types PAIRCORRELATION, VELOCITYAUTOCORRELATION, vcmWrite, zdensity, KINETICENERGYDISTN, DSF, subsetWrite with format = binaryCharmm and COARSEGRAIN with outputMode 1 or 2, with their parameters, internal units)
         s.analysis = []
         for a in (c.analysis[i] for i in range(int(c.nanalysis))):
             d = {"name": a.name.decode(), "type": (a.type_name or b"").decode(), "eval_rate": int(a.eval_rate), "outputrate": int(a.outputrate),
@@ -204,6 +204,9 @@ def load_deck(object_file, restart_file=None, extra_objects=None):
                          id_list=[int(a.sw_idlist[k]) for k in range(int(a.sw_nid))] if a.sw_idlist else None,
                          species=[a.sw_species[k].decode() for k in range(int(a.sw_nspecies))] or None,
                          rmin=list(a.sw_rmin), rmax=list(a.sw_rmax), vmin=list(a.sw_vmin), vmax=list(a.sw_vmax))
+            if a.type == _lib.AN_COARSEGRAIN:      # outputMode 1 or 2; smear_radius in internal units
+                d.update(nx=int(a.cg_n[0]), ny=int(a.cg_n[1]), nz=int(a.cg_n[2]), output_mode=int(a.cg_output_mode), nfiles=int(a.cg_nfiles),
+                         smear_radius=float(a.smear_radius), smear_method=("impulse", "hat")[a.smear_method])
             s.analysis.append(d)
     finally:
         lib.ddcmi_setup_free(p)

@@ -57,6 +57,7 @@ def _dsf_args(nspecies, mmax, select, nrank=1):
 
 
 SUBSET_RECORD = np.dtype([("id", "<u8"), ("pinfo", "<u4"), ("r", "<f4", (3,))])      # struct ddcmi_subset_record: 24 bytes, the file's record
+CG_RECORD = np.dtype([("label", "<i8"), ("species", "<i4"), ("pad", "<i4"), ("n", "<f8"), ("mass", "<f8"), ("K", "<f8", (3,)), ("p", "<f8", (3,))])      # struct ddcmi_cg_record: 80 bytes
 GID_MAX = 2 ** 64 - 1
 
 
@@ -181,6 +182,7 @@ def _declare(lib):
     lib.ddcmi_kinetic_energy_distn.argtypes = [vp, ctypes.c_int, ctypes.c_int, _dp, _dp, _ip, _ip, _lp, _lp, _dp]
     lib.ddcmi_charge_density_modes.argtypes = [vp, ctypes.c_int, _ip, ctypes.c_int, _dp, _lp]
     lib.ddcmi_subset_records.argtypes = [vp, ctypes.POINTER(CSubsetFilter), ctypes.c_int64, vp, _lp]
+    lib.ddcmi_coarsegrain.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int64, vp, _lp]
     lib._ddcmi_declared = True
 
 
@@ -686,6 +688,20 @@ class MartiniHIP(object):
         del keep
         return rec[:int(n[0])]
 
+    def coarsegrain(self, nx, ny, nz, smear_radius=0.0, smear_method="impulse", count_only=False, cap=None, out=None):
+        """ANALYSIS COARSEGRAIN, one evaluation of this rank (ddcmi_coarsegrain): the non-empty (label, species) entries in ascending
+        order as a structured array of CG_RECORD (label, species, n, mass, K[3], p[3]; internal units), label = igz + nz (igy + ny igx);
+        smear_radius in internal length units (<= 0: one cell per bead), smear_method "impulse" or "hat" (anything else is impulse).
+        count_only: the count alone.  cap / out: the capacity handed down (default: the count) and the array the records land in."""
+        a = (int(nx), int(ny), int(nz), int(self.s.nspecies), float(smear_radius), _smear_method(smear_method))
+        n = np.zeros(1, np.int64)
+        self._chk(self.lib.ddcmi_coarsegrain(self.ctx, *a, 0, None, n.ctypes.data_as(_lp)))
+        if count_only:
+            return int(n[0])
+        rec = np.zeros(int(n[0]), CG_RECORD) if out is None else out
+        self._chk(self.lib.ddcmi_coarsegrain(self.ctx, *a, int(n[0]) if cap is None else int(cap), rec.ctypes.data_as(ctypes.c_void_p), n.ctypes.data_as(_lp)))
+        return rec[:int(n[0])]
+
     def download(self, mask=POS | VEL | FORCE):
         n = self.n
         out = [np.zeros(n) for _ in range(9)]
@@ -780,6 +796,8 @@ def _declare_domains(lib):
     lib.ddcmi_group_kinetic_energy_distn.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _ip, _ip, _lp, _lp, _dp]
     lib.ddcmi_group_charge_density_modes.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int, _ip, ctypes.c_int, _dp, _lp]
     lib.ddcmi_group_subset_records.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.POINTER(CSubsetFilter), ctypes.c_int64, vp, _lp]
+    lib.ddcmi_group_coarsegrain.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int,
+                                            ctypes.c_int64, vp, _lp]
     lib._ddcmi_dom_declared = True
 
 
@@ -1010,6 +1028,21 @@ class MartiniGroup(object):
         self._chk(self.lib.ddcmi_group_subset_records(self.arr, self.n, ctypes.byref(f), tot if cap is None else int(cap), rec.ctypes.data_as(ctypes.c_void_p), n.ctypes.data_as(_lp)))
         del keep
         return (rec[:tot], n) if per_rank else rec[:tot]
+
+    def coarsegrain(self, nx, ny, nz, smear_radius=0.0, smear_method="impulse", per_rank=False, cap=None, out=None):
+        """ddcmi_group_coarsegrain: the domains' entries merged by (label, species) in rank order, duplicate keys added -- or, per_rank,
+        (records one block behind the other in rank order, count[rank])"""
+        a = (int(nx), int(ny), int(nz), int(self.s.nspecies), float(smear_radius), _smear_method(smear_method))
+        n = np.zeros(self.n, np.int64)
+        self._chk(self.lib.ddcmi_group_coarsegrain(self.arr, self.n, *a, 0, None, n.ctypes.data_as(_lp)))
+        tot = int(n.sum())
+        rec = np.zeros(tot, CG_RECORD) if out is None else out
+        self._chk(self.lib.ddcmi_group_coarsegrain(self.arr, self.n, *a, tot if cap is None else int(cap), rec.ctypes.data_as(ctypes.c_void_p), n.ctypes.data_as(_lp)))
+        if per_rank:
+            return rec[:tot], n
+        from .analysis import merge_cg_records
+        off = np.concatenate([[0], np.cumsum(n)])
+        return merge_cg_records([rec[off[r]:off[r + 1]] for r in range(self.n)])
 
     def energies(self):
         """sum over ranks = energyInfo.c allreduce()"""

@@ -332,6 +332,26 @@ typedef struct ddcmi_subset_filter
 } ddcmi_subset_filter;
 typedef struct ddcmi_subset_record { uint64_t gid; uint32_t pinfo; float r[3]; } ddcmi_subset_record;      /* 24 bytes: the file's record */
 int ddcmi_subset_records(ddcmi_ctx *ctx, const ddcmi_subset_filter *filter, int64_t cap, ddcmi_subset_record *rec, int64_t *count);
+/* ANALYSIS COARSEGRAIN on the device (coarsegrain.c:242-448, coarsegrain_eval): one evaluation's sums over this rank's owned beads per
+ * (grid cell, species) of an nx x ny x nz grid of the orthorhombic box, in one read-only pass under the rules above, as the non-empty
+ * entries in ascending (label, species) order; label = igz + nz (igy + ny igx).  Internal units: n the sum of the weights, mass of
+ * weight m, K[a] of weight 0.5 m v_a v_a, p[a] of weight m v_a; m is the species' mass of ddcmi_set_species.  smear_radius <= 0: the
+ * one cell (int)r_a per axis, r_a = x_a (n_a / L_a) - corner_a (n_a / L_a), weight 1.  Otherwise the reference's two cells per axis
+ * (floor(r_a + 0.5) - 1 and floor(r_a + 0.5), -1 -> n_a - 1 and n_a -> 0 on every axis, open ones too), lSmear = min(2 smear_radius,
+ * L_a / n_a), weights by smear_method 0 (impulse) or 1 (hat), corner weight (wx wy) wz, corners below 1e-20 skipped.  Positions are
+ * those a download returns (wrapped).  Where the reference runs off its grid, a cell index outside [0, n_a) is clamped into it (a
+ * bead on the upper face, a NaN: cell 0).  U, virial and the virial tensor of the reference's record are zero on the Martini path and
+ * are not computed.  Every sum is added in an order that depends only on the set of contributions (stable radix sort by key, then a
+ * segmented reduction whose association depends only on the segment's length): no floating-point atomics, identical bytes when repeated.
+ * *count: this rank's entries, always.  rec NULL: nothing else.  Otherwise the records, cap their room: cap < *count is DDCMI_EINVAL
+ * and leaves rec untouched.  The records are formed in a device buffer of the context and copied once.  Over ranks, merge by key.
+ * Refused: n_a < 1, an nspecies that is not the context's, no state or no box, a smear_method other than 0 or 1, a smear_radius that is
+ * not finite (DDCMI_EINVAL); a box that is not orthorhombic, nx ny nz nspecies > DDCMI_CG_MAX_KEYS (DDCMI_EUNSUPPORTED).  A domain
+ * that holds no bead gives count 0. [sync] */
+#define DDCMI_CG_MAX_KEYS (1 << 28)      /* bounds the sort key label * nspecies + species and the sentinel one above it: 32 bits hold it, four 8-bit passes sort it */
+typedef struct ddcmi_cg_record { int64_t label; int32_t species; int32_t pad; double n, mass, K[3], p[3]; } ddcmi_cg_record;      /* 80 bytes */
+int ddcmi_coarsegrain(ddcmi_ctx *ctx, int nx, int ny, int nz, int nspecies, double smear_radius, int smear_method, int64_t cap, ddcmi_cg_record *rec,
+                      int64_t *count);
 
 /* ---- introspection / measurement ------------------------------------------- */
 /* list statistics of the last build: stats[0]=stored full-list entries,

@@ -74,6 +74,10 @@ int ddcmi_group_charge_density_modes(ddcmi_ctx **ctxs, int n, int nspecies, cons
 /* ddcmi_subset_records for an in-process group: count[r] of every domain r; with rec, the domains' records one block behind the
  * other in rank order, cap the room for all of them (too small: DDCMI_EINVAL, the counts set, rec untouched) */
 int ddcmi_group_subset_records(ddcmi_ctx **ctxs, int n, const ddcmi_subset_filter *filter, int64_t cap, ddcmi_subset_record *rec, int64_t *count);
+/* ddcmi_coarsegrain for an in-process group: count[r] of every domain r; with rec, the domains' records one block behind the other in
+ * rank order, cap the room for all of them (too small: DDCMI_EINVAL, the counts set, rec untouched) */
+int ddcmi_group_coarsegrain(ddcmi_ctx **ctxs, int n, int nx, int ny, int nz, int nspecies, double smear_radius, int smear_method, int64_t cap,
+                            ddcmi_cg_record *rec, int64_t *count);
 /* the lean step (a single domain of FREE beads without bonded terms: one launch per step, the second stage of its energy / virial /
  * kinetic sums formed for all pending steps at once): the sums of the steps of the last such launch, 32 doubles per step --
  * {lj, ele, virial xx yy zz xy xz yz} as the full list counts them (twice), {rk, tion xx yy zz xy xz yz}, 0, the bonded kernels'
