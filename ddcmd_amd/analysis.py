@@ -9,6 +9,8 @@ KineticEnergyDistn: the accumulation and the two files of kineticEnergyDistn.c f
 (Martini*.kinetic_energy_distn).
 DynamicStructureFactor: the wave vectors, the buffer and the file text of dsf.c from the device's charge-density modes
 (Martini*.charge_density_modes).
+StaticStructureFactor: the wave vectors of ssf_kvector, their four sign combinations, S(k) and the lines of ssf_eval (ssf.c) from the
+device's density modes (Martini*.structure_modes); in_plane lists the (n_x, n_y, 0) of an undulation spectrum.
 SubsetWrite: the pinfo tables of pinfo.c, the header of write_fileheader (io.c) and the file of subsetWriteBinaryCharmm
 (subsetWrite.c) around the device's packed records (Martini*.subset_records); read_subset reads such a file back.
 CoarseGrain: the table keyed by (label, species) that accumulates the device's evaluations (Martini*.coarsegrain) and the cgrid file
@@ -434,6 +436,82 @@ def parse_dsf_output(text):
     loop = np.array([int(r[0]) for r in rows], np.int64)
     val = np.array([[float(x) for x in r[1:]] for r in rows], np.float64).reshape(len(rows), -1)
     return loop, val[:, 0], val[:, 1::2] + 1j * val[:, 2::2]
+
+
+SSF_SIGNS = ((1, 1, 1), (1, 1, -1), (1, -1, 1), (1, -1, -1))      # ssf_eval's ppp, ppm, pmp, pmm
+SSF_FACT = (1.0, 0.5, 0.25)                                        # by the number of zero components: how often the four coincide
+
+
+def expand_signs(n):
+    """the signed triples of the vectors n[nv, 3] in ssf_eval's four combinations: [4 nv, 3] int32, vector after vector, +++ ++- +-+ +-- each"""
+    n = np.asarray(n, np.int32).reshape(-1, 3)
+    return (n[:, None, :] * np.array(SSF_SIGNS, np.int32)[None, :, :]).reshape(-1, 3)
+
+
+def in_plane(nmax):
+    """the wave vectors (n_x, n_y, 0), 0 <= n_x, n_y <= nmax without (0, 0, 0), n_x slowest, of a bilayer's undulation spectrum: [(nmax + 1)^2 - 1, 3]
+    int32.  expand_signs gives the signed list for Martini*.structure_modes (every vector four times: its two in-plane signs, each twice)."""
+    nmax = int(nmax)
+    if nmax < 1:
+        raise ValueError("nmax = %d: at least 1" % nmax)
+    return np.array([(nx, ny, 0) for nx in range(nmax + 1) for ny in range(nmax + 1) if nx or ny], np.int32)
+
+
+class StaticStructureFactor(object):
+    """one SSF analysis (ssf.c) in an orthorhombic box h (the nine entries, internal length) with kmax a bare number in internal inverse
+    length, as the reference reads it.  n[nv, 3]: ssf_kvector's list in its order -- n_a runs over [0, (int)(kmax L_a / 2 pi)), n_x slowest; the
+    first n_z with k^2 >= kmax^2 ends its n_z loop; a vector is kept if k^2 < kmax^2 / 2 and it is not (0,0,0).  kvec[4 nv, 3]: the signed
+    triples Martini*.structure_modes takes (expand_signs).  Sk(rho) is fact[zeros] times the sum of |rho|^2 over a vector's four combinations,
+    rho added over the ranks; lines(rho) the text ssf_eval prints.  (The reference's evaluation ends the program; the deck word SSF stays
+    unsupported.)"""
+    in_plane = staticmethod(in_plane)
+
+    def __init__(self, h, kmax, species=None):
+        h = np.asarray(h, np.float64).reshape(3, 3)
+        if np.abs(h - np.diag(np.diag(h))).max() > 1e-10 or not np.all(np.diag(h) > 0.0):
+            raise ValueError("only orthorhombic boxes are supported")
+        self.kmax, self.species = float(kmax), species
+        self.kbasis = 2.0 * np.pi / np.diag(h)      # RECIP_LATTICEVECTORS of an orthorhombic box: one component each
+        # kDirectionMax: 1 / |b_a| where the basis is orthogonal
+        nmax = [int(self.kmax * (1.0 / np.sqrt(b * b))) for b in self.kbasis]
+        kmax2, keep = self.kmax * self.kmax, []
+        for nx in range(nmax[0]):
+            for ny in range(nmax[1]):
+                for nz in range(nmax[2]):
+                    if self._k2((nx, ny, nz)) >= kmax2:
+                        break
+                    if (nx or ny or nz) and self._k2((nx, ny, nz)) < 0.5 * kmax2:
+                        keep.append((nx, ny, nz))
+        self.n = np.array(keep, np.int32).reshape(-1, 3)
+        self.kvec = expand_signs(self.n)
+        self.fact = np.array([SSF_FACT[int((v == 0).sum())] for v in self.n], np.float64)
+
+    def _k(self, n):
+        return tuple(float(n[a]) * self.kbasis[a] for a in range(3))
+
+    def _k2(self, n):
+        kx, ky, kz = self._k(n)
+        return kx * kx + ky * ky + kz * kz
+
+    def select(self, species_names):
+        """the select array of Martini*.structure_modes: None without a species"""
+        if self.species is None:
+            return None
+        if self.species not in list(species_names):
+            raise ValueError("species %s is not a species of the system" % self.species)
+        return np.array([int(s == self.species) for s in species_names], np.int32)
+
+    def Sk(self, rho):
+        """S_k[nv] from rho[4 nv] (Martini*.structure_modes(self.kvec), added over the ranks)"""
+        rho = np.asarray(rho, np.complex128).reshape(-1)
+        if len(rho) != 4 * len(self.n):
+            raise ValueError("%d values of rho for %d wave vectors in four sign combinations" % (len(rho), len(self.n)))
+        p = rho.reshape(-1, 4)
+        return self.fact * (p.real * p.real + p.imag * p.imag).sum(axis=1)
+
+    def lines(self, rho):
+        """ssf_eval's output: one line "k^2 k_x k_y k_z S_k" per wave vector"""
+        return "".join("%f %f %f %f %e\n" % ((self._k2(v),) + self._k(v) + (sk,)) for v, sk in zip(self.n, self.Sk(rho)))
 
 
 SUBSET_RECORD = np.dtype([("id", "<u8"), ("pinfo", "<u4"), ("r", "<f4", (3,))])      # a binaryCharmm record: 24 bytes

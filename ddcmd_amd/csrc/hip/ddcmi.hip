@@ -1405,5 +1405,6 @@ extern "C" int ddcmi_timing_fused(ddcmi_ctx *ctx, int64_t *launches, double *tot
 #include "ddcmi_census.inl"
 #include "ddcmi_kdist.inl"
 #include "ddcmi_dsf.inl"
+#include "ddcmi_ssf.inl"
 #include "ddcmi_subset.inl"
 #include "ddcmi_coarsegrain.inl"

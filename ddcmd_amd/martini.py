@@ -56,6 +56,25 @@ def _dsf_args(nspecies, mmax, select, nrank=1):
     return sel, np.zeros((nrank, 3, max(int(mmax), 1), 2)), np.zeros(nrank, np.int64)
 
 
+SM_WEIGHTS = {"unit": 0, "charge": 1}
+
+
+def _sm_args(nspecies, kvec, select, weight, nrank=1):
+    """the arrays ddcmi_structure_modes takes and fills: (select or None, weight 0 / 1, kvec int32 [nk, 3], rho[nrank, nk, 2], count[nrank])"""
+    sel = None
+    if select is not None:
+        sel = np.ascontiguousarray(np.asarray(select) != 0, np.int32).reshape(-1)
+        if len(sel) != int(nspecies):
+            raise ValueError("structure_modes: %d entries of select for %d species" % (len(sel), nspecies))
+    if weight not in SM_WEIGHTS:
+        raise ValueError("structure_modes: weight %r, one of %s" % (weight, sorted(SM_WEIGHTS)))
+    kv = np.asarray(kvec)
+    if kv.size % 3 or (kv.size and not np.issubdtype(kv.dtype, np.integer)) or (kv.size and np.abs(kv.astype(np.int64)).max() >= 2 ** 31):
+        raise ValueError("structure_modes: kvec must be integer triples (shape %s, dtype %s)" % (kv.shape, kv.dtype))
+    kv = np.ascontiguousarray(kv.reshape(-1, 3), np.int32)
+    return sel, SM_WEIGHTS[weight], kv, np.zeros((nrank, max(len(kv), 1), 2)), np.zeros(nrank, np.int64)
+
+
 SUBSET_RECORD = np.dtype([("id", "<u8"), ("pinfo", "<u4"), ("r", "<f4", (3,))])      # struct ddcmi_subset_record: 24 bytes, the file's record
 CG_RECORD = np.dtype([("label", "<i8"), ("species", "<i4"), ("pad", "<i4"), ("n", "<f8"), ("mass", "<f8"), ("K", "<f8", (3,)), ("p", "<f8", (3,))])      # struct ddcmi_cg_record: 80 bytes
 GID_MAX = 2 ** 64 - 1
@@ -181,6 +200,7 @@ def _declare(lib):
     lib.ddcmi_zdensity.argtypes = [vp, ctypes.c_int, ctypes.c_double, ctypes.c_int, _dp]
     lib.ddcmi_kinetic_energy_distn.argtypes = [vp, ctypes.c_int, ctypes.c_int, _dp, _dp, _ip, _ip, _lp, _lp, _dp]
     lib.ddcmi_charge_density_modes.argtypes = [vp, ctypes.c_int, _ip, ctypes.c_int, _dp, _lp]
+    lib.ddcmi_structure_modes.argtypes = [vp, ctypes.c_int, _ip, ctypes.c_int, ctypes.c_int, _ip, _dp, _lp]
     lib.ddcmi_subset_records.argtypes = [vp, ctypes.POINTER(CSubsetFilter), ctypes.c_int64, vp, _lp]
     lib.ddcmi_coarsegrain.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int64, vp, _lp]
     lib._ddcmi_declared = True
@@ -673,6 +693,14 @@ class MartiniHIP(object):
         self._chk(self.lib.ddcmi_charge_density_modes(self.ctx, int(self.s.nspecies), _i(sel), int(mmax), _d(rho), count.ctypes.data_as(_lp)))
         return rho[0, :, :, 0] + 1j * rho[0, :, :, 1], int(count[0])
 
+    def structure_modes(self, kvec, select=None, weight="unit"):
+        """ANALYSIS SSF's sums on any list of integer wave vectors, one evaluation of this rank (ddcmi_structure_modes): (rho complex128
+        [nk], count) -- rho[l] the sum of w exp(i 2 pi (n_x x / L_x + n_y y / L_y + n_z z / L_z)), (n_x, n_y, n_z) = kvec[l] (signed), over
+        the owned beads of the species select marks (None: all), count their number; weight "unit": w = 1, "charge": the species' charge"""
+        sel, w, kv, rho, count = _sm_args(self.s.nspecies, kvec, select, weight)
+        self._chk(self.lib.ddcmi_structure_modes(self.ctx, int(self.s.nspecies), _i(sel), w, len(kv), _i(kv), _d(rho), count.ctypes.data_as(_lp)))
+        return rho[0, :len(kv), 0] + 1j * rho[0, :len(kv), 1], int(count[0])
+
     def subset_records(self, count_only=False, cap=None, out=None, **filt):
         """ANALYSIS subsetWrite, format binaryCharmm: this rank's selected beads as the file's records (ddcmi_subset_records), a
         structured array of SUBSET_RECORD (id u8, pinfo u4, r 3 x f4) in the order of download_particles.  The filter's keywords are
@@ -795,6 +823,7 @@ def _declare_domains(lib):
     lib.ddcmi_group_zdensity.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, _dp]
     lib.ddcmi_group_kinetic_energy_distn.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _ip, _ip, _lp, _lp, _dp]
     lib.ddcmi_group_charge_density_modes.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int, _ip, ctypes.c_int, _dp, _lp]
+    lib.ddcmi_group_structure_modes.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int, _ip, ctypes.c_int, ctypes.c_int, _ip, _dp, _lp]
     lib.ddcmi_group_subset_records.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.POINTER(CSubsetFilter), ctypes.c_int64, vp, _lp]
     lib.ddcmi_group_coarsegrain.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int,
                                             ctypes.c_int64, vp, _lp]
@@ -1014,6 +1043,15 @@ class MartiniGroup(object):
         sel, rho, count = _dsf_args(self.s.nspecies, mmax, select, self.n)
         self._chk(self.lib.ddcmi_group_charge_density_modes(self.arr, self.n, int(self.s.nspecies), _i(sel), int(mmax), _d(rho), count.ctypes.data_as(_lp)))
         z = rho[..., 0] + 1j * rho[..., 1]
+        if per_rank:
+            return z, count
+        return self._sum_in_rank_order(z), int(count.sum())
+
+    def structure_modes(self, kvec, select=None, weight="unit", per_rank=False):
+        """ddcmi_group_structure_modes: the domains' (rho, count) added in rank order -- or, per_rank, stacked [rank, ...]"""
+        sel, w, kv, rho, count = _sm_args(self.s.nspecies, kvec, select, weight, self.n)
+        self._chk(self.lib.ddcmi_group_structure_modes(self.arr, self.n, int(self.s.nspecies), _i(sel), w, len(kv), _i(kv), _d(rho), count.ctypes.data_as(_lp)))
+        z = rho[:, :len(kv), 0] + 1j * rho[:, :len(kv), 1]
         if per_rank:
             return z, count
         return self._sum_in_rank_order(z), int(count.sum())

@@ -304,6 +304,19 @@ int ddcmi_kinetic_energy_distn(ddcmi_ctx *ctx, int nspecies, int ndist, const do
  * select without a member, gives zeros and count 0. [sync] */
 #define DDCMI_DSF_MAX_M 256
 int ddcmi_charge_density_modes(ddcmi_ctx *ctx, int nspecies, const int *select, int mmax, double *rho, int64_t *count);
+/* The density modes of ANALYSIS SSF (ssf.c:91-120) on any list of integer wave vectors, on the device, in one read-only pass under the
+ * rules above: rho[l] = {re, im} of sum w_j exp(i 2 pi (n_x x_j / L_x + n_y y_j / L_y + n_z z_j / L_z)), (n_x, n_y, n_z) = kvec[l] (signed),
+ * over the owned beads whose species is selected -- select[nspecies], nonzero: takes part; NULL: every species.  weight 0: w = 1 (ssf.c);
+ * weight 1: w the species' charge of ddcmi_set_species (DSF's weight).  *count: the selected owned beads.  Over ranks, add rho and the
+ * counts.  Positions and phase reduction are ddcmi_charge_density_modes': the position a download returns without a further wrap,
+ * t = r / L less its nearest integer, the phase n . t in turns less its nearest integer, one sincospi.  The value of a wave vector
+ * does not depend on the list: it has the same bits wherever it stands, whatever else the list holds (duplicates and (0,0,0) -- the
+ * sum of w -- included) and whatever nk is.  Orthorhombic boxes; 1 <= nk <= DDCMI_SM_MAX_K and |component| <= DDCMI_SM_MAX_N, above
+ * them DDCMI_EUNSUPPORTED.  nspecies must be the context's.  A domain that holds no bead, or a select without a member, gives zeros and
+ * count 0. [sync] */
+#define DDCMI_SM_MAX_N 1024
+#define DDCMI_SM_MAX_K 4096
+int ddcmi_structure_modes(ddcmi_ctx *ctx, int nspecies, const int *select, int weight, int nk, const int32_t *kvec, double *rho, int64_t *count);
 /* ANALYSIS subsetWrite, format binaryCharmm, on the device (subsetWrite.c:409-522): the owned beads a filter selects as the file's
  * 24-byte records, in one read-only pass under the rules above.  The filter is rejectParticle's (subsetWrite.c:532-564), in its order
  * and with its comparisons: a bead is dropped if gid < idmin, gid > idmax, gid % modulus != 0, odd and gid even, r_a > rmax[a] or

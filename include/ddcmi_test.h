@@ -71,6 +71,10 @@ int ddcmi_group_kinetic_energy_distn(ddcmi_ctx **ctxs, int n, int nspecies, int 
 /* ddcmi_charge_density_modes for an in-process group: every domain's own result, domain after domain -- rho[r*6*mmax ...], count[r]
  * for domain r */
 int ddcmi_group_charge_density_modes(ddcmi_ctx **ctxs, int n, int nspecies, const int *select, int mmax, double *rho, int64_t *count);
+/* ddcmi_structure_modes for an in-process group: every domain's own result, domain after domain -- rho[r*2*nk ...], count[r] for
+ * domain r */
+int ddcmi_group_structure_modes(ddcmi_ctx **ctxs, int n, int nspecies, const int *select, int weight, int nk, const int32_t *kvec, double *rho,
+                                int64_t *count);
 /* ddcmi_subset_records for an in-process group: count[r] of every domain r; with rec, the domains' records one block behind the
  * other in rank order, cap the room for all of them (too small: DDCMI_EINVAL, the counts set, rec untouched) */
 int ddcmi_group_subset_records(ddcmi_ctx **ctxs, int n, const ddcmi_subset_filter *filter, int64_t cap, ddcmi_subset_record *rec, int64_t *count);

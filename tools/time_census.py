@@ -5,12 +5,14 @@ one plain step of the same box in the same process.
 Every call is timed by HIP events recorded on the context's stream around it (the kernels and the copy of the result; median of
 20 after 3 warm-up calls), with the host clock around the [sync] call next to it; the step is the mean of 200 steps after 50
 (rebuilds included), host clock.  Bytes read per bead: momentum 24 (velocity) + 8 (group, species words); zdensity 32 (the position
-record); the VAF sample 32 + 24 + 48 + 8; the kinetic-energy histogram 24 (velocity) + 4 (species word)."""
+record); the VAF sample 32 + 24 + 48 + 8; the kinetic-energy histogram 24 (velocity) + 4 (species word).  The rows of
+ddcmi_structure_modes give sincospi evaluations per second against the FP64 vector issue rate instead: its work is arithmetic."""
 import ctypes, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import ddcmd_amd
 from ddcmd_amd.martini import MartiniHIP
+from ddcmd_amd.analysis import expand_signs, in_plane
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 hip = ctypes.CDLL("libamdhip64.so")
@@ -88,4 +90,21 @@ for spec in (sys.argv[1:] or ["water:102", "lipid:12,12,6"]):
         nbytes = s.natoms * bpb
         print("  %-32s %8.4f ms by events (min %.4f; host clock %.4f ms)  %.3f GB read, %.2f TB/s = %.0f %% of 8 TB/s"
               % (label, med, lo, host, nbytes / 1e9, nbytes / (1e-3 * med) / 1e12, 100 * nbytes / (1e-3 * med) / 8e12), flush=True)
+    # structure_modes is bound by arithmetic, not by bytes: one sincospi per selected bead and wave vector.  The roof is the FP64 vector
+    # issue rate, 256 CUs x 64 lanes x 2.4 GHz = 39.3e12 lane-instructions / s (78.6 TFLOP/s counts an FMA twice); one evaluation costs
+    # SM_FP64 FP64 instructions in k_structure_modes' inner loop (counted in the gfx950 code: the phase 3, its reduction 3, sincospi 26,
+    # the two sums 2) beside about as many 32-bit selects
+    SM_FP64, ROOF = 34, 256 * 64 * 2.4e9
+    quad = expand_signs(in_plane(16))      # 4 x 288 wave vectors: every in-plane vector up to n = 16 in its four sign combinations
+    big = int(np.argmax(np.bincount(s.species, minlength=s.nspecies)))
+    one = np.zeros(s.nspecies, np.int32)
+    one[big] = 1
+    sm_rows = [("structure_modes %s nk=%d" % (s.species_name[big], len(quad)), int((s.species == big).sum()), len(quad), lambda: m.structure_modes(quad, select=one)),
+               ("structure_modes all nk=1024", s.natoms, 1024, lambda: m.structure_modes(quad[:1024])),
+               ("structure_modes all nk=64", s.natoms, 64, lambda: m.structure_modes(quad[:64]))]
+    for label, nsel, nk, call in sm_rows:
+        med, lo, host = timed(m, call, e0, e1)
+        rate = nsel * nk / (1e-3 * med)
+        print("  %-32s %8.4f ms by events (min %.4f; host clock %.4f ms)  %d beads x %d vectors: %.3g sincospi/s = %.0f %% of the FP64 vector roof"
+              % (label, med, lo, host, nsel, nk, rate, 100 * rate * SM_FP64 / ROOF), flush=True)
     m.close()
