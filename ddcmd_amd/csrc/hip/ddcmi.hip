@@ -633,6 +633,21 @@ extern "C" int ddcmi_create(ddcmi_ctx **out, int device)
    ctx->no_bonded_lds = getenv("DDCMI_NO_BONDED_LDS_TABLES") != nullptr;
    /* test hook, armed only together with DDCMI_DEBUG_HOOKS=1 (a stray value alone does nothing; read per context: a test sets it between two of them) */
    ctx->debug_image_bound = (getenv("DDCMI_DEBUG_HOOKS") && getenv("DDCMI_DEBUG_IMAGE_BOUND")) ? atoi(getenv("DDCMI_DEBUG_IMAGE_BOUND")) : 0;
+   /* DDCMI_DEBUG_TAIL=<k> (with DDCMI_DEBUG_HOOKS=1): schedule_tiles cuts the last tiles of every XCD run into k row parts instead of asking its
+    * makespan search -- the tests of the pair kernel's lane splits choose the parts they walk (ddcmi_debug_tile_items shows what was launched) */
+   if (getenv("DDCMI_DEBUG_HOOKS") && getenv("DDCMI_DEBUG_TAIL"))
+   {
+      const char *tv = getenv("DDCMI_DEBUG_TAIL");
+      char *end = nullptr;
+      const long k = strtol(tv, &end, 10);
+      if (end == tv || *end != '\0' || !(k == 1 || k == 2 || k == 3 || k == 4 || k == 6 || k == 8))
+      {
+         g_create_err = std::string("DDCMI_DEBUG_TAIL=") + tv + ": the tail of the tile schedule is cut into 1, 2, 3, 4, 6 or 8 parts";
+         delete ctx;
+         return DDCMI_EINVAL;
+      }
+      ctx->debug_tail = (int)k;
+   }
    /* (Rounds 3-5 registered the context itself with hipHostRegister, so that the two small count arrays inside it -- mig_scnt, hs_cnt: host
     * transport and in-process groups only -- were DMA targets.  A heap object registered, unregistered and freed, its address handed out again by
     * the allocator: later copies from or to pageable memory in those pages ended with "Memory access fault by GPU node" -- 5 of 12 processes that ran

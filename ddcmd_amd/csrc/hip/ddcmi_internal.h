@@ -226,6 +226,7 @@ struct ddcmi_ctx
    dbuf<int> tile_work, sched, tile_perm;   /* per-tile cost estimate (bit 30: stages halo beads); XCD ranges [2][16]; tile order */
    int nitems = 0;                     /* work items of k_nonbond: the tiles with owned beads, the last ones of each XCD's run cut into parts */
    int sched_cache[2][8][3] = {};      /* tail split of each class and XCD run: {tiles it was found for, tiles cut, parts} */
+   int debug_tail = 0;                 /* tests (DDCMI_DEBUG_HOOKS=1 DDCMI_DEBUG_TAIL=k): parts the tail of every run is cut into, in place of the search and its cache; 0: not forced */
    int sched_longest[2] = {0, 0}, ntile_class[2] = {0, 0};      /* class 0: all-owned neighbourhoods (all tiles on one domain), class 1: the rest */
    hipStream_t stream_post = nullptr;  /* the post of the build's results to the host, beside the transposition */
    hipStream_t stream2 = nullptr;      /* decomposed runs: halo exchange, concurrent with the class-0 tiles */

@@ -345,8 +345,10 @@ static int schedule_tiles(ddcmi_ctx *ctx, int wg_per_cu)
           * is kept while the run's tile count stays within 3 % of the count it was found for and re-derived every
           * 64th rebuild. */
          int *cache = ctx->sched_cache[lo == 0 ? 0 : 1][x];
-         const bool cached = cache[0] > 0 && abs(cache[0] - n) <= 2 + n / 32 && (ctx->nrebuild & 63) != 0;
-         if (cached) { best_m = std::min(cache[1], n); best_k = cache[2]; }
+         const int forced = ctx->debug_tail;      /* (tests only, ddcmi_create: the parts are given, no search and no cache) */
+         const bool cached = forced || (cache[0] > 0 && abs(cache[0] - n) <= 2 + n / 32 && (ctx->nrebuild & 63) != 0);
+         if (forced) { best_k = forced; best_m = std::min(n, 1024 / forced); }
+         else if (cached) { best_m = std::min(cache[1], n); best_k = cache[2]; }
          else if (n > 0 && n < 8 * S)
          {
             double best = makespan(tl, n, 0, 1);
@@ -405,6 +407,28 @@ static int schedule_tiles(ddcmi_ctx *ctx, int wg_per_cu)
       ctx->dircnt_clean = dirs;
    }
    return DDCMI_OK;       /* the pinned buffers are rewritten at the next rebuild, behind its own synchronisation */
+}
+/* test entry point (include/ddcmi_test.h): the work items of the last list build as k_nonbond is launched with them -- perm[] as schedule_tiles
+ * left it in pinned memory, and the owned beads of each item's tile from the cell table.  Host numbers: no device counter, no kernel. */
+extern "C" int ddcmi_debug_tile_items(ddcmi_ctx *ctx, int cap, int *nitems, int *item, int *nown)
+{
+   if (!ctx || !nitems) return DDCMI_EINVAL;
+   *nitems = 0;
+   if (!ctx->list_valid || !ctx->h_pin[1].h) SETERR(ctx, DDCMI_EINVAL, "ddcmi_debug_tile_items needs a built list");
+   *nitems = ctx->nitems;
+   if (cap < ctx->nitems || !item || !nown) SETERR(ctx, DDCMI_EINVAL, "ddcmi_debug_tile_items: room for %d work items, the schedule holds %d", cap, ctx->nitems);
+   (void)hipSetDevice(ctx->device);
+   std::vector<int> start((size_t)ctx->gp.ncell + 1);
+   HIPCHK(ctx, hipMemcpyAsync(start.data(), ctx->cell_start_o.p, start.size() * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+   const int *perm = ctx->h_pin[1].h;
+   for (int q = 0; q < ctx->nitems; q++)
+   {
+      const int t = perm[q] & 0xffffff;
+      item[q] = perm[q];
+      nown[q] = (t < ctx->ntile) ? start[(size_t)TCELLS * t + TCELLS] - start[(size_t)TCELLS * t] : -1;
+   }
+   return DDCMI_OK;
 }
 
 /* rebuild phase 4: per-tile staging lists + full neighbour list (16-bit ELL per tile) */

@@ -6,6 +6,7 @@
  *   ddcmi_plan_*               the host logic of the halo exchange / domain directions, callable without a GPU (world-2 CPU tests)
  *   ddcmi_debug_branch_census  which rarely taken dihedral branches a test's geometry drives
  *   ddcmi_debug_bonded_layout  what the bonded kernels' lane layout decided for a test's term lists
+ *   ddcmi_debug_tile_items     the work items the pair kernel was launched with (tiles, row parts) and the owned beads of their tiles
  *   ddcmi_debug_wave_reduce    the transposed wave reduction of several sums against the one-sum reduction, on the test's own numbers */
 #ifndef DDCMI_TEST_H
 #define DDCMI_TEST_H
@@ -89,6 +90,13 @@ int ddcmi_group_coarsegrain(ddcmi_ctx **ctxs, int n, int nx, int ny, int nz, int
 int ddcmi_debug_lean_history(ddcmi_ctx *ctx, int *nsteps, double *sums);
 /* the displacement bound of the shell-limited walk: the word the reduction launches add to, and the lean steps' words since the rebuild (largest |v|^2 of each; ring[32]) */
 int ddcmi_debug_disp(ddcmi_ctx *ctx, double *disp, float *ring, int *nring);
+/* census of the pair kernel's work items after a list build, in launch order: item[q] = tile | part << 24 | (nparts - 1) << 27 as k_nonbond reads it
+ * (a whole tile: part 0 of 1), nown[q] = owned beads of that tile; *nitems = their number.  Part p of n walks the rows [nown p / n, nown (p + 1) / n)
+ * of the tile; how many lanes then share a bead's row follows from that count alone (tests/pair_split_systems.py restates it).  cap < *nitems:
+ * DDCMI_EINVAL with *nitems set and the arrays untouched.  Host numbers (the schedule as it left for the device, the cell table): no device
+ * counter.  Test aid: shows which lane splits and row parts a test's tiles really drive; DDCMI_DEBUG_HOOKS=1 DDCMI_DEBUG_TAIL=k at ddcmi_create
+ * (k = 1, 2, 3, 4, 6, 8; anything else is refused there) cuts the last min(n, 1024 / k) tiles of each of the eight runs into k parts. [sync] */
+int ddcmi_debug_tile_items(ddcmi_ctx *ctx, int cap, int *nitems, int *item, int *nown);
 
 /* the wave reductions of the pair kernel's epilogue against each other, on the current device: nsets sets of in[64][n] doubles (lane-major, 1 <= n <= 16,
  * nsets <= 65535), one 64-thread workgroup each; single[set][k] = wave_sum_dpp of column k, multi[set][k] = what wave_sum_multi_dpp<n> of all
