@@ -7,7 +7,11 @@
  *   ddcmi_debug_branch_census  which rarely taken dihedral branches a test's geometry drives
  *   ddcmi_debug_bonded_layout  what the bonded kernels' lane layout decided for a test's term lists
  *   ddcmi_debug_tile_items     the work items the pair kernel was launched with (tiles, row parts) and the owned beads of their tiles
- *   ddcmi_debug_wave_reduce    the transposed wave reduction of several sums against the one-sum reduction, on the test's own numbers */
+ *   ddcmi_debug_wave_reduce    the transposed wave reduction of several sums against the one-sum reduction, on the test's own numbers
+ *   ddcmi_debug_recip          the four reciprocal routines and the two bare double-precision seeds, on the test's own numbers
+ *   ddcmi_debug_wave_ops       the wave's prefix sum, maximum and row sum and the decaying maximum of the lean steps' words, every lane's result
+ *   ddcmi_debug_scan           the exclusive prefix sum of the rebuild on a context's stream and scratch array
+ *   ddcmi_debug_sort_cells     the two in-cell sorts on the test's own cells and keys */
 #ifndef DDCMI_TEST_H
 #define DDCMI_TEST_H
 #include "ddcmi.h"
@@ -102,6 +106,27 @@ int ddcmi_debug_tile_items(ddcmi_ctx *ctx, int cap, int *nitems, int *item, int 
  * nsets <= 65535), one 64-thread workgroup each; single[set][k] = wave_sum_dpp of column k, multi[set][k] = what wave_sum_multi_dpp<n> of all
  * columns hands lane k.  The two must agree bit for bit. [sync] */
 int ddcmi_debug_wave_reduce(int n, int nsets, const double *in, double *single, double *multi);
+
+/* the device primitives the kernels share, each on the caller's numbers and on the current device (tests/test_gpu_device_primitives.py).  Arguments
+ * out of range: DDCMI_EINVAL. [sync]
+ * ddcmi_debug_recip: out[i] = f(in[i]), one thread per element, 1 <= n <= 2^24; which = 0 rsqrt_f64, 1 rcp_f64 (single-precision seed, two
+ * Newton steps: the bonded kernels'), 2 rsqrt_f64_pair, 3 rcp_f64_pair (double-precision seed, one step: the pair kernel's), 4 the bare seed
+ * v_rsq_f64, 5 the bare seed v_rcp_f64. */
+int ddcmi_debug_recip(int which, int n, const double *in, double *out);
+/* ddcmi_debug_wave_ops: nsets sets of 64 values (nsets <= 65535), one 64-thread workgroup each, out[set][lane] = what the lane got; which = 0
+ * wave_scan_inclusive_dpp (int32), 1 wave_max_dpp (int32 >= 0), 2 row_sum_dpp (double), 3 lean_effective (float, the lane its own index). */
+int ddcmi_debug_wave_ops(int which, int nsets, const void *in, void *out);
+/* ddcmi_debug_scan: ddcmi_scan_exclusive of in[n] on the context's stream with the context's scratch array; the context needs no beads.  in_place != 0:
+ * source and destination are one device array.  total == NULL: the scan is given no word for its total.  out has room for n +
+ * DDCMI_DEBUG_SCAN_GUARD ints (n <= 0: for the guard alone): the device destination is that long, starts as the caller's out[] and comes back whole, so
+ * that out[] shows what the scan left alone -- everything where n <= 0 (then *total = 0), the guard behind element n otherwise.  n <= 2^28. */
+#define DDCMI_DEBUG_SCAN_GUARD 2048
+int ddcmi_debug_scan(ddcmi_ctx *ctx, int n, const int *in, int *out, int *total, int in_place);
+/* ddcmi_debug_sort_cells: the in-cell sort of the rebuild on order[norder]: cell c is order[start[c] ... start[c] + cnt[c]) (cells do not overlap;
+ * a cell outside order[]: DDCMI_EINVAL).  key == NULL: k_sort_cells, ascending entries.  Otherwise k_sort_cells_key: the entries index key[norder]
+ * (unsigned) and key2[norder] (may be NULL), ascending (key, key2, entry); an entry of a cell outside [0, norder): DDCMI_EINVAL.  What lies
+ * between the cells is left alone.  ncell <= 2^20, norder <= 2^24. */
+int ddcmi_debug_sort_cells(int ncell, const int *start, const int *cnt, int norder, int *order, const uint64_t *key, const int *key2);
 
 /* roctx ranges opened so far (DDCMI_ROCTX=1: MDSTEP, DDCENERGY, CHARMM_NONBOND ... named like ptiming.h's regions; 0 without the variable) */
 long ddcmi_debug_roctx_ranges(void);
