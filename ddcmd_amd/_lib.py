@@ -165,6 +165,7 @@ class CSetup(ctypes.Structure):
         ("lcg_state", c_u64_p), ("lcg_multID", ctypes.POINTER(ctypes.c_uint32)), ("lcg_prime", ctypes.POINTER(ctypes.c_uint32)),
         ("group_vcm", c_double_p),
         ("nanalysis", ctypes.c_int), ("analysis", ctypes.POINTER(CAnalysis)),
+        ("group_vset", c_int_p), ("group_v", c_double_p), ("group_Fz", c_double_p),
     ]
 
 

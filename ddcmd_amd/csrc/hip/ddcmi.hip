@@ -915,7 +915,8 @@ extern "C" int ddcmi_set_groups(ddcmi_ctx *ctx, int ngroup, const int *type, con
     *  with a larger count left ngroup ahead of the Berendsen scalars' vectors, which the next step then wrote past) */
    for (int g = 0; g < ngroup; g++)
    {
-      if (type[g] != DDCMI_FREE && type[g] != DDCMI_BERENDSEN && type[g] != DDCMI_LANGEVIN) SETERR(ctx, DDCMI_EUNSUPPORTED, "group %d: only FREE, BERENDSEN and LANGEVIN groups are supported", g);
+      if (type[g] != DDCMI_FREE && type[g] != DDCMI_BERENDSEN && type[g] != DDCMI_LANGEVIN && type[g] != DDCMI_FROZEN && type[g] != DDCMI_FIXEDVELOCITY && type[g] != DDCMI_QUENCH)
+         SETERR(ctx, DDCMI_EUNSUPPORTED, "group %d: only FREE, BERENDSEN, LANGEVIN, FROZEN, FIXEDVELOCITY and QUENCH groups are supported (kind %d)", g, type[g]);
       if (type[g] == DDCMI_LANGEVIN && (!tau || !(tau[g] > 0.0) || !Teq)) SETERR(ctx, DDCMI_EINVAL, "group %d: LANGEVIN needs Teq and tau > 0", g);
    }
    ctx->ngroup = ngroup;
@@ -930,6 +931,8 @@ extern "C" int ddcmi_set_groups(ddcmi_ctx *ctx, int ngroup, const int *type, con
    ctx->glambda.assign(ngroup, 1.0); ctx->gTsum.assign(ngroup, 0.0); ctx->gT.assign(ngroup, 0.0);
    ctx->gnT.assign(ngroup, 0); ctx->gdoScaling.assign(ngroup, 0);
    ctx->gvcm.clear();
+   ctx->gvset.clear(); ctx->gvel.clear();
+   ctx->groups_set = true;
    return DDCMI_OK;
 }
 
@@ -938,6 +941,17 @@ extern "C" int ddcmi_set_group_vcm(ddcmi_ctx *ctx, int ngroup, const double *vcm
    ARGCHK(ctx, ngroup < 0 || ngroup > 32 || (ngroup > 0 && !vcm), "ddcmi_set_group_vcm: %d groups%s", ngroup, vcm ? "" : ", vcm is NULL");
    if (ngroup != ctx->ngroup) SETERR(ctx, DDCMI_EINVAL, "ddcmi_set_group_vcm: %d groups, ddcmi_set_groups gave %d", ngroup, ctx->ngroup);
    ctx->gvcm.assign(vcm, vcm + 3 * (size_t)ngroup);
+   return DDCMI_OK;
+}
+extern "C" int ddcmi_set_group_velocity(ddcmi_ctx *ctx, int ngroup, const int *set, const double *v)
+{
+   ARGCHK(ctx, ngroup <= 0 || ngroup > 32 || !set || !v, "ddcmi_set_group_velocity: %d groups%s%s", ngroup, set ? "" : ", set is NULL", v ? "" : ", v is NULL");
+   if (!ctx->groups_set) SETERR(ctx, DDCMI_EINVAL, "ddcmi_set_group_velocity comes after ddcmi_set_groups");
+   if (ngroup != ctx->ngroup) SETERR(ctx, DDCMI_EINVAL, "ddcmi_set_group_velocity: %d groups, ddcmi_set_groups gave %d", ngroup, ctx->ngroup);
+   for (int k = 0; k < 3 * ngroup; k++)
+      if (!std::isfinite(v[k])) SETERR(ctx, DDCMI_EINVAL, "ddcmi_set_group_velocity: group %d: component %d of v is not finite", k / 3, k % 3);
+   ctx->gvset.assign(set, set + ngroup);
+   ctx->gvel.assign(v, v + 3 * (size_t)ngroup);
    return DDCMI_OK;
 }
 extern "C" int ddcmi_set_group_temperature(ddcmi_ctx *ctx, int group, double Teq)

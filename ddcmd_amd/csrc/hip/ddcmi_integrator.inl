@@ -175,6 +175,9 @@ __global__ void k_finish_energy(double *r, double self_ele)
 struct GroupLambda { double v[32]; double a[32]; double dfac[32]; unsigned lang_mask; unsigned long long seed, counter_front, counter_back;
                      double scale[3]; /* barostat: positions are scaled by this (adjustPosn) before the drift; 1 otherwise */
                      unsigned vcm_mask; double vw[32][3]; /* Langevin groups with a drift velocity (langevin.c:106,167 `vcm`): v = vcm + a (v - vcm) + ... adds vw = (1 - a) vcm to either update */
+                     /* the kinds that are no thermostat (kind_update below): kind_mask = the groups of any of the three, so that a wave without such a bead skips that code;
+                      * fixset_mask: the FIXEDVELOCITY groups with a vector, which lies in vw[g] (only Langevin groups use vw otherwise) */
+                     unsigned kind_mask, frozen_mask, fixset_mask, quench_mask;
                      ulonglong2 *lcg; /* RANDOM type LCG64 (ddcmi_set_random_lcg64): the beads' own streams (the reference's), in slot order; nullptr = the counter-based stream */ };
 __device__ __forceinline__ unsigned long long smix64(unsigned long long z)
 {
@@ -226,6 +229,23 @@ __device__ __forceinline__ void group_gauss3(const GroupLambda &gl, int i, const
    if (gl.lcg) lcg_gauss3(gl.lcg, i, g0, g1, g2);
    else gauss3(gl.seed, gid[i], counter, g0, g1, g2);
 }
+static_assert(sizeof(GroupLambda) <= 2048, "GroupLambda travels by value as a kernel argument: well under the 4 KB of kernel arguments");
+/* velocityUpdate of the GROUP kinds that are no thermostat, the same at FRONT and at BACK (nglf.c:74-108); a = (dt/2)/m, f the force the call sees:
+ *   QUENCH (quench.c)                per component: if (v f < 0) v = 0 -- a product and a strict <: v f == 0, -0.0 and f == 0 leave v alone -- then v += a f
+ *   FIXEDVELOCITY (fixedVelocity.c)  v = the group's vector where one is set; else nothing: the bead coasts
+ *   FROZEN (frozen.c)                nothing: the reference saves v, zeroes it for the drift and puts it back -- here the stored velocity stays where it is
+ *                                    (kinetic terms, temperatures and analyses see it) and the drift takes zero (the callers: frozen_mask) */
+__device__ __forceinline__ void kind_update(const GroupLambda &gl, int gr, double a, double f0, double f1, double f2, double &x, double &y, double &z)
+{
+   if (gl.quench_mask >> gr & 1u)
+   {
+      if (x * f0 < 0.0) x = 0.0;
+      if (y * f1 < 0.0) y = 0.0;
+      if (z * f2 < 0.0) z = 0.0;
+      x = fma(a, f0, x); y = fma(a, f1, y); z = fma(a, f2, z);
+   }
+   else if (gl.fixset_mask >> gr & 1u) { x = gl.vw[gr][0]; y = gl.vw[gr][1]; z = gl.vw[gr][2]; }
+}
 /* the largest |v|^2 of a workgroup's drifting beads, rounded up, into column 7 of its row of partials: the displacement bound of the
  * shell-limited walk (NbTileArgs::disp) adds dt * sqrt(max over the rows) per step (k_reduce_jobs) */
 template <int NW>
@@ -254,12 +274,14 @@ __global__ void k_kick_drift(int nloc, double dt, const double *__restrict__ inv
    if (i < nloc)
    {
       bool done = false;
+      const int gr = group[i] & 31;
+      const bool frozen = glambda.frozen_mask >> gr & 1u;      /* drifts with zero velocity, whatever it stores */
       if (mode != 3)
       {
          /* nglfconstraint splits the pass around the FRONT constraint solve: mode 1 = barostat scaling of the
           * positions (adjustPosn) + kick, mode 2 = drift with the constrained velocities */
          double4 p = pos[i];
-         if (mode == 2) { p.x = fma(dt, vx[i], p.x); p.y = fma(dt, vy[i], p.y); p.z = fma(dt, vz[i], p.z); pos[i] = p; done = true; }
+         if (mode == 2) { if (!frozen) { p.x = fma(dt, vx[i], p.x); p.y = fma(dt, vy[i], p.y); p.z = fma(dt, vz[i], p.z); pos[i] = p; } done = true; }
          else if (glambda.scale[0] != 1.0 || glambda.scale[1] != 1.0 || glambda.scale[2] != 1.0)
          { p.x *= glambda.scale[0]; p.y *= glambda.scale[1]; p.z *= glambda.scale[2]; pos[i] = p; }
       }
@@ -267,10 +289,10 @@ __global__ void k_kick_drift(int nloc, double dt, const double *__restrict__ inv
       {
          const double im = invmass[species[i]];
          double a = (0.5 * dt) * im;
-         const int gr = group[i] & 31;
          double lam = glambda.v[gr];
          double x = vx[i], y = vy[i], z = vz[i];
-         if (glambda.lang_mask >> gr & 1u)
+         if (glambda.kind_mask >> gr & 1u) kind_update(glambda, gr, a, fx[i], fy[i], fz[i], x, y, z);
+         else if (glambda.lang_mask >> gr & 1u)
          {
             double g0, g1, g2, d = glambda.dfac[gr] * sqrt(im), al = glambda.a[gr];
             group_gauss3(glambda, i, gid, glambda.counter_front, g0, g1, g2);
@@ -287,9 +309,10 @@ __global__ void k_kick_drift(int nloc, double dt, const double *__restrict__ inv
          if (mode == 3)
          {
             double4 p = pos[i];
-            p.x = fma(dt, x, glambda.scale[0] * p.x); p.y = fma(dt, y, glambda.scale[1] * p.y); p.z = fma(dt, z, glambda.scale[2] * p.z);
+            if (frozen) { p.x = glambda.scale[0] * p.x; p.y = glambda.scale[1] * p.y; p.z = glambda.scale[2] * p.z; }
+            else { p.x = fma(dt, x, glambda.scale[0] * p.x); p.y = fma(dt, y, glambda.scale[1] * p.y); p.z = fma(dt, z, glambda.scale[2] * p.z); }
             pos[i] = p;
-            v2 = __double2float_ru(x * x + y * y + z * z);
+            v2 = frozen ? 0.0f : __double2float_ru(x * x + y * y + z * z);      /* (a bead that stays has no share in the displacement bound) */
          }
       }
    }
@@ -327,7 +350,8 @@ __global__ __launch_bounds__(DDCMI_BLOCK) void k_kick_ke(int nloc, double dt, co
          const double im = invmass[sp];
          double a = (0.5 * dt) * im;
          const int gr = group[i] & 31;
-         if (glambda.lang_mask >> gr & 1u)
+         if (glambda.kind_mask >> gr & 1u) kind_update(glambda, gr, a, fx[i], fy[i], fz[i], x, y, z);
+         else if (glambda.lang_mask >> gr & 1u)
          {
             double g0, g1, g2, d = glambda.dfac[gr] * sqrt(im), al = glambda.a[gr];
             group_gauss3(glambda, i, gid, glambda.counter_back, g0, g1, g2);
@@ -367,8 +391,10 @@ __global__ __launch_bounds__(DDCMI_BLOCK) void k_kick_ke_drift(int nloc, double 
       double f0 = fx[i], f1 = fy[i], f2 = fz[i];
       const int gr = group[i] & 31;
       const bool lang = glambda.lang_mask >> gr & 1u;
+      const bool kind = glambda.kind_mask >> gr & 1u, frozen = glambda.frozen_mask >> gr & 1u;
       double x, y, z, g0, g1, g2, dl = 0.0, al = 0.0;
-      if (lang)
+      if (kind) { x = vx[i]; y = vy[i]; z = vz[i]; kind_update(glambda, gr, a, f0, f1, f2, x, y, z); }
+      else if (lang)
       {
          dl = glambda.dfac[gr] * sqrt(im); al = glambda.a[gr];
          group_gauss3(glambda, i, gid, glambda.counter_back, g0, g1, g2);
@@ -381,7 +407,8 @@ __global__ __launch_bounds__(DDCMI_BLOCK) void k_kick_ke_drift(int nloc, double 
       acc[0] += 0.5 * m * (vxx + vyy + vzz);
       acc[1] += m * vxx; acc[2] += m * vyy; acc[3] += m * vzz;
       acc[4] += m * (x * y); acc[5] += m * (x * z); acc[6] += m * (y * z);
-      if (lang)
+      if (kind) kind_update(glambda, gr, a, f0, f1, f2, x, y, z);      /* (the FRONT update sees the same force: QUENCH applies its zeroing rule a second time) */
+      else if (lang)
       {
          group_gauss3(glambda, i, gid, glambda.counter_front, g0, g1, g2);
          x = fma(dl, g0, fma(a, f0, al * x)); y = fma(dl, g1, fma(a, f1, al * y)); z = fma(dl, g2, fma(a, f2, al * z));
@@ -394,9 +421,10 @@ __global__ __launch_bounds__(DDCMI_BLOCK) void k_kick_ke_drift(int nloc, double 
          x = fma(a, f0, x); y = fma(a, f1, y); z = fma(a, f2, z);
       }
       vx[i] = x; vy[i] = y; vz[i] = z;
-      v2 = fmaxf(v2, __double2float_ru(x * x + y * y + z * z));
+      if (!frozen) v2 = fmaxf(v2, __double2float_ru(x * x + y * y + z * z));
       double4 p = pos[i];
-      p.x = fma(dt, x, glambda.scale[0] * p.x); p.y = fma(dt, y, glambda.scale[1] * p.y); p.z = fma(dt, z, glambda.scale[2] * p.z);
+      if (frozen) { p.x = glambda.scale[0] * p.x; p.y = glambda.scale[1] * p.y; p.z = glambda.scale[2] * p.z; }
+      else { p.x = fma(dt, x, glambda.scale[0] * p.x); p.y = fma(dt, y, glambda.scale[1] * p.y); p.z = fma(dt, z, glambda.scale[2] * p.z); }
       pos[i] = p;
    }
    block_reduce_store<7>(acc, partials + (size_t)blockIdx.x * 8);

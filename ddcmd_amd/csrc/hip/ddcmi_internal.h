@@ -193,6 +193,9 @@ struct ddcmi_ctx
    int ngroup = 1; std::vector<int> gtype, ginterval; std::vector<double> gTeq, gtau;
    std::vector<double> glambda, gTsum, gT; std::vector<int> gnT, gdoScaling;
    std::vector<double> gvcm;           /* LANGEVIN groups: drift velocity [3 ngroup] (ddcmi_set_group_vcm; empty = zero) */
+   /* FIXEDVELOCITY groups: gvset[g] != 0: the vector gvel[3 g ..] is written at FRONT and BACK (ddcmi_set_group_velocity).
+    * Empty = none set.  groups_set: ddcmi_set_groups has been called (the setter comes after it) */
+   std::vector<int> gvset; std::vector<double> gvel; bool groups_set = false;
    int64_t loop = 0; double time = 0;
    int excludePotentialTerm = 0;
    bool has_charge = false;

@@ -1248,6 +1248,7 @@ extern "C" int ddcmi_group_step_nglf(ddcmi_ctx **ctxs, int n, double dt, int nst
    for (ddcmi_ctx *c : g->ranks)
       if (!c->forces_valid) SETERR(ctxs[0], DDCMI_EINVAL, "ddcmi_group_step_nglf needs forces: call ddcmi_group_eval_forces first (firstEnergyCall, masters.c:579)");
    for (ddcmi_ctx *c : g->ranks) if ((rc = mg_check_one_domain_features(c))) return rc;
+   for (ddcmi_ctx *c : g->ranks) if ((rc = kinds_pairing_check(c))) return rc;
    for (int s = 0; s < nsteps; s++)
    {
       bool rebuild = false;

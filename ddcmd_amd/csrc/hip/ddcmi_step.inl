@@ -401,6 +401,7 @@ static GroupLambda front_lambda(const ddcmi_ctx *ctx, double dt)
 {
    GroupLambda lam;
    lam.lang_mask = 0; lam.seed = ctx->rng_seed; lam.vcm_mask = 0;
+   lam.kind_mask = lam.frozen_mask = lam.fixset_mask = lam.quench_mask = 0;
    lam.lcg = ctx->lcg_on ? ctx->lcg.p : nullptr;
    lam.scale[0] = lam.scale[1] = lam.scale[2] = 1.0;
    /* the FRONT update of a step sees the loop count before its increment, the BACK update the one after */
@@ -412,6 +413,16 @@ static GroupLambda front_lambda(const ddcmi_ctx *ctx, double dt)
       /* lambda applies at the FRONT kick when doScaling is set (berendsen.c:74-80) */
       lam.v[g] = (g < ctx->ngroup && ctx->gtype[g] == DDCMI_BERENDSEN && ctx->gdoScaling[g]) ? ctx->glambda[g] : 1.0;
       lam.a[g] = 1.0; lam.dfac[g] = 0.0;
+      lam.vw[g][0] = lam.vw[g][1] = lam.vw[g][2] = 0.0;
+      const int kind = g < ctx->ngroup ? ctx->gtype[g] : DDCMI_FREE;
+      if (kind == DDCMI_FROZEN || kind == DDCMI_FIXEDVELOCITY || kind == DDCMI_QUENCH) lam.kind_mask |= 1u << g;
+      if (kind == DDCMI_FROZEN) lam.frozen_mask |= 1u << g;
+      if (kind == DDCMI_QUENCH) lam.quench_mask |= 1u << g;
+      if (kind == DDCMI_FIXEDVELOCITY && (size_t)g < ctx->gvset.size() && ctx->gvset[g])
+      {
+         lam.fixset_mask |= 1u << g;
+         for (int k = 0; k < 3; k++) lam.vw[g][k] = ctx->gvel[3 * g + k];
+      }
       if (g < ctx->ngroup && ctx->gtype[g] == DDCMI_LANGEVIN)
       {
          lam.lang_mask |= 1u << g;
@@ -728,6 +739,17 @@ int ddcmi_displacement_check(ddcmi_ctx *ctx, int *need)
    return DDCMI_OK;
 }
 static int mg_check_one_domain_features(ddcmi_ctx *ctx);
+/* FROZEN / FIXEDVELOCITY / QUENCH groups beside constraint groups or a barostat: the constraint solver would move frozen beads and
+ * overwrite set velocities; the pairing is refused at the step, before anything moves */
+static int kinds_pairing_check(ddcmi_ctx *ctx)
+{
+   if (!(ctx->ncgroup > 0 || ctx->baro_beta > 0.0)) return DDCMI_OK;
+   for (int g = 0; g < ctx->ngroup; g++)
+      if (ctx->gtype[g] == DDCMI_FROZEN || ctx->gtype[g] == DDCMI_FIXEDVELOCITY || ctx->gtype[g] == DDCMI_QUENCH)
+         SETERR(ctx, DDCMI_EUNSUPPORTED, "group %d is FROZEN, FIXEDVELOCITY or QUENCH (kind %d): such groups are not supported together with %s", g, ctx->gtype[g],
+                ctx->ncgroup > 0 ? "constraint groups (NGLFCONSTRAINT)" : "a barostat");
+   return DDCMI_OK;
+}
 static int rebuild_due(ddcmi_ctx *ctx, bool *due)
 {
    if (!ctx->list_valid) { *due = true; return DDCMI_OK; }
@@ -754,6 +776,7 @@ extern "C" int ddcmi_step_nglf(ddcmi_ctx *ctx, double dt, int nsteps)
    (void)hipSetDevice(ctx->device);
    int rc;
    if ((rc = mg_check_one_domain_features(ctx))) return rc;
+   if ((rc = kinds_pairing_check(ctx))) return rc;
    if (ctx->baro_beta > 0.0 && ctx->nmol_total == 0 && decomposed(ctx)) SETERR(ctx, DDCMI_EINVAL, "the barostat of a decomposed run needs the molecule count: ddcmi_set_molecule_lists_gid");
    if (ctx->baro_beta > 0.0 && ctx->nmol_total == 0)
       for (int m = 0; m < ctx->nmoltype; m++)

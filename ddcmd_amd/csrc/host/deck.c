@@ -665,6 +665,9 @@ ddcmi_setup *ddcmi_deck_load_with(const char *object_file, const char *restart_f
       s->group_tau = calloc(s->ngroup, sizeof(double));
       s->group_vcm = calloc(3 * (size_t)s->ngroup, sizeof(double));
       s->group_interval = calloc(s->ngroup, sizeof(int));
+      s->group_vset = calloc(s->ngroup, sizeof(int));
+      s->group_v = calloc(3 * (size_t)s->ngroup, sizeof(double));
+      s->group_Fz = calloc(s->ngroup, sizeof(double));
       for (int g = 0; g < s->ngroup; g++)
       {
          OBJECT *go = object_find(gnames[g], "GROUP");
@@ -720,6 +723,50 @@ ddcmi_setup *ddcmi_deck_load_with(const char *object_file, const char *restart_f
                free(dyn);
                if (!explicit_time) { free(type); FAIL("GROUP %s: Teq_dynamics other than EXPLICIT_TIME is not supported (langevin.c:74-79 steers the temperature from the global energy)", gnames[g]); }
             }
+         }
+         else if (strcmp(type, "FROZEN") == 0) s->group_type[g] = DDCMI_GROUP_FROZEN;       /* frozen_parms (frozen.c): no keys */
+         else if (strcmp(type, "QUENCH") == 0) s->group_type[g] = DDCMI_GROUP_QUENCH;       /* quench_parms (quench.c): no keys */
+         else if (strcmp(type, "FIXEDVELOCITY") == 0)
+         {
+            /* fixedVelocity_parms (fixedVelocity.c): `v` is optional -- without it the group's beads coast */
+            s->group_type[g] = DDCMI_GROUP_FIXEDVELOCITY;
+            if (object_testforkeyword(go, "v"))
+            {
+               double *v = &s->group_v[3 * g];
+               v[0] = v[1] = v[2] = NAN;
+               const int nv = object_get(go, "v", v, WITH_UNITS, 3, "0.0 0.0 0.0", "l/t", NULL);
+               if (nv != 3 || !isfinite(v[0]) || !isfinite(v[1]) || !isfinite(v[2]))
+               { free(type); FAIL("GROUP %s: v needs three finite components (got %d: %g %g %g)", gnames[g], nv, v[0], v[1], v[2]); }
+               s->group_vset[g] = 1;
+            }
+         }
+         else if (strcmp(type, "EXTFORCE") == 0)
+         {
+            /* extforce_parms (extforce.c): Fzeq is an EQUATION of time there (eq_parse, like LANGEVIN's Teq above): a constant with an
+             * optional unit of force is what this loader takes, anything else is refused, not misread.  The loader reads the type; the
+             * device integrator has no EXTFORCE update yet, and plugin.c / MartiniHIP refuse such a group by its name */
+            s->group_type[g] = DDCMI_GROUP_EXTFORCE;
+            if (!object_testforkeyword(go, "Fzeq")) { free(type); FAIL("GROUP %s: EXTFORCE needs the key Fzeq", gnames[g]); }
+            char *feq = NULL;
+            object_get(go, "Fzeq", &feq, LITERAL, 1, "0.0");
+            char *endp = NULL;
+            const double val = strtod(feq, &endp);
+            while (endp && (*endp == ' ' || *endp == '\t')) endp++;
+            int ok = endp && endp != feq && isfinite(val);
+            if (ok && *endp)
+            {
+               size_t L = strlen(endp);
+               while (L > 0 && (endp[L - 1] == ' ' || endp[L - 1] == '\t' || endp[L - 1] == ';')) endp[--L] = 0;
+               if (L > 0)
+               {
+                  const double one = units_convert(1.0, endp, "m*l/t^2");
+                  ok = (one == one) && one > 0.0 && isfinite(one) && (*endp != '-' && *endp != '+' && *endp != '*' && *endp != '/' && *endp != '^');
+               }
+            }
+            free(feq);
+            if (!ok) { free(type); FAIL("GROUP %s: Fzeq is not a constant force (an equation of time is not supported)", gnames[g]); }
+            object_get(go, "Fzeq", &s->group_Fz[g], WITH_UNITS, 1, "0.0", "m*l/t^2", NULL);
+            if (!isfinite(s->group_Fz[g])) { free(type); FAIL("GROUP %s: Fzeq is not a finite force", gnames[g]); }
          }
          else s->group_type[g] = DDCMI_GROUP_OTHER;
          free(type);
@@ -1142,7 +1189,7 @@ void ddcmi_setup_free(ddcmi_setup *s)
    free(s->angle_off); free(s->angleI); free(s->angleJ); free(s->angleK); free(s->angle_func); free(s->angle_k); free(s->angle_t0);
    free(s->tors_off); free(s->torsI); free(s->torsJ); free(s->torsK); free(s->torsL); free(s->tors_func); free(s->tors_n); free(s->tors_k); free(s->tors_delta);
    for (int i = 0; i < s->ngroup; i++) if (s->group_name) free(s->group_name[i]);
-   free(s->group_name); free(s->group_type); free(s->group_Teq); free(s->group_tau); free(s->group_vcm); free(s->group_interval);
+   free(s->group_name); free(s->group_type); free(s->group_Teq); free(s->group_tau); free(s->group_vcm); free(s->group_interval); free(s->group_vset); free(s->group_v); free(s->group_Fz);
    free(s->rx); free(s->ry); free(s->rz); free(s->vx); free(s->vy); free(s->vz); free(s->gid); free(s->species); free(s->group);
    free(s->rest_gid); free(s->rest_fc); free(s->rest_r0); free(s->rest_kb);
    free(s->cons_off); free(s->consI); free(s->consJ); free(s->cons_grp); free(s->cons_r0);

@@ -15,7 +15,10 @@
 extern "C" {
 #endif
 
-enum { DDCMI_GROUP_FREE = 0, DDCMI_GROUP_BERENDSEN = 1, DDCMI_GROUP_LANGEVIN = 2, DDCMI_GROUP_OTHER = 3 };
+/* the numbers of include/ddcmi.h's group kinds; OTHER: any other GROUP type, refused by ddcmi_set_groups */
+enum { DDCMI_GROUP_FREE = 0, DDCMI_GROUP_BERENDSEN = 1, DDCMI_GROUP_LANGEVIN = 2, DDCMI_GROUP_OTHER = 3,
+       DDCMI_GROUP_FROZEN = 4, DDCMI_GROUP_FIXEDVELOCITY = 5, DDCMI_GROUP_QUENCH = 6,
+       DDCMI_GROUP_EXTFORCE = 7 /* read by the loader (Fzeq); no kind of include/ddcmi.h yet: refused by name where a deck is to run */ };
 
 /* one ANALYSIS object (analysis_init, analysis.c:120-160).  type: the row of host/analysis.c's table that evaluates it; DDCMI_AN_NONE is any
  * other type (not supported: the driver names it once on stderr) */
@@ -145,6 +148,10 @@ typedef struct ddcmi_setup
    /* SIMULATE analysis = name ... (analysis.c:120-160): every ANALYSIS object in the list, in list order */
    int nanalysis;
    ddcmi_analysis *analysis;
+   /* GROUP type FIXEDVELOCITY (fixedVelocity.c): group_vset[g] = 1 where the object has a `v` key, group_v[3 g ..] its value; type EXTFORCE
+    * (extforce.c): group_Fz[g] = the constant of `Fzeq`.  Internal units; zero for every other group */
+   int *group_vset;
+   double *group_v, *group_Fz;
 } ddcmi_setup;
 
 /* lcg64_default over n particles in order (lcg64.c:98-110, primes.c:35-63 with prime_init(30000, task, ntasks), ddcMD.c:70) */

@@ -239,10 +239,20 @@ static void martini_parms(POTENTIAL *potential, SIMULATE *simulate)
       if (s->group_type[g] == DDCMI_GROUP_FREE) gtype[g] = DDCMI_FREE;
       else if (s->group_type[g] == DDCMI_GROUP_BERENDSEN) gtype[g] = DDCMI_BERENDSEN;
       else if (s->group_type[g] == DDCMI_GROUP_LANGEVIN) gtype[g] = DDCMI_LANGEVIN;
-      else die("group_init", "only FREE, BERENDSEN and LANGEVIN groups are supported on this path");
+      else if (s->group_type[g] == DDCMI_GROUP_FROZEN) gtype[g] = DDCMI_FROZEN;
+      else if (s->group_type[g] == DDCMI_GROUP_FIXEDVELOCITY) gtype[g] = DDCMI_FIXEDVELOCITY;
+      else if (s->group_type[g] == DDCMI_GROUP_QUENCH) gtype[g] = DDCMI_QUENCH;
+      else
+      {
+         char msg[400];
+         snprintf(msg, sizeof(msg), "GROUP %s: type %s: only FREE, BERENDSEN, LANGEVIN, FROZEN, FIXEDVELOCITY and QUENCH groups are supported on this path",
+                  s->group_name[g], s->group_type[g] == DDCMI_GROUP_EXTFORCE ? "EXTFORCE (read, but the device integrator has no such update yet)" : "unknown");
+         die("group_init", msg);
+      }
    }
    rc |= ddcmi_set_groups(ctx, s->ngroup, gtype, s->group_Teq, s->group_tau, s->group_interval);
    if (s->group_vcm) rc |= ddcmi_set_group_vcm(ctx, s->ngroup, s->group_vcm);
+   if (!rc && s->group_vset && s->group_v) rc |= ddcmi_set_group_velocity(ctx, s->ngroup, s->group_vset, s->group_v);      /* fixedVelocity_parms */
    rc |= ddcmi_set_random(ctx, s->rng_seed);
    if (s->nrest > 0)      /* restraint_parms + restraintGPU_parms (restraint.c:177-208) */
       rc |= ddcmi_set_restraints(ctx, s->nrest, s->rest_gid, s->rest_fc, s->rest_r0, s->rest_kb, s->rest_origin);
@@ -443,6 +453,13 @@ INTEGRATOR *integrator_init(void *parent, const char *name, const char *type)
       {
          /* the reference's own pairing for these type strings (integrator.c:59-64): nglf() on the host, the
           * potential on the accelerator.  The default keeps the whole step on the device. */
+         for (int g = 0; g < su->ngroup; g++)      /* refused here, before any output file is opened: nglf() below kicks FREE and BERENDSEN groups only */
+            if (su->group_type[g] != DDCMI_GROUP_FREE && su->group_type[g] != DDCMI_GROUP_BERENDSEN)
+            {
+               char msg[400];
+               snprintf(msg, sizeof(msg), "GROUP %s: the host integrator (DDCMI_CPU_INTEGRATOR=1) handles FREE and BERENDSEN groups only: LANGEVIN, FROZEN, FIXEDVELOCITY and QUENCH groups run on the device integrator", su->group_name[g]);
+               die("integrator_init", msg);
+            }
          in->eval_integrator = (void (*)(void *, void *, void *))nglf;
          in->uses_gpu = 0;
          printf("INTEGRATOR %s on the host (nglf.c), potential on the accelerator\n", type);
@@ -501,7 +518,7 @@ void nglf(DDC *ddc, SIMULATE *simulate, void *parms)
    STATE *st = sys->state;
    const double L[3] = {sys->box->h0[0], sys->box->h0[4], sys->box->h0[8]};
    for (int g = 0; g < sys->ngroup; g++)
-      if (sys->group[g]->itype != FREE && sys->group[g]->itype != BERENDSEN) die("nglf", "the host integrator handles FREE and BERENDSEN groups");
+      if (sys->group[g]->itype != FREE && sys->group[g]->itype != BERENDSEN) die("nglf", "the host integrator (DDCMI_CPU_INTEGRATOR=1) handles FREE and BERENDSEN groups only: LANGEVIN, FROZEN, FIXEDVELOCITY and QUENCH groups run on the device integrator");
    for (int k = 0; k < st->nlocal; k++) group_velocityUpdate(1, k, st->group[k], st, 0.5 * dt);
    for (int k = 0; k < st->nlocal; k++)
    {
@@ -881,7 +898,9 @@ SIMULATE *simulate_init(const char *object_file, const char *restart_file, const
    {
       GROUP *gp = sys->group[g] = calloc(1, sizeof(GROUP));
       gp->name = strdup(s->group_name[g]); gp->index = g;
-      gp->itype = s->group_type[g] == DDCMI_GROUP_FREE ? FREE : s->group_type[g] == DDCMI_GROUP_BERENDSEN ? BERENDSEN : s->group_type[g] == DDCMI_GROUP_LANGEVIN ? LANGEVIN_GROUP : OTHER_GROUP;
+      gp->itype = s->group_type[g] == DDCMI_GROUP_FREE ? FREE : s->group_type[g] == DDCMI_GROUP_BERENDSEN ? BERENDSEN : s->group_type[g] == DDCMI_GROUP_LANGEVIN ? LANGEVIN_GROUP
+                  : s->group_type[g] == DDCMI_GROUP_FROZEN ? FROZEN : s->group_type[g] == DDCMI_GROUP_FIXEDVELOCITY ? FIXEDVELOCITY
+                  : s->group_type[g] == DDCMI_GROUP_QUENCH ? QUENCH : OTHER_GROUP;
       gp->Teq = s->group_Teq[g]; gp->tau = s->group_tau[g]; gp->interval = s->group_interval[g];
    }
    BOX_STRUCT *box = sys->box = calloc(1, sizeof(BOX_STRUCT));

@@ -37,7 +37,7 @@ typedef struct etype_st
 } ETYPE;
 
 typedef struct species_st { char *name; int index; double mass, charge; ETYPE energyInfo; /* the per-species copy kinetic_terms keeps (energy.c:136-147) */ } SPECIES;
-enum GROUP_CLASS { FREE, BERENDSEN, LANGEVIN_GROUP, OTHER_GROUP };
+enum GROUP_CLASS { FREE, BERENDSEN, LANGEVIN_GROUP, OTHER_GROUP, FROZEN, FIXEDVELOCITY, QUENCH };      /* (group.h:80-83's names; the numbers are include/ddcmi.h's kinds) */
 typedef struct group_st { char *name; int index; int itype; double Teq, tau; int interval; ETYPE energyInfo;
                           double Tsum, lambda; int nT, doScaling;      /* BERENDSEN_PARMS' running state (berendsen.c:30-62), host integrator */
 } GROUP;

@@ -9,6 +9,8 @@ from . import _lib
 
 _INT_ARRAYS_SPECIES = ("ljtype", "moltype", "resitype", "atomoffset")
 GROUP_FREE, GROUP_BERENDSEN, GROUP_LANGEVIN, GROUP_OTHER = 0, 1, 2, 3
+GROUP_FROZEN, GROUP_FIXEDVELOCITY, GROUP_QUENCH = 4, 5, 6      # include/ddcmi.h's kinds; 3 stays refused
+GROUP_EXTFORCE = 7      # read by the loader (group_Fz); the device has no such kind yet: MartiniHIP refuses it by name
 
 
 class Setup(object):
@@ -61,6 +63,8 @@ class Setup(object):
         self.group_name = []
         self.group_type = self.group_interval = np.zeros(0, np.int32)
         self.group_Teq = self.group_tau = np.zeros(0)
+        # FIXEDVELOCITY groups: group_vset[g] = 1 where a vector is set, group_v[3 g ..] its value.  None: nothing set
+        self.group_vset = self.group_v = self.group_Fz = None
         self.natoms = 0
         self.rx = self.ry = self.rz = self.vx = self.vy = self.vz = np.zeros(0)
         self.gid = np.zeros(0, np.uint64)
@@ -172,6 +176,9 @@ def load_deck(object_file, restart_file=None, extra_objects=None):
         s.group_Teq = _arr(c.group_Teq, ng, np.float64)
         s.group_tau = _arr(c.group_tau, ng, np.float64)
         s.group_vcm = _arr(c.group_vcm, 3 * ng, np.float64) if c.group_vcm else np.zeros(3 * ng)
+        s.group_vset = _arr(c.group_vset, ng, np.int32) if c.group_vset else np.zeros(ng, np.int32)
+        s.group_v = _arr(c.group_v, 3 * ng, np.float64) if c.group_v else np.zeros(3 * ng)
+        s.group_Fz = _arr(c.group_Fz, ng, np.float64) if c.group_Fz else np.zeros(ng)
         na = c.natoms
         for k in ("rx", "ry", "rz", "vx", "vy", "vz"):
             setattr(s, k, _arr(getattr(c, k), na, np.float64))
@@ -226,6 +233,8 @@ _ARRAY_FIELDS = ("h", "sigma", "eps", "shift", "mass", "charge", "ljtype", "molt
                  "tors_off", "torsI", "torsJ", "torsK", "torsL", "tors_func", "tors_n", "tors_k", "tors_delta",
                  "group_type", "group_interval", "group_Teq", "group_tau",
                  "rx", "ry", "rz", "vx", "vy", "vz", "gid", "species", "group")
+# saved when the Setup has them, read where the file has them (fixtures written before FIXEDVELOCITY groups have none)
+_OPTIONAL_ARRAY_FIELDS = ("group_vset", "group_v", "group_Fz")
 
 
 def setup_to_dict(s):
@@ -233,6 +242,9 @@ def setup_to_dict(s):
     d = {"setup_" + k: np.asarray(getattr(s, k)) for k in _ARRAY_FIELDS}
     for k in Setup.scalar_fields:
         d["setup_" + k] = np.asarray(getattr(s, k))
+    for k in _OPTIONAL_ARRAY_FIELDS:
+        if getattr(s, k, None) is not None:
+            d["setup_" + k] = np.asarray(getattr(s, k))
     d["setup_species_name"] = np.array(s.species_name)
     d["setup_group_name"] = np.array(s.group_name)
     return d
@@ -242,6 +254,9 @@ def setup_from_dict(d):
     s = Setup()
     for k in _ARRAY_FIELDS:
         setattr(s, k, np.array(d["setup_" + k]))
+    for k in _OPTIONAL_ARRAY_FIELDS:
+        if "setup_" + k in d:
+            setattr(s, k, np.array(d["setup_" + k]))
     for k in Setup.scalar_fields:
         v = d["setup_" + k]
         setattr(s, k, v.item())

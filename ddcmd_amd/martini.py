@@ -142,6 +142,7 @@ def _declare(lib):
     lib.ddcmi_set_neighbor.argtypes = [vp, ctypes.c_double, ctypes.c_int]
     lib.ddcmi_set_groups.argtypes = [vp, ctypes.c_int, _ip, _dp, _dp, _ip]
     lib.ddcmi_set_group_vcm.argtypes = [vp, ctypes.c_int, _dp]
+    lib.ddcmi_set_group_velocity.argtypes = [vp, ctypes.c_int, _ip, _dp]
     lib.ddcmi_set_group_temperature.argtypes = [vp, ctypes.c_int, ctypes.c_double]
     lib.ddcmi_set_clock.argtypes = [vp, ctypes.c_int64, ctypes.c_double]
     lib.ddcmi_set_random.argtypes = [vp, ctypes.c_uint64]
@@ -469,12 +470,17 @@ class MartiniHIP(object):
                                                 nt, _i(t["tors_ijkl"]), _i(t["tors_func"]), _i(t["tors_n"]), _d(t["tors_k"]), _d(t["tors_delta"]),
                                                 int(s.excludePotentialTerm)))
         self._chk(self.lib.ddcmi_set_neighbor(self.ctx, s.deltaR, int(s.updateRate)))
-        gt = i32(np.where(np.isin(np.asarray(s.group_type), (1, 2)), np.asarray(s.group_type), 0))     # FREE / BERENDSEN / LANGEVIN
+        gt = i32(s.group_type)      # FREE / BERENDSEN / LANGEVIN / FROZEN / FIXEDVELOCITY / QUENCH: as they are
+        if np.any((gt == 3) | (gt == 7)):         # EXTFORCE (7: read by the loader, not built on the device) and any other GROUP type of a deck: never run as FREE
+            raise DdcmiError("GROUP %s: its type (EXTFORCE or another) is none of FREE, BERENDSEN, LANGEVIN, FROZEN, FIXEDVELOCITY, QUENCH"
+                             % ", ".join(str(s.group_name[g]) if g < len(s.group_name) else str(g) for g in np.flatnonzero((gt == 3) | (gt == 7))))
         self._chk(self.lib.ddcmi_set_groups(self.ctx, s.ngroup, _i(gt), _d(f64(s.group_Teq)), _d(f64(s.group_tau)), _i(i32(s.group_interval))))
         vcm = getattr(s, "group_vcm", None)
         if vcm is not None and np.any(np.asarray(vcm) != 0.0):      # LANGEVIN groups: the velocity the friction relaxes towards (langevin.c:167)
             self._vcm = f64(np.ravel(vcm))
             self._chk(self.lib.ddcmi_set_group_vcm(self.ctx, s.ngroup, _d(self._vcm)))
+        if getattr(s, "group_vset", None) is not None and np.any(np.asarray(s.group_vset) != 0):      # FIXEDVELOCITY groups with a `v` key
+            self.set_group_velocity(s.group_vset, s.group_v)
         self._chk(self.lib.ddcmi_set_random(self.ctx, int(getattr(s, "rng_seed", 0))))
         if float(getattr(s, "npt_beta", 0.0)) > 0.0:      # INTEGRATOR type=NGLFCONSTRAINT: barostat on the molecular pressure
             self.set_barostat(float(s.npt_T), float(s.npt_P0), float(s.npt_beta), float(s.npt_tau), isotropic=bool(getattr(s, "npt_isotropic", 0)),
@@ -507,6 +513,15 @@ class MartiniHIP(object):
     def _chk(self, rc):
         if rc != 0:
             raise DdcmiError("ddcmi error %d: %s" % (rc, self.lib.ddcmi_last_error(self.ctx).decode()))
+
+    def set_group_velocity(self, vset, v):
+        """ddcmi_set_group_velocity: FIXEDVELOCITY groups -- vset[g] != 0: the group's beads get v[g] (internal units) at every velocity
+        update; 0: they coast.  One entry per group of the Setup."""
+        vs = np.ascontiguousarray(np.ravel(vset), dtype=np.int32)
+        vv = np.ascontiguousarray(np.ravel(v), dtype=np.float64)
+        if vv.size != 3 * vs.size:
+            raise DdcmiError("set_group_velocity: %d flags, %d components" % (vs.size, vv.size))
+        self._chk(self.lib.ddcmi_set_group_velocity(self.ctx, int(vs.size), _i(vs), _d(vv)))
 
     def close(self):
         if self.ctx:
@@ -963,6 +978,11 @@ class MartiniGroup(object):
 
     def step(self, nsteps=1, dt=None):
         self._chk(self.lib.ddcmi_group_step_nglf(self.arr, self.n, float(self.s.dt if dt is None else dt), int(nsteps)))
+
+    def set_group_velocity(self, vset, v):
+        """MartiniHIP.set_group_velocity on every domain: the per-group tables belong to each context"""
+        for r in self.ranks:
+            r.set_group_velocity(vset, v)
 
     def group_temperatures(self):
         T = np.zeros(max(1, self.s.ngroup))

@@ -40,8 +40,9 @@ enum { DDCMI_E_LJ = 0, DDCMI_E_ELE, DDCMI_E_BOND, DDCMI_E_ANGLE, DDCMI_E_TORS, D
 enum { DDCMI_XX = 0, DDCMI_YY, DDCMI_ZZ, DDCMI_XY, DDCMI_XZ, DDCMI_YZ };
 /* download mask */
 enum { DDCMI_POS = 1, DDCMI_VEL = 2, DDCMI_FORCE = 4 };
-/* group (thermostat) kinds: free.c, berendsen.c */
-enum { DDCMI_FREE = 0, DDCMI_BERENDSEN = 1, DDCMI_LANGEVIN = 2 };
+/* group kinds (a GROUP's velocityUpdate): free.c, berendsen.c, langevin.c, frozen.c, fixedVelocity.c, quench.c.
+ * 3 is no kind: it stays refused (the deck loader files every other GROUP type under that number) */
+enum { DDCMI_FREE = 0, DDCMI_BERENDSEN = 1, DDCMI_LANGEVIN = 2, DDCMI_FROZEN = 4, DDCMI_FIXEDVELOCITY = 5, DDCMI_QUENCH = 6 };
 
 /* particle labels (gid_type = uint64_t, gid.h:13): MOL 32 | RESID 16 | GROUP 8 | ATOM 8 (bioGid.h:13-22).  The molecule id
  * (reOrgPairs, molecule lists), the residue runs of the bonded terms (charmmResidues) and the group:atom codes of the
@@ -121,7 +122,14 @@ int ddcmi_set_neighbor(ddcmi_ctx *ctx, double deltaR, int updateRate);
 /* GROUP objects (group.c:48-90): type DDCMI_FREE / DDCMI_BERENDSEN{Teq,tau,interval} /
  * DDCMI_LANGEVIN{Teq,tau} (langevin.c:92-128, constant Teq, vcm = 0).  Teq in internal energy units
  * (kB = 1).  The Langevin noise is a counter-based normal stream keyed by (seed, gid, loop): the
- * reference's per-particle LCG64 states are not reproduced -- statistical parity only. */
+ * reference's per-particle LCG64 states are not reproduced -- statistical parity only.
+ * DDCMI_FROZEN / DDCMI_FIXEDVELOCITY / DDCMI_QUENCH: Teq, tau and interval of such a group are ignored (neither
+ * checked nor used).  With a = (dt/2)/m and f the force the call sees, at FRONT and at BACK (nglf.c:74-108):
+ *   FROZEN         the bead does not move and its stored velocity never changes (frozen.c saves v, zeroes it for the drift and puts it
+ *                  back): the stored velocity still enters the kinetic terms, the group's temperature and every analysis
+ *   FIXEDVELOCITY  v = the group's vector where one is set (ddcmi_set_group_velocity); else nothing: the bead coasts (fixedVelocity.c)
+ *   QUENCH         per component: if (v f < 0) v = 0; then v += a f (quench.c; a product, strict <)
+ * A step of a context that has one of these three kinds together with constraint groups or a barostat is refused (DDCMI_EUNSUPPORTED). */
 int ddcmi_set_groups(ddcmi_ctx *ctx, int ngroup, const int *type, const double *Teq, const double *tau, const int *interval);
 /* LANGEVIN groups, the rest of langevin_velocityUpdate (langevin.c:92-128): `vcm`, the velocity the friction relaxes towards
  * (:106,167; v = vcm + a (v - vcm) + c f + d g), per group, [3 ngroup], internal units; after ddcmi_set_groups (which resets it
@@ -130,6 +138,10 @@ int ddcmi_set_groups(ddcmi_ctx *ctx, int ngroup, const int *type, const double *
  * (the equation grammar is simutil's eq_parse, which the reference tree does not hold: the deck loader takes constants). */
 int ddcmi_set_group_vcm(ddcmi_ctx *ctx, int ngroup, const double *vcm);
 int ddcmi_set_group_temperature(ddcmi_ctx *ctx, int group, double Teq);
+/* FIXEDVELOCITY groups: set[g] != 0: the group's beads get v[3 g ..] (internal units) at every FRONT and BACK update; set[g] == 0: the
+ * group has no `v` key and its beads coast.  Entries of groups of other kinds are checked and ignored.  Comes after ddcmi_set_groups (which
+ * resets it: no vector set) with its group count, and checks every value for finiteness before it keeps any: a refused call changes nothing. */
+int ddcmi_set_group_velocity(ddcmi_ctx *ctx, int ngroup, const int *set, const double *v /* [3 ngroup] */);
 /* INTEGRATOR type=NGLFCONSTRAINT (nglfconstraint.c:510-574): NGLF plus a semi-isotropic Berendsen
  * barostat (changeVolume, :64-84) driven by the molecular pressure of the last force evaluation at the
  * target temperature T: lambda_xy = cbrt(1 + beta dt/tau ((Pxx+Pyy)/2 - P0)), lambda_z likewise from Pzz;
