@@ -106,6 +106,16 @@ class CAnalysis(ctypes.Structure):
                 ("cg_n", ctypes.c_int * 3), ("cg_output_mode", ctypes.c_int), ("cg_nfiles", ctypes.c_int), ("cg_smear_string", ctypes.c_char_p)]
 
 
+TR_NONE, TR_THERMALIZE = range(2)      # enum ddcmi_transform_kind
+
+
+class CTransform(ctypes.Structure):
+    """Mirror of struct ddcmi_transform (ddcmd_amd/csrc/host/deck.h)."""
+    _fields_ = [("name", ctypes.c_char_p), ("type_name", ctypes.c_char_p), ("type", ctypes.c_int), ("rate", ctypes.c_int64),
+                ("method", ctypes.c_int), ("select", ctypes.c_int), ("keep_vcm", ctypes.c_int), ("seed", ctypes.c_uint64),
+                ("ntemp", ctypes.c_int), ("temperature", c_double_p)]
+
+
 class CSetup(ctypes.Structure):
     """Mirror of struct ddcmi_setup (ddcmd_amd/csrc/host/deck.h)."""
     _fields_ = [
@@ -166,6 +176,7 @@ class CSetup(ctypes.Structure):
         ("group_vcm", c_double_p),
         ("nanalysis", ctypes.c_int), ("analysis", ctypes.POINTER(CAnalysis)),
         ("group_vset", c_int_p), ("group_v", c_double_p), ("group_Fz", c_double_p),
+        ("ntransform", ctypes.c_int), ("transform", ctypes.POINTER(CTransform)),
     ]
 
 

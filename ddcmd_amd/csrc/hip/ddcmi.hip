@@ -1432,6 +1432,7 @@ extern "C" int ddcmi_timing_fused(ddcmi_ctx *ctx, int64_t *launches, double *tot
 #include "ddcmi_analysis.inl"
 #include "ddcmi_vaf.inl"
 #include "ddcmi_census.inl"
+#include "ddcmi_thermalize.inl"
 #include "ddcmi_kdist.inl"
 #include "ddcmi_dsf.inl"
 #include "ddcmi_ssf.inl"

@@ -377,6 +377,7 @@ struct ddcmi_ctx
     * (k_gather_state, the migration records) */
    dbuf<VafRec> vaf, vaf2; bool vaf_on = false;
    dbuf<double> census_part;      /* the census passes (ddcmi_census_frame.inl): the pass's per-workgroup sums and, behind them, its result */
+   dbuf<double> therm_tab;        /* TRANSFORM THERMALIZE (ddcmi_thermalize.inl): the classes' temperatures, or their {vcm, scale, new vcm, apply} rows; the ranks' gathered sums */
    /* subsetWrite's frames (ddcmi_subset.inl): the filter's tables with the workgroups' counts and offsets, the idList, the packed records */
    dbuf<unsigned> subset_tab; dbuf<unsigned long long> subset_ids, subset_rec;
    /* COARSEGRAIN (ddcmi_coarsegrain.inl): the sort's (key, value) pairs, source and destination; its digit counts and their scan; the

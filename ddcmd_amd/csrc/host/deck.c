@@ -896,6 +896,77 @@ ddcmi_setup *ddcmi_deck_load_with(const char *object_file, const char *restart_f
             FAIL("ANALYSIS %s: %d groups and %d species need a pinfo field of more than 4 bytes", an->name, s->ngroup, s->nspecies);
       }
    }
+   /* TRANSFORM objects (transform_init, transform.c:30-60): SIMULATE transform = name ...; type THERMALIZE with the keys of
+    * thermalizeTransform_parms (thermalizeTransform.c:51-91), refused where validateObject (:111-175) refuses.  Behind the groups and
+    * the species: the object names them */
+   {
+      char **tnames = NULL;
+      char *stype = get_string(sim, "type", "MD");
+      const int transform_master = strcasecmp(stype, "TRANSFORM") == 0;
+      free(stype);
+      if (transform_master) FAIL("SIMULATE type = TRANSFORM (transformMaster, masters.c:58-69: a run that only transforms and exits) is not supported");
+      const int nt = object_getv(sim, "transform", (void **)&tnames, STRING, IGNORE_IF_NOT_FOUND);
+      if (nt > 0)
+      {
+         s->ntransform = nt;
+         s->transform = calloc(nt, sizeof(ddcmi_transform));
+         for (int t = 0; t < nt; t++) s->transform[t].name = tnames[t];
+      }
+      free(tnames);
+      for (int t = 0; t < s->ntransform; t++)
+      {
+         ddcmi_transform *tr = &s->transform[t];
+         OBJECT *to = object_find(tr->name, "TRANSFORM");
+         if (!to) FAIL("TRANSFORM %s not found", tr->name);
+         tr->type_name = get_string(to, "type", "NONE");
+         char *rate = get_string(to, "rate", "NONE");      /* transform.c:41-52; no key: atStartThenExit, which never runs at rate */
+         if (strcasecmp(rate, "atCheckpoint") == 0) tr->rate = s->checkpointrate;
+         else if (strcasecmp(rate, "atMaxLoop") == 0) tr->rate = s->maxloop;
+         else if (isdigit((unsigned char)rate[0])) tr->rate = strtol(rate, NULL, 10);
+         free(rate);
+         if (strcasecmp(tr->type_name, "THERMALIZE") != 0) continue;
+         tr->type = DDCMI_TR_THERMALIZE;
+         int randomize = 0, rescale = 0;
+         object_get(to, "randomizeSeed", &randomize, INT, 1, "0");
+         if (randomize != 0)
+            FAIL("TRANSFORM %s: randomizeSeed = %d is refused: a seed drawn at run time makes a run that cannot be repeated (set seed instead)", tr->name, randomize);
+         if (object_testforkeyword(to, "randomize")) FAIL("TRANSFORM %s: the obsolete keyword randomize (thermalizeTransform.c:140-146)", tr->name);
+         object_get(to, "keepVcm", &tr->keep_vcm, INT, 1, "0");
+         object_get(to, "seed", &tr->seed, U64, 1, "385212586");
+         object_get(to, "rescale", &rescale, INT, 1, "0");
+         char *method = get_string(to, "method", "BOLTZMANN");
+         const int juttner = strncmp(method, "JUTTNER", 7) == 0;
+         tr->method = strncmp(method, "RESCALE", 7) == 0 ? 1 : 0;      /* matched by its head; anything else stays BOLTZMANN (:57-66) */
+         free(method);
+         if (rescale != 0) tr->method = 1;
+         else if (juttner) FAIL("TRANSFORM %s: method = JUTTNER (relativistic) is not supported: BOLTZMANN and RESCALE are", tr->name);
+         double temp[64];
+         const int nT = object_get(to, "temperature", temp, WITH_UNITS, 64, NULL, "T", NULL);
+         char **sn = NULL, **gn = NULL;
+         const int nsIn = object_getv(to, "species", (void **)&sn, STRING, IGNORE_IF_NOT_FOUND), ngIn = object_getv(to, "groups", (void **)&gn, STRING, IGNORE_IF_NOT_FOUND);
+         char msg[400] = "";
+         if (nsIn > 0 && ngIn > 0) snprintf(msg, sizeof(msg), "TRANSFORM %s: both species and groups: choose one or the other", tr->name);
+         else if (nsIn == 0 && ngIn == 0 && nT != 1) snprintf(msg, sizeof(msg), "TRANSFORM %s: %d temperatures: without species or groups exactly one", tr->name, nT);
+         else if (nsIn > 0 && nT != nsIn) snprintf(msg, sizeof(msg), "TRANSFORM %s: %d temperatures for %d species", tr->name, nT, nsIn);
+         else if (ngIn > 0 && nT != ngIn) snprintf(msg, sizeof(msg), "TRANSFORM %s: %d temperatures for %d groups", tr->name, nT, ngIn);
+         tr->select = nsIn > 0 ? 1 : (ngIn > 0 ? 2 : 0);
+         tr->ntemp = nsIn > 0 ? s->nspecies : (ngIn > 0 ? (s->ngroup > 0 ? s->ngroup : 1) : 1);
+         tr->temperature = malloc(sizeof(double) * (size_t)tr->ntemp);
+         for (int k = 0; k < tr->ntemp; k++) tr->temperature[k] = -1.0;      /* thermalize_init, thermalize.c:44-46: no change for a class that is not named */
+         if (!msg[0] && tr->select == 0) tr->temperature[0] = temp[0];
+         for (int k = 0; !msg[0] && k < nsIn + ngIn; k++)
+         {
+            const char *nm = nsIn > 0 ? sn[k] : gn[k];
+            const int id = nsIn > 0 ? find_name(s->species_name, s->nspecies, nm) : find_name(s->group_name, s->ngroup, nm);
+            if (id < 0) snprintf(msg, sizeof(msg), "TRANSFORM %s: %s = %s, and the system has no %s of that name", tr->name, nsIn > 0 ? "species" : "groups", nm, nsIn > 0 ? "species" : "group");
+            else tr->temperature[id] = temp[k];
+         }
+         for (int k = 0; k < nsIn; k++) free(sn[k]);
+         for (int k = 0; k < ngIn; k++) free(gn[k]);
+         free(sn); free(gn);
+         if (msg[0]) FAIL("%s", msg);
+      }
+   }
    /* POTENTIAL type=MARTINI */
    {
       char **pnames = NULL;
@@ -1205,6 +1276,8 @@ void ddcmi_setup_free(ddcmi_setup *s)
       free(an->sw_species); free(an->sw_idlist); free(an->sw_length_unit); free(an->cg_smear_string);
    }
    free(s->analysis);
+   for (int t = 0; t < s->ntransform; t++) { free(s->transform[t].name); free(s->transform[t].type_name); free(s->transform[t].temperature); }
+   free(s->transform);
    free(s->u_pressure); free(s->u_volume); free(s->u_temperature); free(s->u_energy); free(s->u_time); free(s->u_length);
    free(s);
 }

@@ -59,6 +59,23 @@ typedef struct ddcmi_analysis
    char *cg_smear_string;       /* smearMethod as the deck spells it (the file's misc_info echoes it) */
 } ddcmi_analysis;
 
+/* one TRANSFORM object of SIMULATE transform = name ... (transform_init, transform.c:30-60).  type DDCMI_TR_THERMALIZE: thermalizeTransform_parms
+ * (thermalizeTransform.c:51-91) as checkInput (:111-175) lets it through; DDCMI_TR_NONE is any other type (not supported: the driver names
+ * it once on stderr and never runs it) */
+enum ddcmi_transform_kind { DDCMI_TR_NONE = 0, DDCMI_TR_THERMALIZE };
+typedef struct ddcmi_transform
+{
+   char *name, *type_name;
+   enum ddcmi_transform_kind type;
+   int64_t rate;                /* an integer, atCheckpoint (the checkpoint rate) or atMaxLoop (maxloop); 0: no rate key -- the transform never runs at rate */
+   int method;                  /* 0 BOLTZMANN, 1 RESCALE (method matched by its head, or rescale != 0) */
+   int select;                  /* 0 global, 1 by species, 2 by group */
+   int keep_vcm;
+   uint64_t seed;
+   int ntemp;                   /* select 0: 1; 1: the system's species; 2: its groups */
+   double *temperature;         /* internal energy units (kB = 1); -1 for a class the object does not name (thermalize_init, thermalize.c:44-46) */
+} ddcmi_transform;
+
 typedef struct ddcmi_setup
 {
    /* SIMULATE (simulate.c:141-169,239-244) */
@@ -152,6 +169,9 @@ typedef struct ddcmi_setup
     * (extforce.c): group_Fz[g] = the constant of `Fzeq`.  Internal units; zero for every other group */
    int *group_vset;
    double *group_v, *group_Fz;
+   /* SIMULATE transform = name ... (simulate.c): every TRANSFORM object in the list, in list order */
+   int ntransform;
+   ddcmi_transform *transform;
 } ddcmi_setup;
 
 /* lcg64_default over n particles in order (lcg64.c:98-110, primes.c:35-63 with prime_init(30000, task, ntasks), ddcMD.c:70) */

@@ -1130,6 +1130,44 @@ void printinfo(SIMULATE *simulate, ETYPE *e_in, int header)
    }
 }
 
+/* atRateTransforms (transform.c:154-180), called behind a batch's kinetic_terms + eval_energyInfo (masters.c:454-457): the transforms whose
+ * rate divides the loop, in list order, on the device.  The reference then calls ddcenergy(.., 1) (transform.c:176): positions did not move,
+ * so the forces and eion stand and the caller's kinetic_terms + eval_energyInfo form the rest from the new velocities.  Collective.
+ * Returns how many ran. */
+static int atRateTransforms(SIMULATE *simulate)
+{
+   const ddcmi_setup *s = simulate->setup;
+   ddcmi_ctx *ctx = simulate->accelerator->parms;
+   int ran = 0;
+   for (int t = 0; t < s->ntransform; t++)
+   {
+      const ddcmi_transform *tr = &s->transform[t];
+      if (tr->type != DDCMI_TR_THERMALIZE || !(tr->rate > 0) || simulate->loop % tr->rate != 0) continue;
+      if (par.rank == 0) printf("Performing transformation %s\n", tr->name);
+      if (ddcmi_thermalize(ctx, tr->method, tr->select, tr->ntemp, tr->temperature, tr->seed, simulate->loop, tr->keep_vcm) != DDCMI_OK) die("atRateTransforms", ddcmi_last_error(ctx));
+      ran++;
+   }
+   return ran;
+}
+/* the TRANSFORM objects of the deck before the first step: an unsupported type is named once and never runs; the host integrator keeps
+ * its velocities in STATE, where a device transform does not reach */
+static void transforms_init(SIMULATE *simulate)
+{
+   const ddcmi_setup *s = simulate->setup;
+   for (int t = 0; t < s->ntransform; t++)
+   {
+      const ddcmi_transform *tr = &s->transform[t];
+      if (tr->type == DDCMI_TR_NONE)
+      { if (par.rank == 0) fprintf(stderr, "ddcmi_md: TRANSFORM %s of type %s is not supported and is ignored\n", tr->name, tr->type_name ? tr->type_name : "?"); }
+      else if (tr->rate > 0 && !simulate->integrator->uses_gpu)
+      {
+         char msg[300];
+         snprintf(msg, sizeof(msg), "TRANSFORM %s runs on the device: not with the host integrator (DDCMI_CPU_INTEGRATOR=1)", tr->name);
+         die("simulateMaster", msg);
+      }
+   }
+}
+
 /* simulateMaster, masters.c:369-559: firstEnergyCall, then batches of steps up to
  * the next print step (findEndLoop :263-281), energies after each batch */
 int simulateMaster(SIMULATE *simulate, const char *datafile_path)
@@ -1148,6 +1186,7 @@ int simulateMaster(SIMULATE *simulate, const char *datafile_path)
       if (simulate->setup->printStress) { snprintf(path, sizeof(path), "%sstress.data", dir); simulate->stressfile = fopen(path, "a"); }
       if (simulate->setup->printHmatrix) { snprintf(path, sizeof(path), "%shmatrix.data", dir); simulate->hmatfile = fopen(path, "a"); }
    }
+   transforms_init(simulate);
    simulate->ddc->update = 3;                                     /* firstEnergyCall :579-620 */
    ddcenergy(simulate->ddc, sys, 1);
    printinfo(simulate, &sys->energyInfo, 1);
@@ -1167,6 +1206,13 @@ int simulateMaster(SIMULATE *simulate, const char *datafile_path)
          if (nextSn < endLoop) endLoop = nextSn;
       }
       endLoop = analysis_next_stop(simulate, endLoop);            /* findEndLoop, masters.c:277-282: the analyses' eval and output rates */
+      for (int t = 0; t < simulate->setup->ntransform; t++)       /* masters.c:273: the transforms' rates */
+      {
+         const ddcmi_transform *tr = &simulate->setup->transform[t];
+         if (tr->type == DDCMI_TR_NONE || !(tr->rate > 0)) continue;
+         const int64_t nextTr = (simulate->loop / tr->rate + 1) * tr->rate;
+         if (nextTr < endLoop) endLoop = nextTr;
+      }
       if (endLoop > simulate->maxloop) endLoop = simulate->maxloop;
       if (simulate->integrator->eval_integrator == (void (*)(void *, void *, void *))nglfHIP)
       {
@@ -1181,6 +1227,11 @@ int simulateMaster(SIMULATE *simulate, const char *datafile_path)
       else
          while (simulate->loop < endLoop)
             simulate->integrator->eval_integrator(simulate->ddc, simulate, simulate->integrator->parms);
+      /* atRateTransforms (masters.c:457): behind the batch and its energies (:448-455), in front of the `data` line (:482), the checkpoint
+       * (:503), the analyses (:504) and the snapshot (:505) of this loop.  The reference forms the kinetic terms in front of it and, when a
+       * transform ran, once more behind it (ddcenergy(.., 1), transform.c:176); here they are formed once, below, from the velocities the
+       * transforms left */
+      atRateTransforms(simulate);
       /* uses_gpu: sendForceEnergyToHost (masters.c:448-453), then kinetic_terms + eval_energyInfo (:454-455) */
       double en[DDCMI_NE], vir[6], rk, tion[6];
       if (ddcmi_get_energies(ctx, en, vir, &rk, tion) != DDCMI_OK) die("simulateMaster", ddcmi_last_error(ctx));

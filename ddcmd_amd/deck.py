@@ -84,6 +84,7 @@ class Setup(object):
         self.rest_r0 = np.zeros((0, 3))
         self.rest_kb = np.zeros(0)
         self.accelerator_type = "NONE"
+        self.transform = []           # SIMULATE transform = ...: the TRANSFORM objects (load_deck)
         self.units = {}
 
     @property
@@ -215,6 +216,15 @@ def load_deck(object_file, restart_file=None, extra_objects=None):
                 d.update(nx=int(a.cg_n[0]), ny=int(a.cg_n[1]), nz=int(a.cg_n[2]), output_mode=int(a.cg_output_mode), nfiles=int(a.cg_nfiles),
                          smear_radius=float(a.smear_radius), smear_method=("impulse", "hat")[a.smear_method])
             s.analysis.append(d)
+        # SIMULATE transform = ...: one dict per TRANSFORM object, in list order (type THERMALIZE with its parameters; temperatures in internal
+        # energy units, -1 for a class the object does not name; rate 0: no rate key)
+        s.transform = []
+        for t in (c.transform[i] for i in range(int(c.ntransform))):
+            d = {"name": t.name.decode(), "type": (t.type_name or b"").decode(), "rate": int(t.rate), "supported": t.type != _lib.TR_NONE}
+            if t.type == _lib.TR_THERMALIZE:
+                d.update(method=("BOLTZMANN", "RESCALE")[t.method], select=("global", "species", "group")[t.select], keep_vcm=bool(t.keep_vcm),
+                         seed=int(t.seed), temperature=[float(t.temperature[k]) for k in range(int(t.ntemp))])
+            s.transform.append(d)
     finally:
         lib.ddcmi_setup_free(p)
     return s

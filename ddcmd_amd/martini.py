@@ -204,7 +204,21 @@ def _declare(lib):
     lib.ddcmi_structure_modes.argtypes = [vp, ctypes.c_int, _ip, ctypes.c_int, ctypes.c_int, _ip, _dp, _lp]
     lib.ddcmi_subset_records.argtypes = [vp, ctypes.POINTER(CSubsetFilter), ctypes.c_int64, vp, _lp]
     lib.ddcmi_coarsegrain.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int64, vp, _lp]
+    lib.ddcmi_thermalize.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int]
     lib._ddcmi_declared = True
+
+
+THERMALIZE_METHODS = {"BOLTZMANN": 0, "RESCALE": 1, "JUTTNER": 2}
+THERMALIZE_SELECTS = {"global": 0, "species": 1, "group": 2}
+
+
+def _thermalize_args(setup, method, temperature, select):
+    """(method, select, temperature array) of ddcmi_thermalize: names or the numbers themselves; the temperatures in internal energy units
+    (kB = 1), one for "global", one per species / group otherwise (< 0: that class is left alone)"""
+    m = THERMALIZE_METHODS[method.upper()] if isinstance(method, str) else int(method)
+    sel = THERMALIZE_SELECTS[select.lower()] if isinstance(select, str) else int(select)
+    t = np.ascontiguousarray(np.atleast_1d(temperature), dtype=np.float64)
+    return m, sel, t
 
 
 def default_port_file():
@@ -745,6 +759,14 @@ class MartiniHIP(object):
         self._chk(self.lib.ddcmi_coarsegrain(self.ctx, *a, int(n[0]) if cap is None else int(cap), rec.ctypes.data_as(ctypes.c_void_p), n.ctypes.data_as(_lp)))
         return rec[:int(n[0])]
 
+    def thermalize(self, method, temperature, select="global", seed=385212586, loop=0, keep_vcm=False):
+        """TRANSFORM type THERMALIZE (ddcmi_thermalize): new velocities for this context's beads, nothing else changes.  method "BOLTZMANN":
+        v = sqrt(T / m) g on the bead's own erand48 stream of (gid, seed, loop); "RESCALE": per class (v - vcm) sqrt(T / T_now) + vcm
+        (keep_vcm) or + vcm sqrt(T / T_now).  select "global" (one temperature), "species" or "group" (one per class, < 0: left alone);
+        internal energy units, kB = 1.  Collective on a decomposed run."""
+        m, sel, t = _thermalize_args(self.s, method, temperature, select)
+        self._chk(self.lib.ddcmi_thermalize(self.ctx, m, sel, int(t.size), _d(t), int(seed), int(loop), int(bool(keep_vcm))))
+
     def download(self, mask=POS | VEL | FORCE):
         n = self.n
         out = [np.zeros(n) for _ in range(9)]
@@ -842,6 +864,7 @@ def _declare_domains(lib):
     lib.ddcmi_group_subset_records.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.POINTER(CSubsetFilter), ctypes.c_int64, vp, _lp]
     lib.ddcmi_group_coarsegrain.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int,
                                             ctypes.c_int64, vp, _lp]
+    lib.ddcmi_group_thermalize.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int]
     lib._ddcmi_dom_declared = True
 
 
@@ -1101,6 +1124,11 @@ class MartiniGroup(object):
         from .analysis import merge_cg_records
         off = np.concatenate([[0], np.cumsum(n)])
         return merge_cg_records([rec[off[r]:off[r + 1]] for r in range(self.n)])
+
+    def thermalize(self, method, temperature, select="global", seed=385212586, loop=0, keep_vcm=False):
+        """ddcmi_group_thermalize: MartiniHIP.thermalize on every domain; RESCALE adds the domains' sums in rank order"""
+        m, sel, t = _thermalize_args(self.s, method, temperature, select)
+        self._chk(self.lib.ddcmi_group_thermalize(self.arr, self.n, m, sel, int(t.size), _d(t), int(seed), int(loop), int(bool(keep_vcm))))
 
     def energies(self):
         """sum over ranks = energyInfo.c allreduce()"""

@@ -378,6 +378,27 @@ typedef struct ddcmi_cg_record { int64_t label; int32_t species; int32_t pad; do
 int ddcmi_coarsegrain(ddcmi_ctx *ctx, int nx, int ny, int nz, int nspecies, double smear_radius, int smear_method, int64_t cap, ddcmi_cg_record *rec,
                       int64_t *count);
 
+/* ---- transforms ------------------------------------------------------------ */
+/* TRANSFORM type THERMALIZE on the device (thermalize.c:83-269): new velocities for the owned beads.  Only the velocities change --
+ * positions, lists, the validity of the forces and the VAF records stay -- and the call is legal whenever a state is uploaded; kinetic
+ * terms read before it are stale (ddcmi_kinetic forms them anew).  select 0: one class, temperature[0]; 1: by species; 2: by group
+ * (getIndex, :271-289); ntemp must cover the classes of the select.  Temperatures in internal energy units (kB = 1).  The mass is the
+ * species' mass of ddcmi_set_species, the one the integrator's kick uses.
+ * method 0 BOLTZMANN (thermalize_boltzmann, :103-125): v = sqrt(T / m) g, g three normals of gasdev0 (random.c:100-112) on the bead's own
+ *    erand48 stream prand48_init((loop % 10000000 + 1) * gid, seed, 0x1234512345ab) (random.c:370-386), reproduced operation by operation:
+ *    a bead's velocity depends on its gid, its mass, T, seed and loop alone -- not on the decomposition, and loop and loop + 10000000 draw
+ *    alike.  A bead whose class has T < 0 is not written.  keep_vcm is ignored.
+ * method 1 RESCALE (thermalize_rescale, :159-269): per class vcm = sum m v / sum m, tempSum = sum m |v - vcm|^2 / (3 (N - 1)),
+ *    v' = (v - vcm) vScale + vcmNew, vScale = sqrt(T / tempSum) or 1 where T <= 0, vcmNew = vcm (keep_vcm != 0) or vcm vScale.  The sums
+ *    follow the census passes' rules (no floating-point atomics, identical bits when repeated); on a decomposed run the call is collective
+ *    and every rank adds the ranks' sums in rank order.  A class with N <= 1 or tempSum == 0, where the reference divides by zero, is not
+ *    written.  At most 512 classes (1 + groups + species, as ddcmi_momentum_by_class): more is DDCMI_EUNSUPPORTED.
+ * method 2 JUTTNER (relativistic): DDCMI_EUNSUPPORTED.
+ * DDCMI_EINVAL: no uploaded state, a method or select out of range, ntemp below the number of classes, a NaN temperature. [sync] */
+int ddcmi_thermalize(ddcmi_ctx *ctx, int method /*0 BOLTZMANN, 1 RESCALE*/, int select /*0 global, 1 by species, 2 by group*/,
+                     int ntemp, const double *temperature /*internal energy units, kB = 1; < 0: leave this class alone*/,
+                     uint64_t seed, int64_t loop, int keep_vcm);
+
 /* ---- introspection / measurement ------------------------------------------- */
 /* list statistics of the last build: stats[0]=stored full-list entries,
  * [1]=excluded-list entries, [2]=ELL width, [3]=image (halo) atoms, [4]=cells,

@@ -11,7 +11,8 @@
  *   ddcmi_debug_recip          the four reciprocal routines and the two bare double-precision seeds, on the test's own numbers
  *   ddcmi_debug_wave_ops       the wave's prefix sum, maximum and row sum and the decaying maximum of the lean steps' words, every lane's result
  *   ddcmi_debug_scan           the exclusive prefix sum of the rebuild on a context's stream and scratch array
- *   ddcmi_debug_sort_cells     the two in-cell sorts on the test's own cells and keys */
+ *   ddcmi_debug_sort_cells     the two in-cell sorts on the test's own cells and keys
+ *   ddcmi_debug_thermalize_rejects  the rejected draws of every bead's BOLTZMANN stream */
 #ifndef DDCMI_TEST_H
 #define DDCMI_TEST_H
 #include "ddcmi.h"
@@ -87,6 +88,13 @@ int ddcmi_group_subset_records(ddcmi_ctx **ctxs, int n, const ddcmi_subset_filte
  * rank order, cap the room for all of them (too small: DDCMI_EINVAL, the counts set, rec untouched) */
 int ddcmi_group_coarsegrain(ddcmi_ctx **ctxs, int n, int nx, int ny, int nz, int nspecies, double smear_radius, int smear_method, int64_t cap,
                             ddcmi_cg_record *rec, int64_t *count);
+/* ddcmi_thermalize for an in-process group: every domain's own beads; RESCALE adds the domains' sums in rank order */
+int ddcmi_group_thermalize(ddcmi_ctx **ctxs, int n, int method, int select, int ntemp, const double *temperature, uint64_t seed, int64_t loop, int keep_vcm);
+/* what ddcmi_thermalize's BOLTZMANN would do with this context's owned beads, without writing a velocity: in the order of
+ * ddcmi_download_particles gid[k] and rejects[k], the draws the bead's three gasdev0 calls rejected (-1: its class has T < 0 and is left
+ * alone); *nout = the owned beads, cap the room (too small: DDCMI_EINVAL with *nout set).  The very kernel of the product. [sync] */
+int ddcmi_debug_thermalize_rejects(ddcmi_ctx *ctx, int select, int ntemp, const double *temperature, uint64_t seed, int64_t loop, int cap, int *nout,
+                                   uint64_t *gid, int *rejects);
 /* the lean step (a single domain of FREE beads without bonded terms: one launch per step, the second stage of its energy / virial /
  * kinetic sums formed for all pending steps at once): the sums of the steps of the last such launch, 32 doubles per step --
  * {lj, ele, virial xx yy zz xy xz yz} as the full list counts them (twice), {rk, tion xx yy zz xy xz yz}, 0, the bonded kernels'
