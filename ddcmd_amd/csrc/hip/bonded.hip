@@ -911,6 +911,49 @@ extern "C" int ddcmi_debug_bonded_layout(ddcmi_ctx *ctx, int out[2][12])
    }
    return DDCMI_OK;
 }
+/* test aids (include/ddcmi_test.h): reduce_gather_row through k_reduce_gather and k_reduce_gather_hist on the test's own rows, with the
+ * product's launch shapes.  Counts are checked on the host; the device outputs start as the caller's arrays. [sync] */
+extern "C" int ddcmi_debug_reduce_gather(int nblocks, int pstride, const double *partials, double *out)
+{
+   if (nblocks < 1 || pstride < nblocks || pstride > (1 << 20) || !partials || !out) return DDCMI_EINVAL;
+   const size_t np = (size_t)pstride * GB_NV;
+   double *d = nullptr;
+   if (hipMalloc((void **)&d, (np + R_SCR_REST) * sizeof(double)) != hipSuccess) return DDCMI_ENOMEM;
+   double *d_res = d + np;      /* the words of d_results up to the bonded blocks' end; the caller gets [R_SCR_BOND, R_SCR_REST) */
+   int rc = DDCMI_ENODEVICE;
+   if (hipMemcpy(d, partials, np * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
+       hipMemcpy(d_res + R_SCR_BOND, out, (R_SCR_REST - R_SCR_BOND) * sizeof(double), hipMemcpyHostToDevice) == hipSuccess)
+   {
+      hipLaunchKernelGGL(k_reduce_gather, dim3(GB_NV), dim3(RG_T), 0, 0, d, nblocks, pstride, d_res);
+      if (hipGetLastError() == hipSuccess && hipMemcpy(out, d_res + R_SCR_BOND, (R_SCR_REST - R_SCR_BOND) * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess) rc = DDCMI_OK;
+   }
+   (void)hipFree(d);
+   return rc;
+}
+extern "C" int ddcmi_debug_reduce_gather_hist(int nflush, const int *nsteps, int nblocks, int pstride, const double *partials, double *hist)
+{
+   if (nflush < 1 || nflush > 16 || !nsteps || nblocks < 1 || pstride < nblocks || pstride > (1 << 13) || !partials || !hist) return DDCMI_EINVAL;
+   for (int i = 0; i < nflush; i++) if (nsteps[i] < 1 || nsteps[i] > LEAN_W) return DDCMI_EINVAL;
+   const size_t bstride = (size_t)pstride * GB_NV, ring = bstride * LEAN_W, nh = (size_t)LEAN_HW * LEAN_W;      /* (bstride as the gather launch lays the ring out) */
+   double *d = nullptr;
+   if (hipMalloc((void **)&d, (ring + nh) * sizeof(double)) != hipSuccess) return DDCMI_ENOMEM;
+   double *d_hist = d + ring;
+   bool ok = hipMemset(d_hist, 0xff, nh * sizeof(double)) == hipSuccess;
+   size_t in_off = 0, h_off = 0;
+   for (int i = 0; ok && i < nflush; i++)
+   {
+      const int np = nsteps[i];
+      const size_t nin = bstride * np, nout = (size_t)LEAN_HW * np;
+      ok = hipMemcpy(d, partials + in_off, nin * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
+           hipMemcpy(d_hist, hist + h_off, nout * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+      if (!ok) break;
+      hipLaunchKernelGGL(k_reduce_gather_hist, dim3(GB_NV, np), dim3(RG_T), 0, 0, d, nblocks, pstride, bstride, d_hist);
+      ok = hipGetLastError() == hipSuccess && hipMemcpy(hist + h_off, d_hist, nout * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
+      in_off += nin; h_off += nout;
+   }
+   (void)hipFree(d);
+   return ok ? DDCMI_OK : DDCMI_ENODEVICE;
+}
 
 static GatherRows gather_rows(const ddcmi_ctx *ctx)
 {
@@ -1230,6 +1273,22 @@ __global__ void k_mol_sum(int nblk, const double *__restrict__ part, double *__r
    double s = 0.0;
    for (int b = 0; b < nblk; b++) s += part[3 * (size_t)b + c];
    out[c] = s;
+}
+/* test aid (include/ddcmi_test.h): k_mol_sum on the test's own part[nblk][3], launched as the product launches it; out[3] starts as the caller's. [sync] */
+extern "C" int ddcmi_debug_mol_sum(int nblk, const double *part, double *out)
+{
+   if (nblk < 1 || nblk > (1 << 20) || !part || !out) return DDCMI_EINVAL;
+   const size_t np = (size_t)3 * nblk;
+   double *d = nullptr;
+   if (hipMalloc((void **)&d, (np + 3) * sizeof(double)) != hipSuccess) return DDCMI_ENOMEM;
+   int rc = DDCMI_ENODEVICE;
+   if (hipMemcpy(d, part, np * sizeof(double), hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(d + np, out, 3 * sizeof(double), hipMemcpyHostToDevice) == hipSuccess)
+   {
+      hipLaunchKernelGGL(k_mol_sum, dim3(1), dim3(64), 0, 0, nblk, d, d + np);
+      if (hipGetLastError() == hipSuccess && hipMemcpy(out, d + np, 3 * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess) rc = DDCMI_OK;
+   }
+   (void)hipFree(d);
+   return rc;
 }
 /* molecularVirial (molecularPressure.c:23-56): sum over the beads of every molecule of (r - R) f on the
  * diagonal, R = the molecule's centre of mass; images are resolved relative to the molecule's first

@@ -665,8 +665,8 @@ extern "C" int ddcmi_create(ddcmi_ctx **out, int device)
    }
    (void)hipMemset(ctx->d_results, 0, R_SIZE * sizeof(double));
    (void)hipMemset(ctx->d_flags, 0, DDCMI_NFLAGS * sizeof(int));
-   if (ctx->red_tmp.ensure(2 * RED_SPLIT * 8 + 8)) { g_create_err = "context allocation failed"; delete ctx; return DDCMI_ENOMEM; }
-   (void)hipMemset(ctx->red_tmp.p, 0, (2 * RED_SPLIT * 8 + 8) * sizeof(double));      /* incl. the two ticket counters */
+   if (ctx->red_tmp.ensure(RED_TMP_DOUBLES)) { g_create_err = "context allocation failed"; delete ctx; return DDCMI_ENOMEM; }
+   (void)hipMemset(ctx->red_tmp.p, 0, RED_TMP_DOUBLES * sizeof(double));      /* incl. the two ticket counters */
    (void)hipDeviceSynchronize();      /* null-stream memsets are not ordered with the context's non-blocking stream */
    memset(ctx->h_results, 0, R_SIZE * sizeof(double));
    { const char *ov = getenv("DDCMI_HALO_OVERLAP"); ctx->halo_overlap = (ov && atoi(ov) != 0); }
@@ -1439,3 +1439,4 @@ extern "C" int ddcmi_timing_fused(ddcmi_ctx *ctx, int64_t *launches, double *tot
 #include "ddcmi_subset.inl"
 #include "ddcmi_coarsegrain.inl"
 #include "ddcmi_debug_primitives.inl"
+#include "ddcmi_debug_reductions.inl"

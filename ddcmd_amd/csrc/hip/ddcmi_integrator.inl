@@ -17,10 +17,12 @@ struct RedJob { const double *partials; int nblocks; int nv; double *out; int fi
 __device__ void finish_energy(double *r, double self_ele);
 /* RED_SPLIT workgroups share a job (one workgroup reading the 0.5 MB of per-tile partials of
  * a 4 M-bead box took 21 us); each leaves its 8 sums in tmp, the last one to arrive (ticket)
- * adds the RED_SPLIT rows in index order.  tmp: [2 jobs][RED_SPLIT][8] doubles, then 2 ticket
- * counters (left at zero). */
+ * adds the RED_SPLIT rows in index order.  tmp: [jobcap jobs][RED_SPLIT][8] doubles, then jobcap ticket
+ * counters (left at zero).  jobcap is the room tmp was made for, not the jobs of this launch: the tickets of a launch with fewer jobs
+ * must not lie in the rows an earlier, longer launch has written (k_reduce_hist). */
 #define RED_SPLIT 8
-__device__ __forceinline__ void reduce_jobs_block(const RedJob &j, const int bx, const int by, double *results, double self_ele, double *tmp, const int njobs = 2)
+#define RED_TMP_DOUBLES (2 * RED_SPLIT * 8 + 8)      /* the step's two jobs: rows, then the two ticket counters */
+__device__ __forceinline__ void reduce_jobs_block(const RedJob &j, const int bx, const int by, double *results, double self_ele, double *tmp, const int jobcap = 2)
 {
    __shared__ double s[1024];
    __shared__ int s_last;
@@ -53,7 +55,7 @@ __device__ __forceinline__ void reduce_jobs_block(const RedJob &j, const int bx,
       __syncthreads();
    }
    double *mytmp = tmp + ((size_t)by * RED_SPLIT + bx) * 8;
-   unsigned int *ticket = (unsigned int *)(tmp + (size_t)njobs * RED_SPLIT * 8) + by;
+   unsigned int *ticket = (unsigned int *)(tmp + (size_t)jobcap * RED_SPLIT * 8) + by;
    if (threadIdx.x < 8) { mytmp[threadIdx.x] = s[threadIdx.x]; __threadfence(); }
    __syncthreads();
    if (threadIdx.x == 0)
@@ -94,15 +96,17 @@ __global__ __launch_bounds__(1024) void k_reduce_jobs(RedJob j0, RedJob j1, doub
 }
 /* the lean steps' sums, all pending steps in ONE launch (ddcmi_ctx::lean_pending): step q's rows lie q * stride doubles behind the first
  * step's; its eight pair sums go to hist[LEAN_HW q], its seven kinetic sums to hist[LEAN_HW q + 8] -- the same workgroups, the same order of
- * additions as the per-step launch (reduce_jobs_block), so the sums are bit for bit the ones that launch forms */
-__global__ __launch_bounds__(1024) void k_reduce_hist(RedJob jf, RedJob jk, size_t stride, int nsteps, double *hist, double *tmp)
+ * additions as the per-step launch (reduce_jobs_block), so the sums are bit for bit the ones that launch forms.  tmp has room for the
+ * 2 LEAN_W jobs of a full ring (LEAN_TMP_DOUBLES); the tickets lie behind all of those rows however many steps are pending */
+#define LEAN_TMP_DOUBLES ((size_t)2 * LEAN_W * RED_SPLIT * 8 + 2 * LEAN_W)      /* rows, then the jobs' tickets (left at zero by their last workgroup) */
+__global__ __launch_bounds__(1024) void k_reduce_hist(RedJob jf, RedJob jk, size_t stride, double *hist, double *tmp)
 {
    const int by = (int)blockIdx.y, q = by >> 1;
    RedJob j = (by & 1) ? jk : jf;
    j.partials += (size_t)q * stride;
    j.out = hist + (size_t)LEAN_HW * q + ((by & 1) ? 8 : 0);
    j.finish = 0; j.disp_dt = 0.0; j.disp = nullptr;
-   reduce_jobs_block(j, (int)blockIdx.x, by, nullptr, 0.0, tmp, 2 * nsteps);
+   reduce_jobs_block(j, (int)blockIdx.x, by, nullptr, 0.0, tmp, 2 * LEAN_W);
 }
 /* the same two jobs and, in further workgroups of the same launch, the periodic images of a single domain brought up to the positions
  * the fused pair kernel has just drifted to (k_halo_update's self-image arm): both only wait for that kernel, one launch instead of two */

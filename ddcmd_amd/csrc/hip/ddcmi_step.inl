@@ -270,6 +270,13 @@ static int launch_forces(ddcmi_ctx *ctx, bool defer_reduce = false, FuseArgs *fu
    return DDCMI_OK;
 }
 
+/* the scratch of k_reduce_hist, zeroed once when it is made (every launch leaves its tickets at zero), and the launch itself: shared with
+ * ddcmi_debug_reduce_hist (include/ddcmi_test.h), so that the test runs on this layout and not on a restatement of it */
+static hipError_t lean_tmp_zero(double *tmp, hipStream_t st) { return hipMemsetAsync(tmp, 0, LEAN_TMP_DOUBLES * sizeof(double), st); }
+static void lean_launch_hist(const RedJob &jf, const RedJob &jk, size_t stride, int np, double *hist, double *tmp, hipStream_t st)
+{
+   hipLaunchKernelGGL(k_reduce_hist, dim3(RED_SPLIT, 2 * np), dim3(1024), 0, st, jf, jk, stride, hist, tmp);
+}
 /* the lean steps' pending sums, all in one launch (k_reduce_hist) */
 int ddcmi_lean_flush(ddcmi_ctx *ctx)
 {
@@ -278,14 +285,13 @@ int ddcmi_lean_flush(ddcmi_ctx *ctx)
    ctx->lean_pending = 0;
    if (!ctx->lean_tmp.p)
    {
-      const size_t nt = (size_t)2 * LEAN_W * RED_SPLIT * 8 + 2 * LEAN_W;      /* rows, then the jobs' tickets (left at zero by their last workgroup) */
-      ENSURE(ctx, ctx->lean_tmp, nt); ENSURE(ctx, ctx->lean_hist, (size_t)LEAN_HW * LEAN_W);
+      ENSURE(ctx, ctx->lean_tmp, LEAN_TMP_DOUBLES); ENSURE(ctx, ctx->lean_hist, (size_t)LEAN_HW * LEAN_W);
       HIPCHK(ctx, hipMemsetAsync(ctx->lean_hist.p, 0, (size_t)LEAN_HW * LEAN_W * sizeof(double), ctx->stream));
-      HIPCHK(ctx, hipMemsetAsync(ctx->lean_tmp.p, 0, nt * sizeof(double), ctx->stream));
+      HIPCHK(ctx, lean_tmp_zero(ctx->lean_tmp.p, ctx->stream));
    }
    RedJob jf = {ctx->lean_part.p, ctx->nitems, 8, nullptr, 0, 0.0, nullptr};
    RedJob jk = {ctx->lean_kpart.p, ctx->nitems, 7, nullptr, 0, 0.0, nullptr};
-   hipLaunchKernelGGL(k_reduce_hist, dim3(RED_SPLIT, 2 * np), dim3(1024), 0, ctx->stream, jf, jk, ctx->lean_stride, np, ctx->lean_hist.p, ctx->lean_tmp.p);
+   lean_launch_hist(jf, jk, ctx->lean_stride, np, ctx->lean_hist.p, ctx->lean_tmp.p, ctx->stream);
    if ((ctx->nbond + ctx->nangle + ctx->ntors) > 0) { int rcb = ddcmi_lean_flush_bonded(ctx, np); if (rcb) return rcb; }
    ctx->lean_hist_n = np;
    return DDCMI_OK;

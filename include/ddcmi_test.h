@@ -12,7 +12,8 @@
  *   ddcmi_debug_wave_ops       the wave's prefix sum, maximum and row sum and the decaying maximum of the lean steps' words, every lane's result
  *   ddcmi_debug_scan           the exclusive prefix sum of the rebuild on a context's stream and scratch array
  *   ddcmi_debug_sort_cells     the two in-cell sorts on the test's own cells and keys
- *   ddcmi_debug_thermalize_rejects  the rejected draws of every bead's BOLTZMANN stream */
+ *   ddcmi_debug_thermalize_rejects  the rejected draws of every bead's BOLTZMANN stream
+ *   ddcmi_debug_reduce_* / _block_reduce / _census_final / _kinetic_finish / _mol_sum  the cross-workgroup reductions on the test's own rows */
 #ifndef DDCMI_TEST_H
 #define DDCMI_TEST_H
 #include "ddcmi.h"
@@ -135,6 +136,41 @@ int ddcmi_debug_scan(ddcmi_ctx *ctx, int n, const int *in, int *out, int *total,
  * (unsigned) and key2[norder] (may be NULL), ascending (key, key2, entry); an entry of a cell outside [0, norder): DDCMI_EINVAL.  What lies
  * between the cells is left alone.  ncell <= 2^20, norder <= 2^24. */
 int ddcmi_debug_sort_cells(int ncell, const int *start, const int *cnt, int norder, int *order, const uint64_t *key, const int *key2);
+
+/* the cross-workgroup reductions, each on the caller's rows and on the current device (tests/test_gpu_reductions.py; tests/reductions.py restates
+ * their orders).  The very kernels of the product with the product's launch shapes.  Arguments out of range: DDCMI_EINVAL.  Every output array
+ * is also an input: the device array starts as the caller's, so that the caller's poison shows what no kernel wrote. [sync]
+ * ddcmi_debug_reduce_jobs: reduce_jobs_block on two jobs of part_q[nrows[q]][8], nv[q] in {0, 3, 7, 8}, finish = 0, disp_dt[q] >= 0 (> 0: column 7
+ * is a maximum and the job's displacement word, which starts as disp0[q], grows; not with nv = 8).  nlaunch <= 64 launches one after the other on ONE
+ * scratch array, sized and zeroed as ddcmi_create does it: front[l] = 0 k_reduce_jobs with grid (RED_SPLIT, 1) on job 0 alone, 1 k_reduce_jobs
+ * with grid (RED_SPLIT, 2), 2 k_reduce_jobs_images without images or messages.  out[l][q][8] and disp[l][q] are what launch l left (out[l] goes in
+ * before launch l; the displacement words carry on from launch to launch).  1 <= nrows <= 2^20. */
+int ddcmi_debug_reduce_jobs(int nlaunch, const int *front, const int nrows[2], const int nv[2], const double *part0, const double *part1,
+                            const double disp_dt[2], const double disp0[2], double *out, double *disp);
+/* ddcmi_debug_reduce_hist: k_reduce_hist as ddcmi_lean_flush launches it, nflush <= 16 flushes of nsteps[i] (1 ... 32) pending steps one after the
+ * other on ONE scratch array, made and zeroed once by the code ddcmi_lean_flush uses.  Step q of a flush has its nrows rows of 8 doubles
+ * q * stride doubles behind the flush's first (stride >= 8 nrows, nrows <= 8192, stride <= 2^17); pair[] (8 sums) and kin[] (7 sums) hold the
+ * flushes' rings one behind the other, nsteps[i] * stride doubles each.  hist[]: 32 doubles per step, flush behind flush; flush i's
+ * part goes in before its launch and comes back after it. */
+int ddcmi_debug_reduce_hist(int nflush, const int *nsteps, int nrows, long long stride, const double *pair, const double *kin, double *hist);
+/* ddcmi_debug_reduce_gather: k_reduce_gather on partials[10][pstride], nblocks <= pstride <= 2^20 values per row; out[24] = the words
+ * [R_SCR_BOND, R_SCR_REST) of the results: {e_bond, virial xx yy zz xy xz yz, -}, {e_angle, 0 x 6, -}, {e_tors, e_impr, 0 x 6}.
+ * ddcmi_debug_reduce_gather_hist: k_reduce_gather_hist on flushes of nsteps[i] steps, step q's ten rows 10 * pstride * q doubles behind the first
+ * (pstride <= 2^13); partials[] and hist[] as for ddcmi_debug_reduce_hist (the sums are words 16 ... 25 of a step). */
+int ddcmi_debug_reduce_gather(int nblocks, int pstride, const double *partials, double *out);
+int ddcmi_debug_reduce_gather_hist(int nflush, const int *nsteps, int nblocks, int pstride, const double *partials, double *hist);
+/* ddcmi_debug_block_reduce: one workgroup of 256 threads per block, nblocks <= 4096, out[nblocks][16].  which = 0, 1, 2: in[nblocks][256][NV]
+ * doubles through block_reduce_store<NV, 4>, NV = 7, 3, 12 (KD_NV), into out[block][0 ... NV); which = 3, 4: in[nblocks][256] floats, none
+ * negative or NaN, through block_vmax_store<4> / block_vmax_store<DDCMI_BLOCK / 64> into out[block][7]. */
+int ddcmi_debug_block_reduce(int which, int nblocks, const void *in, double *out);
+/* ddcmi_debug_census_final: k_census_final on part_d[nwg][nd] and part_c[nwg][nc] (either may be empty; nwg <= 2048, nd, nc <= 65536), grid of
+ * 64-thread workgroups over the longer of the two; which = 0 <RowsSum, double> (out_c doubles), 1 <RowsSum, long long>, 2 <RowsSumMinMax, long long>
+ * (out_c 64-bit integers). */
+int ddcmi_debug_census_final(int which, int nwg, int nd, const double *part_d, double *out_d, int nc, const unsigned *part_c, void *out_c);
+/* ddcmi_debug_kinetic_finish: which = 0 k_group_ke_sum on part[512][2 n] (n groups <= 32), out[2 n]; 1 k_class_kinetic_sum on part[512][n][16]
+ * (n classes <= 64), out[n][12].  ddcmi_debug_mol_sum: k_mol_sum on part[nblk][3], out[3]; nblk <= 2^20. */
+int ddcmi_debug_kinetic_finish(int which, int n, const double *part, double *out);
+int ddcmi_debug_mol_sum(int nblk, const double *part, double *out);
 
 /* roctx ranges opened so far (DDCMI_ROCTX=1: MDSTEP, DDCENERGY, CHARMM_NONBOND ... named like ptiming.h's regions; 0 without the variable) */
 long ddcmi_debug_roctx_ranges(void);

@@ -646,6 +646,45 @@ def test_lean_steps_equal_steps_with_a_reduction_launch_each(case, monkeypatch):
     a.close(); b.close()
 
 
+def test_lean_history_of_a_shorter_run_after_a_longer_one(monkeypatch):
+    """The lean steps' sums are formed by one launch per read-out, however many steps are pending.  The history of a long run of lean steps and
+    then, in the same context, of a shorter one: both equal to the energies, virial and kinetic terms DDCMI_NO_LEAN_STEP=1 reports step by
+    step.  (The second launch once looked for its tickets among the rows the first had left: none of its workgroups took itself for the last,
+    no sum was stored, and the read-out returned the first run's numbers.)  A call's last step is split, so a read-out holds the lean steps
+    in front of the last step taken."""
+    from ddcmd_amd.martini import MartiniHIP
+    import os
+    if any(os.environ.get(k) for k in ("DDCMI_NO_LEAN_STEP", "DDCMI_NO_SELF_IMAGES", "DDCMI_NO_FUSED_STEP")):
+        pytest.skip("the lean step is switched off in this environment")
+    s = make_water_setup(14, temperature_K=310.0)
+    calls = (16, 7)
+    monkeypatch.setenv("DDCMI_NO_LEAN_STEP", "1")
+    a = MartiniHIP(s)
+    monkeypatch.delenv("DDCMI_NO_LEAN_STEP")
+    b = MartiniHIP(s, test_api=True)
+    a.eval_forces(); b.eval_forces()
+    per_step, reads, done = [], [], 0
+    for n in calls:
+        for k in range(n):
+            a.step(1)
+            per_step.append(a.energies())
+        b.step(n)
+        done += n
+        reads.append((done, b.lean_history()))
+    assert len(reads[0][1]) == calls[0] - 1 and 1 <= len(reads[1][1]) < len(reads[0][1]), [len(h) for _, h in reads]
+    for done, h in reads:
+        first = done - 1 - len(h)
+        for k in range(len(h)):
+            e, vir, rk, tion = per_step[first + k]
+            assert abs(0.5 * h[k, 0] - e["lj"]) <= 1e-12 * abs(e["lj"]), (done, k)
+            assert np.abs(0.5 * h[k, 2:8] + h[k, 20:26] - vir).max() <= 1e-12 * np.abs(vir).max(), (done, k)
+            assert abs(h[k, 8] - rk) <= 1e-12 * rk, (done, k)
+            assert np.abs(h[k, 9:15] - tion).max() <= 1e-12 * np.abs(tion).max(), (done, k)
+    ea, eb = a.energies(), b.energies()
+    assert ea[0] == eb[0] and np.array_equal(ea[1], eb[1]) and ea[2] == eb[2]
+    a.close(); b.close()
+
+
 def test_rows_end_at_the_last_shell_that_can_matter(monkeypatch):
     """the pair kernel ends every row at the last distance shell a pair could have left since the rebuild (the displacement
     bound D = sum of the steps' max |dt v|, kept by the fused step): entries of later shells lay further than r_cut + 2 D from
