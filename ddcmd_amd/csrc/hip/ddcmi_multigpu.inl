@@ -114,8 +114,9 @@ __global__ void k_mig_classify(MigGeom mg, int nloc, int mig_cap, double4 *pos, 
       int b = (int)floor((r[a] + 0.5 * mg.L[a]) / mg.W[a]);
       b = min(max(b, 0), mg.P[a] - 1);
       int dd = b - mg.pc[a];
-      if (dd > 1) dd -= mg.P[a];
-      if (dd < -1) dd += mg.P[a];
+      /* across the periodic face the other neighbour is one brick away; an open axis has no such neighbour: folded, a hop from
+       * brick 0 to brick P - 1 became a direction without destination, counted as leaving and delivered to nobody */
+      if ((mg.pbc >> a) & 1) { if (dd > 1) dd -= mg.P[a]; if (dd < -1) dd += mg.P[a]; }
       if (dd > 1 || dd < -1) { atomicMax(&flags[6], 1); atomicMax(&dir_cnt[29], 1); dd = 0; }      /* [29] travels with the counts: every rank learns of it in the same round */
       d[a] = dd;
    }
@@ -1158,7 +1159,19 @@ static int group_refresh_vel(ddcmi_group *g)
 static int group_rebuild(ddcmi_group *g)
 {
    int rc;
-   for (ddcmi_ctx *c : g->ranks) { (void)hipSetDevice(c->device); if ((rc = mg_phase1_migrate_out(c))) return rc; }
+   /* a bead further than one domain away: every domain classifies, and every domain's context says so -- as between processes, where
+    * the flag travels with the counts (dir_cnt[29]) and all ranks fail in the same round */
+   bool far = false;
+   for (ddcmi_ctx *c : g->ranks)
+   {
+      (void)hipSetDevice(c->device);
+      if ((rc = mg_phase1_migrate_out(c))) { if (rc == DDCMI_EINVAL && c->err.find("further than one domain") != std::string::npos) far = true; else return rc; }
+   }
+   if (far)
+   {
+      for (ddcmi_ctx *c : g->ranks) c->err = "a bead moved further than one domain between rebuilds";
+      return DDCMI_EINVAL;
+   }
    for (ddcmi_ctx *B : g->ranks)
    {
       int acc = 0;

@@ -882,13 +882,17 @@ def plan_directions(px, py, pz, rank, pbc=7):
 
 
 def domain_of(setup, grid):
-    """owner rank of every bead for a px*py*pz brick decomposition (box centred on the origin)"""
+    """owner rank of every bead for a px*py*pz brick decomposition (box centred on the origin); a bead outside the box on an open
+    axis belongs to the edge brick on its side, as k_mig_classify has it"""
     px, py, pz = grid
     L = setup.box
     out = np.zeros(setup.natoms, np.int64)
     mult = 1
+    pbc = int(getattr(setup, "pbc", 7))
     for a, (r, P) in enumerate(zip((setup.rx, setup.ry, setup.rz), (px, py, pz))):
-        x = r - L[a] * np.rint(r / L[a])
+        x = np.asarray(r, float)
+        if (pbc >> a) & 1:
+            x = x - L[a] * np.rint(x / L[a])
         b = np.clip(np.floor((x + 0.5 * L[a]) / (L[a] / P)).astype(np.int64), 0, P - 1)
         out += mult * b
         mult *= P
