@@ -594,6 +594,7 @@ __global__ void k_merge_cells(int ncell, int nloc, const int *cnt_o, const int *
    cell_cnt[c] = co + ch;
 }
 
+#include "ddcmi_transport.inl"
 #include "ddcmi_listbuild.inl"
 #include "ddcmi_nonbond.inl"
 #include "ddcmi_integrator.inl"
@@ -784,7 +785,7 @@ __global__ void k_retag(int n, const int *species, const int *nb_of_sp, double4 
  * upload stayed (tools/fuzz_sequence.py).  Decomposed ranks sum it on the device at every rebuild (ddcmi_multigpu.inl). */
 static void update_self_ele(ddcmi_ctx *ctx)
 {
-   if (ctx->nranks > 1 || ctx->loopback || ctx->group_ || ctx->sp_count.empty()) return;
+   if (decomposed(ctx) || ctx->sp_count.empty()) return;
    double q2 = 0.0;
    for (size_t sp = 0; sp < ctx->sp_count.size() && sp < ctx->charge.size(); sp++) q2 += (double)ctx->sp_count[sp] * ctx->charge[sp] * ctx->charge[sp];
    ctx->self_ele = -0.5 * q2 * ctx->keR * ctx->crf;
@@ -966,6 +967,7 @@ extern "C" int ddcmi_set_barostat(ddcmi_ctx *ctx, double T, double P0, double be
           "ddcmi_set_barostat: beta = %g must be >= 0 (0 = off) and, when on, tau = %g > 0 with finite T = %g >= 0 and P0 = %g", beta, tau, T, P0);
    if (beta > 0.0)
    {
+      /* (not decomposed(): a loopback rank owns every bead, its sums are the run's) */
       if (ctx->nranks > 1 || ctx->group_) SETERR(ctx, DDCMI_EUNSUPPORTED, "the barostat is implemented for a single domain");
    }
    ctx->baro_T = T; ctx->baro_P0 = P0; ctx->baro_beta = beta; ctx->baro_tau = tau;
@@ -999,7 +1001,6 @@ extern "C" int ddcmi_set_random(ddcmi_ctx *ctx, uint64_t seed)
 
 /* RANDOM type LCG64: the particles' own streams (LCG64_PARM records in the caller order of ddcmi_upload_state).  On the device
  * they lie in slot order like every other per-bead array and move with the beads (k_gather_state, the migration records). */
-static inline bool lcg_decomposed(const ddcmi_ctx *ctx) { return ctx->nranks > 1 || ctx->loopback || ctx->group_ != nullptr; }
 extern "C" int ddcmi_set_random_lcg64(ddcmi_ctx *ctx, int n, const uint64_t *state, const uint32_t *multID, const uint32_t *prime)
 {
    if (!ctx) return DDCMI_EINVAL;
@@ -1007,7 +1008,7 @@ extern "C" int ddcmi_set_random_lcg64(ddcmi_ctx *ctx, int n, const uint64_t *sta
    if (n == 0 || !state) { ctx->lcg_on = false; return DDCMI_OK; }      /* back to the counter-based stream */
    if (!multID || !prime) SETERR(ctx, DDCMI_EINVAL, "ddcmi_set_random_lcg64: multID and prime are needed with the states");
    if (n != ctx->nloc) SETERR(ctx, DDCMI_EINVAL, "ddcmi_set_random_lcg64: %d records for %d uploaded beads", n, ctx->nloc);
-   if (lcg_decomposed(ctx) && ctx->nrebuild > 0)
+   if (decomposed(ctx) && ctx->nrebuild > 0)
       SETERR(ctx, DDCMI_EINVAL, "ddcmi_set_random_lcg64: the beads of a decomposed run leave their caller order at the first list build; set the streams after ddcmi_upload_state");
    for (int i = 0; i < n; i++)      /* lcg64_checkValue (lcg64.c:111-120) */
       if (multID[i] > 2 || state[i] == 0 || prime[i] % 2 == 0) SETERR(ctx, DDCMI_EINVAL, "ddcmi_set_random_lcg64: record %d {%llx %u %x} is not a valid LCG64 state", i, (unsigned long long)state[i], multID[i], prime[i]);
@@ -1037,7 +1038,7 @@ extern "C" int ddcmi_get_random_lcg64(ddcmi_ctx *ctx, int n, uint64_t *state, ui
    std::vector<int> orig((size_t)n);
    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
    HIPCHK(ctx, hipMemcpy(h.data(), ctx->lcg.p, (size_t)n * sizeof(ulonglong2), hipMemcpyDeviceToHost));
-   const bool by_slot = lcg_decomposed(ctx);      /* a decomposed run: the order of ddcmi_download_particles */
+   const bool by_slot = decomposed(ctx);      /* a decomposed run: the order of ddcmi_download_particles */
    if (!by_slot) HIPCHK(ctx, hipMemcpy(orig.data(), ctx->orig.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
    for (int k = 0; k < n; k++)
    {
@@ -1182,6 +1183,7 @@ extern "C" int ddcmi_upload_positions(ddcmi_ctx *ctx, const double *rx, const do
    if (ctx) { ctx->shell_skip = false; ctx->images_fresh = false; ctx->pack_fresh = false; }
    if (!ctx || !rx || !ry || !rz) return DDCMI_EINVAL;
    if (ctx->nloc <= 0) SETERR(ctx, DDCMI_EINVAL, "ddcmi_upload_positions needs an uploaded state (ddcmi_upload_state)");
+   /* (not decomposed(): a loopback rank migrates no bead) */
    if (ctx->nranks > 1 || ctx->group_) SETERR(ctx, DDCMI_EUNSUPPORTED, "ddcmi_upload_positions: caller-order arrays do not survive migration between domains");
    (void)hipSetDevice(ctx->device);
    const int n = ctx->nloc, nb = cdiv(n, 256);
@@ -1266,7 +1268,7 @@ extern "C" int ddcmi_kinetic(ddcmi_ctx *ctx, double *rk, double *tion)
 }
 
 /* per-group {kinetic energy, bead count} of this rank's beads -> h_results[R_GROUP..];
- * over RCCL the sums are all-reduced first (energyInfo.c:75-112 allreduce) */
+ * over a transport the sums are all-reduced first (energyInfo.c:75-112 allreduce) */
 int ddcmi_group_ke_sums(ddcmi_ctx *ctx)
 {
    (void)hipSetDevice(ctx->device);
@@ -1276,15 +1278,9 @@ int ddcmi_group_ke_sums(ddcmi_ctx *ctx)
    hipLaunchKernelGGL(k_group_ke, dim3(GKE_BLOCKS), dim3(DDCMI_BLOCK), 0, st, n, ng, ctx->d_mass.p, ctx->species.p, ctx->group.p,
                       ctx->vx.p, ctx->vy.p, ctx->vz.p, ctx->kpartials.p);
    hipLaunchKernelGGL(k_group_ke_sum, dim3(1), dim3(64), 0, st, ng, ctx->kpartials.p, ctx->d_results + R_GROUP);
-   if ((ctx->nranks > 1 || ctx->loopback) && ctx->comm && !ctx->group_ && ng > 0)
-      if (ncclAllReduce(ctx->d_results + R_GROUP, ctx->d_results + R_GROUP, 2 * ng, ncclDouble, ncclSum, (ncclComm_t)ctx->comm, st) != ncclSuccess)
-         SETERR(ctx, DDCMI_ECOMM, "ncclAllReduce of the group kinetic energies failed");
-   int rc = fetch_results(ctx);
-   if (rc) return rc;
-   if ((ctx->nranks > 1 || ctx->loopback) && ctx->hcomm && !ctx->group_ && ng > 0)      /* host transport: summed on the host copy */
-      if (ddcmi_rdzv_allreduce_f64(ctx->hcomm, ctx->h_results + R_GROUP, 2 * ng, 0) != DDCMI_OK)
-         SETERR(ctx, DDCMI_ECOMM, "all-reduce of the group kinetic energies failed: %s", ddcmi_rdzv_last_error(ctx->hcomm));
-   return DDCMI_OK;
+   int rc;
+   if (!ctx->group_ && (rc = mg_allreduce_device(ctx, ctx->d_results + R_GROUP, 2 * (size_t)ng))) return rc;
+   return fetch_results(ctx);
 }
 extern "C" int ddcmi_group_temperatures(ddcmi_ctx *ctx, double *Tgroup)
 {
@@ -1333,7 +1329,7 @@ extern "C" int ddcmi_comm_stats(const ddcmi_ctx *ctx, int64_t stats[8])
    int v = 0;
    (void)ncclGetVersion(&v);
    stats[0] = ctx->nsend; stats[1] = ctx->nrecv; stats[2] = ctx->hmsg_s.n; stats[3] = ctx->hmsg_r.n;
-   stats[4] = v; stats[5] = ctx->comm ? (ctx->loopback ? 3 : 1) : ctx->hcomm ? 2 : 0;
+   stats[4] = v; stats[5] = transport_kind(ctx);
    stats[6] = ctx->nranks; stats[7] = ctx->rank;
    return DDCMI_OK;
 }
@@ -1342,7 +1338,7 @@ extern "C" int ddcmi_comm_peer_stats(const ddcmi_ctx *ctx, int cap, int *peer, i
 {
    if (!ctx || cap < 0) return -1;
    const HaloMsgs &ms = ctx->hmsg_s, &mr = ctx->hmsg_r;
-   if (!ctx->comm && !ctx->hcomm) return 0;
+   if (transport_kind(ctx) == 0) return 0;
    for (int k = 0; k < ms.n && k < cap; k++)
    {
       if (peer) peer[k] = ms.peer[k];
@@ -1428,6 +1424,7 @@ extern "C" int ddcmi_timing_fused(ddcmi_ctx *ctx, int64_t *launches, double *tot
 }
 
 #include "ddcmi_multigpu.inl"
+#include "ddcmi_preflight.inl"
 #include "ddcmi_census_frame.inl"
 #include "ddcmi_analysis.inl"
 #include "ddcmi_vaf.inl"

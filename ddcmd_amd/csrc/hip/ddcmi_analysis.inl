@@ -367,7 +367,7 @@ extern "C" int ddcmi_group_pair_correlation(ddcmi_ctx **ctxs, int n, double rmin
                             if (g->ranks[0]->nranks > 1)
                             {
                                for (ddcmi_ctx *c : g->ranks) if ((rc = pc_pack(c))) return rc;
-                               if ((rc = mg_xchg_data_local(g, 3))) return rc;
+                               if ((rc = group_exchange(g, 4, [](const ddcmi_ctx *c) { return group_halo_side(c, c->pc_send.p, c->pc_recv.p); }))) return rc;
                             }
                             return (int)DDCMI_OK;
                          },

@@ -514,7 +514,7 @@ struct PostJobs
 };
 int ddcmi_post(ddcmi_ctx *ctx, hipStream_t st, PostJobs &j);            /* device arrays -> the mailbox; fills j.off */
 int ddcmi_post_wait(ddcmi_ctx *ctx, hipStream_t st);                    /* spin until the post has landed */
-int ddcmi_agree_poll(ddcmi_ctx *ctx);                                   /* in front of a host wait: has a peer reported a failed rebuild? (ddcmi_multigpu.inl) */
+int ddcmi_agree_poll(ddcmi_ctx *ctx);                                   /* in front of a host wait: has a peer reported a failed rebuild? (ddcmi_transport.inl) */
 int ddcmi_fetch(ddcmi_ctx *ctx, hipStream_t st, int *dst, const int *src_host_mapped, int n);
 struct TailJobs
 {

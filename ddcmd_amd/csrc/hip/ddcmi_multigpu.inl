@@ -12,10 +12,13 @@
  * destination rank and a periodic shift; a direction whose destination is the
  * rank itself (undivided periodic axis) yields local image beads, exactly like
  * the single-domain path.  Halo beads live in the image slots behind the owned
- * beads; the sender applies the shift.  Transport is RCCL point-to-point
- * (grouped ncclSend/ncclRecv, one message per direction: 7 distinct peers at
- * 2x2x2 = the 7 xGMI links) or, for tests on one GPU, direct copies between
- * contexts of one process (ddcmi_group_*).
+ * beads; the sender applies the shift.  The data travel through the context's
+ * transport (ddcmi_transport.inl: RCCL point-to-point, grouped sends and receives,
+ * one message per peer: 7 distinct peers at 2x2x2 = the 7 xGMI links; or the host
+ * rendezvous) or, for tests on one GPU, by direct copies between contexts of one
+ * process (ddcmi_group_*).  This file holds the direction plan, the migration and
+ * halo kernels, the rebuild's phases and the in-process group; it does not ask
+ * which transport a context has.
  */
 
 struct DirTab
@@ -351,7 +354,7 @@ static int mg_ensure_owned(ddcmi_ctx *ctx, size_t need)
    return DDCMI_OK;
 }
 
-/* ---- transport ------------------------------------------------------------ */
+/* ---- which directions travel ---------------------------------------------------- */
 struct ddcmi_group { std::vector<ddcmi_ctx *> ranks; };
 
 /* loopback: a single rank sends its periodic images to itself through the transport, so the whole
@@ -360,10 +363,6 @@ static inline bool dir_remote(const int *dest, int rank, bool loopback, int code
 static inline bool mg_remote(const ddcmi_ctx *ctx, int code) { return dir_remote(ctx->dir_dest, ctx->rank, ctx->loopback, code); }
 static inline bool mg_selfdir(const ddcmi_ctx *ctx, int code) { return code != 13 && ctx->dir_dest[code] == ctx->rank && !ctx->loopback; }
 static inline int mg_opp(int code) { return 26 - code; }
-static inline bool mg_transport(const ddcmi_ctx *ctx) { return ctx->comm != nullptr || ctx->hcomm != nullptr; }
-
-#define NCCLCHK2(ctx, call) do { ncclResult_t _r = (call); if (_r != ncclSuccess) SETERR(ctx, DDCMI_ECOMM, "%s failed: %s", #call, ncclGetErrorString(_r)); } while (0)
-#define HOSTCHK(ctx, call) do { int _r = (call); if (_r != DDCMI_OK) SETERR(ctx, DDCMI_ECOMM, "%s failed: %s", #call, ddcmi_rdzv_last_error((ctx)->hcomm)); } while (0)
 
 /* ---- host logic shared by every transport (and callable without a GPU) ------ */
 /* what this rank receives, from the all-gathered send counts: the message a neighbour sends along ITS
@@ -372,6 +371,13 @@ static void plan_recv_counts(const int *dest, int rank, bool loopback, const int
 {
    for (int code = 0; code < 27; code++)
       rcnt[code] = dir_remote(dest, rank, loopback, mg_opp(code)) ? all_counts[27 * dest[mg_opp(code)] + code] : 0;
+}
+/* the arriving migrants lie flattened by the SENDER's direction code: the segments' offsets, and their total */
+static int mig_recv_offsets(const int *rcnt, int *roff)
+{
+   int acc = 0;
+   for (int c = 0; c < 27; c++) { roff[c] = acc; acc += rcnt[c]; }
+   return acc;
 }
 /* buffer layout of the halo exchange from the per-direction counts: remote segments ordered by
  * (peer rank, direction code) on both sides, so the segments of one peer are contiguous and travel as
@@ -446,8 +452,7 @@ extern "C" int ddcmi_plan_halo_layout(int px, int py, int pz, int rank, int pbc,
  * The block of a rank is 32 ints: slot 28 carries the rank's pending error code (local_err: an allocation or a check that
  * failed on the way to this round), slot 29 the device's "a bead moved further than one domain" flag -- so a hard error
  * of ONE rank ends the rebuild on EVERY rank in the same round, instead of leaving the others inside the next exchange.
- * RCCL: the all-gather reads dir_cnt on the device; host transport: the rendezvous' all-gather after the download. */
-#define MG_BLK 32
+ * How the blocks travel: mg_gather_counts (ddcmi_transport.inl). */
 static int mg_counts_round(ddcmi_ctx *ctx, int *scnt, int *rcnt, bool *any_over, int *my_max, bool with_flags, int local_err)
 {
    hipStream_t st = ctx->stream;
@@ -457,7 +462,6 @@ static int mg_counts_round(ddcmi_ctx *ctx, int *scnt, int *rcnt, bool *any_over,
    int *h = ctx->pinned(2, 64 + (MG_BLK + 27) * (size_t)nr);
    if (!h) SETERR(ctx, DDCMI_ENOMEM, "pinned staging for the count exchange");
    int *all = h + 64, *packed = h + 64 + MG_BLK * (size_t)nr;
-   if (with_flags && ctx->hcomm) HIPCHK(ctx, hipMemcpyAsync(ctx->h_flags, ctx->d_flags, 8 * sizeof(int), hipMemcpyDeviceToHost, st));
    if (ctx->dir_cnt.cap < MG_BLK && ctx->dir_cnt.ensure(MG_BLK)) SETERR(ctx, DDCMI_ENOMEM, "direction counters");
    if (local_err)
    {
@@ -466,24 +470,7 @@ static int mg_counts_round(ddcmi_ctx *ctx, int *scnt, int *rcnt, bool *any_over,
       h[32 + 28] = local_err;
       HIPCHK(ctx, hipMemcpyAsync(ctx->dir_cnt.p, h + 32, MG_BLK * sizeof(int), hipMemcpyHostToDevice, st));
    }
-   if (ctx->hcomm)
-   {
-      HIPCHK(ctx, hipMemcpyAsync(h, ctx->dir_cnt.p, MG_BLK * sizeof(int), hipMemcpyDeviceToHost, st));
-      HIPCHK(ctx, hipStreamSynchronize(st));
-      HOSTCHK(ctx, ddcmi_rdzv_allgather(ctx->hcomm, h, all, MG_BLK * sizeof(int)));
-   }
-   else
-   {
-      ENSURE(ctx, ctx->cnt_xchg, 32 + MG_BLK * (size_t)nr);
-      NCCLCHK2(ctx, ncclAllGather(ctx->dir_cnt.p, ctx->cnt_xchg.p + 32, MG_BLK, ncclInt, (ncclComm_t)ctx->comm, st));
-      /* every rank's block (and this rank's flags) through the mailbox: no copy call that waits, no late wake-up (scan.hip) */
-      PostJobs pj;
-      pj.add(ctx->cnt_xchg.p + 32, MG_BLK * (size_t)nr).add(ctx->d_flags, 8);
-      int rcp;
-      if ((rcp = ddcmi_post(ctx, st, pj)) || (rcp = ddcmi_post_wait(ctx, st))) return rcp;
-      memcpy(all, ctx->mbox.h + pj.off[0], MG_BLK * (size_t)nr * sizeof(int));
-      if (with_flags) memcpy(ctx->h_flags, ctx->mbox.h + pj.off[1], 8 * sizeof(int));
-   }
+   { int rcg = mg_gather_counts(ctx, h, all, with_flags); if (rcg) return rcg; }
    *any_over = false;
    for (int r = 0; r < nr; r++)
    {
@@ -509,269 +496,73 @@ static int mg_counts_round(ddcmi_ctx *ctx, int *scnt, int *rcnt, bool *any_over,
    plan_recv_counts(ctx->dir_dest, ctx->rank, ctx->loopback, packed, rcnt);
    return DDCMI_OK;
 }
-static int mg_fatal(ddcmi_ctx *ctx, int code, const char *msg);
-/* the ranks agree on the outcome of a phase that has no count round behind it: max of the error codes (one small collective) */
-static int mg_agree(ddcmi_ctx *ctx, int local_rc)
-{
-   if ((ctx->nranks == 1 && !ctx->loopback) || !mg_transport(ctx)) return local_rc;
-   const std::string local_msg = ctx->err;
-   hipStream_t st = ctx->stream;
-   int worst = local_rc < 0 ? -local_rc : local_rc;
-   if (ctx->hcomm)
-   {
-      double v = (double)worst;
-      HOSTCHK(ctx, ddcmi_rdzv_allreduce_f64(ctx->hcomm, &v, 1, 1));
-      worst = (int)v;
-   }
-   else
-   {
-      int *h = ctx->pinned(2, 64);
-      if (!h) SETERR(ctx, DDCMI_ENOMEM, "pinned staging for the count exchange");
-      ENSURE(ctx, ctx->cnt_xchg, 32);
-      h[0] = worst;
-      HIPCHK(ctx, hipMemcpyAsync(ctx->cnt_xchg.p, h, sizeof(int), hipMemcpyHostToDevice, st));
-      NCCLCHK2(ctx, ncclAllReduce(ctx->cnt_xchg.p, ctx->cnt_xchg.p + 1, 1, ncclInt, ncclMax, (ncclComm_t)ctx->comm, st));
-      PostJobs pj;
-      pj.add(ctx->cnt_xchg.p + 1, 1);
-      int rcp;
-      if ((rcp = ddcmi_post(ctx, st, pj)) || (rcp = ddcmi_post_wait(ctx, st))) return rcp;
-      worst = ctx->mbox.h[pj.off[0]];
-   }
-   if (local_rc) { ctx->err = local_msg; return local_rc; }
-   if (worst) SETERR(ctx, DDCMI_ECOMM, "another rank failed during the list rebuild (error %d): its own message says why", worst);
-   return DDCMI_OK;
-}
-/* The same agreement without anybody waiting for it (RCCL transport, rebuilds after the first two).  ADVICE r3: from the third
- * rebuild on a rank whose local phase failed (a bond stretched beyond the halo in a system going unstable, a capacity, an
- * allocation) used to abort its communicator and return, and its peers sat in the next halo kernel until something outside
- * killed the job.  Now every rank contributes its error code to an all-reduce (max) queued behind the phase's kernels, a post
- * kernel leaves the result in mapped host memory, and nobody waits: the failing rank returns its own error once the
- * collective has run; a healthy rank goes on queueing steps and looks at the word in front of its next host wait (ddcmi_agree_poll:
- * the next rebuild's count round, a read of energies, a download, ddcmi_sync) -- the word lands BEFORE the exchange the failed
- * peer never joins, so the look cannot hang, and a reported failure aborts the communicator (which releases the waiting
- * kernels) and returns DDCMI_ECOMM naming the rebuild.  Cost: one small collective per rebuild on the stream, no host wait. */
-__global__ void k_agree_post(const int *src, int *dst, int seq)
-{
-   if (threadIdx.x == 0)
-   {
-      dst[1] = *src;
-      __threadfence_system();
-      __hip_atomic_store(dst, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-   }
-}
-static int mg_agree_async(ddcmi_ctx *ctx, int local_rc, int pretend_peer_code = 0 /* tests: the code a failed peer would have contributed */)
-{
-   hipStream_t st = ctx->stream;
-   if (!ctx->agree.h)
-   {
-      if (ctx->agree.ensure(16, 0)) return mg_agree(ctx, local_rc);
-      memset(ctx->agree.h, 0, 16 * sizeof(int));
-   }
-   { int rcp = ddcmi_agree_poll(ctx); if (rcp && !local_rc) return rcp; }      /* (never two agreements in flight) */
-   const std::string local_msg = ctx->err;
-   int *h = ctx->pinned(2, 64);
-   if (!h) return mg_agree(ctx, local_rc);
-   h[0] = std::max(local_rc < 0 ? -local_rc : local_rc, pretend_peer_code);
-   int *d = ctx->d_flags + DDCMI_FLAG_AGREE;
-   /* (a rebuild that went well contributes the zero its tail launch left there: no copy) */
-   if (h[0] != 0 || !ctx->list_valid) HIPCHK(ctx, hipMemcpyAsync(d, h, sizeof(int), hipMemcpyHostToDevice, st));
-   NCCLCHK2(ctx, ncclAllReduce(d, d + 1, 1, ncclInt, ncclMax, (ncclComm_t)ctx->comm, st));
-   ctx->agree_seq++;
-   hipLaunchKernelGGL(k_agree_post, dim3(1), dim3(64), 0, st, d + 1, ctx->agree.d, ctx->agree_seq);
-   ctx->agree_pending = true; ctx->agree_loop = ctx->loop;
-   if (local_rc)
-   {
-      /* this rank's own failure: it has told the others; it returns once the collective has run (its peers all join it) */
-      (void)hipStreamSynchronize(st);
-      ctx->agree_pending = false;
-      ctx->err = local_msg;
-      return local_rc;
-   }
-   return DDCMI_OK;
-}
-int ddcmi_agree_poll(ddcmi_ctx *ctx)
-{
-   if (!ctx->agree_pending) return DDCMI_OK;
-   volatile int *flag = ctx->agree.h;
-   struct timespec t0; clock_gettime(CLOCK_MONOTONIC, &t0);
-   for (unsigned long spin = 0;; spin++)
-   {
-      if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == ctx->agree_seq) break;
-      if ((spin & 0xff) == 0xff)
-      {
-         struct timespec t1; clock_gettime(CLOCK_MONOTONIC, &t1);
-         if ((t1.tv_sec - t0.tv_sec) + 1e-9 * (t1.tv_nsec - t0.tv_nsec) > 20.0)
-         {
-            ctx->agree_pending = false;
-            return mg_fatal(ctx, DDCMI_ECOMM, "the ranks' agreement on the last list rebuild did not arrive within 20 s: a peer rank is gone");
-         }
-         sched_yield();
-      }
-   }
-   ctx->agree_pending = false;
-   const int worst = ctx->agree.h[1];
-   if (worst)
-   {
-      char b[256];
-      snprintf(b, sizeof(b), "another rank failed during the list rebuild at loop %lld (error %d): its own message says why", (long long)ctx->agree_loop, worst);
-      return mg_fatal(ctx, DDCMI_ECOMM, b);      /* (aborting the communicator releases this rank's kernels that wait for the peer) */
-   }
-   return DDCMI_OK;
-}
-/* a rank that cannot go on at a point where its peers already wait for its data leaves the job: the host transport's
- * streams are closed (the peers' receives fail at once with "peer closed"), an RCCL communicator is aborted (peers inside
- * a kernel are released when the launcher tears the job down on this rank's non-zero exit) */
-static int mg_fatal(ddcmi_ctx *ctx, int code, const char *msg)
-{
-   if (msg) ctx->err = msg;
-   if (ctx->hcomm) ddcmi_rdzv_abort(ctx->hcomm);
-   else if (ctx->comm) { (void)ncclCommAbort((ncclComm_t)ctx->comm); ctx->comm = nullptr; }
-   return code;
-}
-/* host transport: device segments -> host staging -> TCP streams -> host staging -> device segments.
- * nm* messages; offsets and counts in doubles */
-static int mg_host_exchange(ddcmi_ctx *ctx, hipStream_t st, int nms, const int *speer, const double *const *sdev, const size_t *scount,
-                            int nmr, const int *rpeer, double *const *rdev, const size_t *rcount)
-{
-   size_t stot = 0, rtot = 0;
-   for (int k = 0; k < nms; k++) stot += scount[k];
-   for (int k = 0; k < nmr; k++) rtot += rcount[k];
-   ctx->hstage_s.resize(stot + 1); ctx->hstage_r.resize(rtot + 1);
-   const void *sb[27]; void *rb[27]; size_t sbytes[27], rbytes[27];
-   size_t o = 0;
-   for (int k = 0; k < nms; k++)
-   {
-      HIPCHK(ctx, hipMemcpyAsync(ctx->hstage_s.data() + o, sdev[k], scount[k] * sizeof(double), hipMemcpyDeviceToHost, st));
-      sb[k] = ctx->hstage_s.data() + o; sbytes[k] = scount[k] * sizeof(double); o += scount[k];
-   }
-   HIPCHK(ctx, hipStreamSynchronize(st));
-   o = 0;
-   for (int k = 0; k < nmr; k++) { rb[k] = ctx->hstage_r.data() + o; rbytes[k] = rcount[k] * sizeof(double); o += rcount[k]; }
-   HOSTCHK(ctx, ddcmi_rdzv_exchange(ctx->hcomm, nms, speer, sb, sbytes, nmr, rpeer, rb, rbytes));
-   o = 0;
-   for (int k = 0; k < nmr; k++)
-   {
-      HIPCHK(ctx, hipMemcpyAsync(rdev[k], ctx->hstage_r.data() + o, rcount[k] * sizeof(double), hipMemcpyHostToDevice, st));
-      o += rcount[k];
-   }
-   HIPCHK(ctx, hipStreamSynchronize(st));      /* the staging vector is reused by the next exchange */
-   return DDCMI_OK;
-}
-/* migration records: one message per direction (rebuilds only); segments are flattened
- * with the given offsets (send: by my direction code; recv: by the SENDER's direction code) */
+/* migration records (rebuilds only): one message per remote direction with a non-zero count, in ascending direction code on both
+ * sides.  The segment sent along direction `code` lies at code * sstride_items (without a stride: at soff[code]), the segment a
+ * neighbour sent along ITS direction `code` arrives at roff[code]; offsets and counts in items of `width` doubles */
 static int mg_xchg_data(ddcmi_ctx *ctx, const double *sbase, const int *soff, const int *scnt, size_t sstride_items,
                         double *rbase, const int *roff, const int *rcnt, int width)
 {
-   hipStream_t st = ctx->stream;
-   if (ctx->hcomm)
-   {
-      int speer[27], rpeer[27], nms = 0, nmr = 0;
-      const double *sdev[27]; double *rdev[27]; size_t sc[27], rc_[27];
-      for (int code = 0; code < 27; code++)
-      {
-         if (mg_remote(ctx, code) && scnt[code] > 0)
-         {
-            sdev[nms] = sstride_items ? sbase + (size_t)code * sstride_items * width : sbase + (size_t)soff[code] * width;
-            sc[nms] = (size_t)scnt[code] * width; speer[nms++] = ctx->dir_dest[code];
-         }
-         if (mg_remote(ctx, mg_opp(code)) && rcnt[code] > 0)
-         { rdev[nmr] = rbase + (size_t)roff[code] * width; rc_[nmr] = (size_t)rcnt[code] * width; rpeer[nmr++] = ctx->dir_dest[mg_opp(code)]; }
-      }
-      return mg_host_exchange(ctx, st, nms, speer, sdev, sc, nmr, rpeer, rdev, rc_);
-   }
-   ncclComm_t comm = (ncclComm_t)ctx->comm;
-   NCCLCHK2(ctx, ncclGroupStart());
+   /* (the peers already wait for this rank's records: mg_fatal) */
+   if (sstride_items > (size_t)INT32_MAX / 26) return mg_fatal(ctx, DDCMI_EUNSUPPORTED, "migration segments of more than 2^31 / 26 beads");
+   HaloMsgs ms, mr;
+   ms.n = mr.n = 0;
    for (int code = 0; code < 27; code++)
    {
       if (mg_remote(ctx, code) && scnt[code] > 0)
-      {
-         const double *src = sstride_items ? sbase + (size_t)code * sstride_items * width : sbase + (size_t)soff[code] * width;
-         NCCLCHK2(ctx, ncclSend(src, (size_t)scnt[code] * width, ncclDouble, ctx->dir_dest[code], comm, st));
-      }
+      { ms.peer[ms.n] = ctx->dir_dest[code]; ms.off[ms.n] = sstride_items ? code * (int)sstride_items : soff[code]; ms.cnt[ms.n++] = scnt[code]; }
       if (mg_remote(ctx, mg_opp(code)) && rcnt[code] > 0)
-         NCCLCHK2(ctx, ncclRecv(rbase + (size_t)roff[code] * width, (size_t)rcnt[code] * width, ncclDouble, ctx->dir_dest[mg_opp(code)], comm, st));
+      { mr.peer[mr.n] = ctx->dir_dest[mg_opp(code)]; mr.off[mr.n] = roff[code]; mr.cnt[mr.n++] = rcnt[code]; }
    }
-   NCCLCHK2(ctx, ncclGroupEnd());
-   return DDCMI_OK;
+   return mg_exchange(ctx, ms, sbase, mr, rbase, width, ctx->stream);
 }
 /* halo beads (every step): each peer pair exchanges ONE message (mg_layout_halo), which is what
  * the grouped point-to-point kernel's time follows */
 static int mg_xchg_halo(ddcmi_ctx *ctx, const double *sbase, double *rbase, int width, hipStream_t st)
 {
-   const HaloMsgs &ms = ctx->hmsg_s, &mr = ctx->hmsg_r;
-   if (ctx->hcomm)
-   {
-      const double *sdev[27]; double *rdev[27]; size_t sc[27], rc_[27];
-      for (int k = 0; k < ms.n; k++) { sdev[k] = sbase + (size_t)ms.off[k] * width; sc[k] = (size_t)ms.cnt[k] * width; }
-      for (int k = 0; k < mr.n; k++) { rdev[k] = rbase + (size_t)mr.off[k] * width; rc_[k] = (size_t)mr.cnt[k] * width; }
-      return mg_host_exchange(ctx, st, ms.n, ms.peer, sdev, sc, mr.n, mr.peer, rdev, rc_);
-   }
-   ncclComm_t comm = (ncclComm_t)ctx->comm;
-   /* DDCMI_DEBUG_SPLIT_MSGS=<k> (with DDCMI_DEBUG_HOOKS=1, loopback only): every message travels as k send/recv pairs -- what a rank with k peers hands
-    * RCCL per step (2x2x2: seven), on the one GPU there is to measure on: the same bytes, k times the operations of the group */
-   static const int split = (getenv("DDCMI_DEBUG_HOOKS") && getenv("DDCMI_DEBUG_SPLIT_MSGS")) ? std::max(1, atoi(getenv("DDCMI_DEBUG_SPLIT_MSGS"))) : 1;
-   NCCLCHK2(ctx, ncclGroupStart());
-   if (split > 1 && ctx->loopback)
-   {
-      for (int k = 0; k < ms.n; k++)
-         for (int q = 0; q < split; q++)
-         {
-            const size_t a = (size_t)ms.cnt[k] * q / split, b = (size_t)ms.cnt[k] * (q + 1) / split;
-            if (b > a) NCCLCHK2(ctx, ncclSend(sbase + ((size_t)ms.off[k] + a) * width, (b - a) * width, ncclDouble, ms.peer[k], comm, st));
-         }
-      for (int k = 0; k < mr.n; k++)
-         for (int q = 0; q < split; q++)
-         {
-            const size_t a = (size_t)mr.cnt[k] * q / split, b = (size_t)mr.cnt[k] * (q + 1) / split;
-            if (b > a) NCCLCHK2(ctx, ncclRecv(rbase + ((size_t)mr.off[k] + a) * width, (b - a) * width, ncclDouble, mr.peer[k], comm, st));
-         }
-      NCCLCHK2(ctx, ncclGroupEnd());
-      return DDCMI_OK;
-   }
-   for (int k = 0; k < ms.n; k++) NCCLCHK2(ctx, ncclSend(sbase + (size_t)ms.off[k] * width, (size_t)ms.cnt[k] * width, ncclDouble, ms.peer[k], comm, st));
-   for (int k = 0; k < mr.n; k++) NCCLCHK2(ctx, ncclRecv(rbase + (size_t)mr.off[k] * width, (size_t)mr.cnt[k] * width, ncclDouble, mr.peer[k], comm, st));
-   NCCLCHK2(ctx, ncclGroupEnd());
-   return DDCMI_OK;
+   return mg_exchange(ctx, ctx->hmsg_s, sbase, ctx->hmsg_r, rbase, width, st);
 }
 static void mg_layout_halo(ddcmi_ctx *ctx)
 {
    plan_halo_layout(ctx->dir_dest, ctx->rank, ctx->nranks, ctx->loopback, ctx->hs_cnt, ctx->hr_cnt, ctx->sseg, ctx->rseg,
                     ctx->send_off, ctx->recv_off, &ctx->nsend, &ctx->nrecv, ctx->hmsg_s, ctx->hmsg_r);
 }
-/* in-process emulation: same matching rule, direct device copies */
-static int mg_xchg_data_local(ddcmi_group *g, int which /*0 migration, 1 halo5, 2 halo3, 3 the pair correlation's records (pc_send -> pc_recv, 4 wide)*/)
+/* in-process emulation: same matching rule, direct device copies.  One domain's side of such an exchange, in items of `width` doubles: */
+struct GroupSide
+{
+   const double *src; const int *scnt; const int *soff; int sstride;      /* the segment sent along direction `code`: scnt[code] items at soff[code] -- at code * sstride where soff is null */
+   double *dst; const int *roff;                                          /* the segment a neighbour sent along ITS direction `code` lands at roff[code] */
+};
+/* a domain's side along the halo's layout (mg_layout_halo): the position and velocity halo, and the analyses that send their own records along it */
+static GroupSide group_halo_side(const ddcmi_ctx *c, const double *src, double *dst) { return GroupSide{src, c->hs_cnt, c->send_off, 0, dst, c->recv_off}; }
+template <class Side /* GroupSide (const ddcmi_ctx *) */>
+static int group_exchange(ddcmi_group *g, int width, Side side)
 {
    for (ddcmi_ctx *A : g->ranks) HIPCHK(A, hipStreamSynchronize(A->stream));
    for (ddcmi_ctx *A : g->ranks)
+   {
+      const GroupSide a = side(A);
       for (int code = 0; code < 27; code++)
       {
-         if (!mg_remote(A, code)) continue;
-         ddcmi_ctx *B = g->ranks[A->dir_dest[code]];
-         if (which == 0)
-         {
-            int n = A->mig_scnt[code];
-            if (n <= 0) continue;
-            int roff = 0;
-            for (int c = 0; c < code; c++) roff += B->mig_rcnt[c];
-            const size_t mw = (size_t)mig_width(A);
-            HIPCHK(A, hipMemcpyAsync(B->mig_in.p + (size_t)roff * mw, A->mig_out.p + (size_t)code * A->mig_cap * mw, (size_t)n * mw * sizeof(double), hipMemcpyDeviceToDevice, A->stream));
-         }
-         else
-         {
-            int n = A->hs_cnt[code];
-            if (n <= 0) continue;
-            int w = (which == 1) ? 5 : (which == 3) ? 4 : 3;
-            double *dst = (which == 1 ? B->hrecv5.p : which == 3 ? B->pc_recv.p : B->hrecv3.p) + (size_t)B->recv_off[code] * w;
-            const double *src = (which == 3 ? A->pc_send.p : A->sendbuf.p) + (size_t)A->send_off[code] * w;
-            HIPCHK(A, hipMemcpyAsync(dst, src, (size_t)n * w * sizeof(double), hipMemcpyDeviceToDevice, A->stream));
-         }
+         if (!mg_remote(A, code) || a.scnt[code] <= 0) continue;
+         const GroupSide b = side(g->ranks[A->dir_dest[code]]);
+         const size_t so = a.soff ? (size_t)a.soff[code] : (size_t)code * a.sstride;
+         HIPCHK(A, hipMemcpyAsync(b.dst + (size_t)b.roff[code] * width, a.src + so * width, (size_t)a.scnt[code] * width * sizeof(double), hipMemcpyDeviceToDevice, A->stream));
       }
+   }
    /* a device-to-device hipMemcpy on the null stream is ordered neither with the host nor with the ranks'
     * non-blocking streams: the copies go on the sender's stream and every stream is drained before the
     * receivers' kernels are queued */
    for (ddcmi_ctx *A : g->ranks) HIPCHK(A, hipStreamSynchronize(A->stream));
    return DDCMI_OK;
 }
+/* every domain's receive counts from the domains' send counts, by the rule of the transports' count round (plan_recv_counts) */
+static void group_recv_counts(ddcmi_group *g, int (ddcmi_ctx::*scnt)[27], int (ddcmi_ctx::*rcnt)[27])
+{
+   std::vector<int> all(27 * g->ranks.size());
+   for (ddcmi_ctx *A : g->ranks) memcpy(all.data() + 27 * (size_t)A->rank, A->*scnt, 27 * sizeof(int));
+   for (ddcmi_ctx *B : g->ranks) plan_recv_counts(B->dir_dest, B->rank, B->loopback, all.data(), B->*rcnt);
+}
+
 
 /* ---- rebuild phases --------------------------------------------------------- */
 /* enqueue the classification of the owned beads (stay / leave towards one of 26 directions); no host round trip */
@@ -983,8 +774,8 @@ int ddcmi_mg_rebuild(ddcmi_ctx *ctx)
    }
    int lrc = DDCMI_OK;
    {
-      int roff[27], acc = 0;
-      for (int c = 0; c < 27; c++) { roff[c] = acc; acc += ctx->mig_rcnt[c]; }
+      int roff[27];
+      const int acc = mig_recv_offsets(ctx->mig_rcnt, roff);
       /* (between a count round and its data exchange only an allocation of a few MB can fail: that rank leaves the job, mg_fatal) */
       if (ctx->mig_in.ensure((size_t)acc * mig_width(ctx) + 16)) return mg_fatal(ctx, DDCMI_ENOMEM, "device allocation for the arriving beads failed");
       if ((rc = mg_xchg_data(ctx, ctx->mig_out.p, nullptr, ctx->mig_scnt, ctx->mig_cap, ctx->mig_in.p, roff, ctx->mig_rcnt, mig_width(ctx)))) return rc;
@@ -1109,23 +900,6 @@ int ddcmi_mg_refresh_vel(ddcmi_ctx *ctx)
    }
    return mg_unpack_vel(ctx, st);
 }
-/* sum of n doubles on the device over the ranks, in place */
-static int mg_allreduce_device(ddcmi_ctx *ctx, double *d, size_t n)
-{
-   if (n == 0 || (ctx->nranks == 1 && !ctx->loopback) || !mg_transport(ctx)) return DDCMI_OK;
-   if (ctx->hcomm)
-   {
-      ctx->hstage_s.resize(n + 1);
-      HIPCHK(ctx, hipMemcpyAsync(ctx->hstage_s.data(), d, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-      HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-      HOSTCHK(ctx, ddcmi_rdzv_allreduce_f64(ctx->hcomm, ctx->hstage_s.data(), (int)n, 0));
-      HIPCHK(ctx, hipMemcpyAsync(d, ctx->hstage_s.data(), n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-      HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-      return DDCMI_OK;
-   }
-   NCCLCHK2(ctx, ncclAllReduce(d, d, n, ncclDouble, ncclSum, (ncclComm_t)ctx->comm, ctx->stream));
-   return DDCMI_OK;
-}
 
 /* ---- in-process group (tests on one GPU) ----------------------------------- */
 /* the group's all-reduce: element-wise sum of one device array per domain, written back to all of them */
@@ -1152,7 +926,7 @@ static int group_refresh_vel(ddcmi_group *g)
 {
    int rc;
    for (ddcmi_ctx *c : g->ranks) if ((rc = mg_pack_vel(c, c->stream))) return rc;
-   if ((rc = mg_xchg_data_local(g, 2))) return rc;
+   if ((rc = group_exchange(g, 3, [](const ddcmi_ctx *c) { return group_halo_side(c, c->sendbuf.p, c->hrecv3.p); }))) return rc;
    for (ddcmi_ctx *c : g->ranks) if ((rc = mg_unpack_vel(c, c->stream))) return rc;
    return DDCMI_OK;
 }
@@ -1172,24 +946,19 @@ static int group_rebuild(ddcmi_group *g)
       for (ddcmi_ctx *c : g->ranks) c->err = "a bead moved further than one domain between rebuilds";
       return DDCMI_EINVAL;
    }
+   group_recv_counts(g, &ddcmi_ctx::mig_scnt, &ddcmi_ctx::mig_rcnt);
+   std::vector<int> roff(27 * g->ranks.size());
    for (ddcmi_ctx *B : g->ranks)
    {
-      int acc = 0;
-      for (int code = 0; code < 27; code++)
-      {
-         B->mig_rcnt[code] = mg_remote(B, mg_opp(code)) ? g->ranks[B->dir_dest[mg_opp(code)]]->mig_scnt[code] : 0;
-         acc += B->mig_rcnt[code];
-      }
+      const int acc = mig_recv_offsets(B->mig_rcnt, roff.data() + 27 * (size_t)B->rank);
       if (B->mig_in.ensure((size_t)acc * mig_width(B) + 16)) SETERR(B, DDCMI_ENOMEM, "migration buffer");
    }
-   if ((rc = mg_xchg_data_local(g, 0))) return rc;
+   if ((rc = group_exchange(g, mig_width(g->ranks[0]), [&](const ddcmi_ctx *c) { return GroupSide{c->mig_out.p, c->mig_scnt, nullptr, c->mig_cap, c->mig_in.p, roff.data() + 27 * (size_t)c->rank}; }))) return rc;
    for (ddcmi_ctx *c : g->ranks) if ((rc = mg_phase2_migrate_in(c))) return rc;
    for (ddcmi_ctx *c : g->ranks) if ((rc = mg_halo_select(c))) return rc;
-   for (ddcmi_ctx *B : g->ranks)
-      for (int code = 0; code < 27; code++)
-         B->hr_cnt[code] = mg_remote(B, mg_opp(code)) ? g->ranks[B->dir_dest[mg_opp(code)]]->hs_cnt[code] : 0;
+   group_recv_counts(g, &ddcmi_ctx::hs_cnt, &ddcmi_ctx::hr_cnt);
    for (ddcmi_ctx *c : g->ranks) if ((rc = mg_phase3_pack(c, 5))) return rc;
-   if ((rc = mg_xchg_data_local(g, 1))) return rc;
+   if ((rc = group_exchange(g, 5, [](const ddcmi_ctx *c) { return group_halo_side(c, c->sendbuf.p, c->hrecv5.p); }))) return rc;
    for (ddcmi_ctx *c : g->ranks) if ((rc = mg_phase4_finish(c))) return rc;
    {
       ddcmi_ctx *c0 = g->ranks[0];
@@ -1210,7 +979,7 @@ static int group_refresh(ddcmi_group *g)
 {
    int rc;
    for (ddcmi_ctx *c : g->ranks) if ((rc = mg_pack3(c, c->stream))) return rc;
-   if ((rc = mg_xchg_data_local(g, 2))) return rc;
+   if ((rc = group_exchange(g, 3, [](const ddcmi_ctx *c) { return group_halo_side(c, c->sendbuf.p, c->hrecv3.p); }))) return rc;
    for (ddcmi_ctx *c : g->ranks) c->halo_fresh = true;
    return DDCMI_OK;
 }
@@ -1380,17 +1149,6 @@ extern "C" int ddcmi_domain_bounds(const ddcmi_ctx *ctx, double lo[3], double hi
    return DDCMI_OK;
 }
 
-/* nglfconstraint's barostat and velocity constraints given by caller-order indices are solved per domain: with several
- * domains each rank would scale its own box from its local virial and solve constraint groups without their halo
- * partners -- silently wrong physics.  Checked where the decomposition is set up AND at every step call, whatever the
- * call order.  The gid forms carry the cross-domain sums and the velocity halo. */
-static int mg_check_one_domain_features(ddcmi_ctx *ctx)
-{
-   if (ctx->nranks > 1 && ((ctx->baro_beta > 0.0 && !ctx->mol_gid) || (ctx->ncgroup > 0 && !ctx->cons_gid)))
-      SETERR(ctx, DDCMI_EUNSUPPORTED, "%d domains: the barostat and the velocity constraints (NGLFCONSTRAINT) work on a single domain unless the molecules and the "
-             "constraint groups are named by gid (ddcmi_set_molecule_lists_gid, ddcmi_set_constraints_gid)", ctx->nranks);
-   return DDCMI_OK;
-}
 /* RCCL bootstrap (the 128-byte id is distributed by the caller: MPI_Bcast in
  * ddcMD, torch.distributed in bench.py) */
 extern "C" int ddcmi_comm_unique_id(char id[128])
@@ -1431,19 +1189,6 @@ extern "C" int ddcmi_comm_init_host(ddcmi_ctx *ctx, ddcmi_rdzv *rdzv, int px, in
    mg_set_topology(ctx, rank, nranks, px, py, pz);
    return mg_check_one_domain_features(ctx);
 }
-/* sum of n doubles over the ranks, in place on the host */
-static int mg_allreduce_host_values(ddcmi_ctx *ctx, double *values, int n)
-{
-   if ((ctx->nranks == 1 && !ctx->loopback) || !mg_transport(ctx)) return DDCMI_OK;
-   if (ctx->hcomm) { HOSTCHK(ctx, ddcmi_rdzv_allreduce_f64(ctx->hcomm, values, n, 0)); return DDCMI_OK; }
-   { int rca = ddcmi_agree_poll(ctx); if (rca) return rca; }
-   double *d = ctx->d_results + R_GROUP;   /* scratch */
-   HIPCHK(ctx, hipMemcpyAsync(d, values, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-   NCCLCHK2(ctx, ncclAllReduce(d, d, n, ncclDouble, ncclSum, (ncclComm_t)ctx->comm, ctx->stream));
-   HIPCHK(ctx, hipMemcpyAsync(values, d, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-   return DDCMI_OK;
-}
 /* energyInfo.c:9-63 allreduce(): sum the ETYPE block across ranks */
 extern "C" int ddcmi_comm_allreduce_sum(ddcmi_ctx *ctx, double *values, int n)
 {
@@ -1455,237 +1200,6 @@ extern "C" int ddcmi_comm_allreduce_sum(ddcmi_ctx *ctx, double *values, int n)
       return DDCMI_OK;
    }
    return mg_allreduce_host_values(ctx, values, n);
-}
-/* ---- preflight: the first real multi-rank launch fails fast and legibly ------------------------------------
- * ddcUpdate.c:56-85 / energyInfo.c:37 meet their peers for the first time inside the first step; a fabric that does not carry one
- * of the seven links of a brick, a rank on the wrong device or a stale communicator id shows there as a hang.  This runs right
- * behind ddcmi_comm_init, before any state is uploaded: (1) ONE grouped exchange of a known pattern along every direction the brick
- * plan names -- the matching rule, peers and grouping of the per-step halo exchange and of the migration (mg_xchg_data), PF_N doubles
- * per direction, verified element by element on the receiver --, (2) one 24-double sum all-reduce (energyInfo.c allreduce()) and
- * (3) one all-gather of MG_BLK ints per rank (the rebuild's count round), each held against its closed form.  RCCL: everything is
- * queued on the context's stream with an event behind each stage and the host polls under a deadline -- when it passes, the rank
- * says which stage never finished and, for the exchange, from which peer ranks and directions nothing arrived (the receive buffer,
- * pre-filled with a sentinel, is read back on a second stream), aborts its communicator and returns DDCMI_ECOMM.  Host transport:
- * the rendezvous' own per-transfer timeouts name the peer.  The ranks then agree on the outcome (max of the error codes): a rank
- * whose data was wrong reports what it saw, every other rank reports that a peer failed -- all return non-zero from the same call. */
-#define PF_N 512
-__global__ void k_pf_fill(int n, double *send, double *recv, int rank, int corrupt_code)
-{
-   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-   if (i >= 27 * n) return;
-   const int code = i / n, k = i % n;
-   send[i] = (double)(rank * 27 + code) * 4096.0 + (double)k + (code == corrupt_code && k == 7 ? 0.5 : 0.0);
-   recv[i] = -1.0;
-}
-static void pf_dir_name(int code, char *b, size_t nb) { snprintf(b, nb, "(%+d,%+d,%+d)", code % 3 - 1, (code / 3) % 3 - 1, code / 9 - 1); }
-/* what every rank of a run must have been given alike -- box, cut-offs, tables, species, molecule tables, term counts, groups, the process grid -- as one
- * 64-bit number (FNV-1a over the values' bytes): the preflight's all-gather carries it, and ranks that read different decks say so before the first step
- * instead of exchanging halos of different widths */
-static uint64_t mg_param_hash(const ddcmi_ctx *ctx)
-{
-   uint64_t h = 1469598103934665603ull;
-   auto eat = [&](const void *p, size_t n) { const unsigned char *b = (const unsigned char *)p; for (size_t k = 0; k < n; k++) { h ^= b[k]; h *= 1099511628211ull; } };
-   auto vd = [&](const std::vector<double> &v) { const size_t n = v.size(); eat(&n, sizeof(n)); if (n) eat(v.data(), n * sizeof(double)); };
-   auto vi = [&](const std::vector<int> &v) { const size_t n = v.size(); eat(&n, sizeof(n)); if (n) eat(v.data(), n * sizeof(int)); };
-   eat(ctx->h, sizeof(ctx->h)); eat(&ctx->pbc, sizeof(int));
-   eat(&ctx->rmax, sizeof(double)); eat(&ctx->deltaR, sizeof(double)); eat(&ctx->updateRate, sizeof(int));
-   eat(&ctx->keR, sizeof(double)); eat(&ctx->krf, sizeof(double)); eat(&ctx->crf, sizeof(double));
-   eat(&ctx->nlj, sizeof(int)); vd(ctx->sigma); vd(ctx->eps); vd(ctx->shift);
-   eat(&ctx->nspecies, sizeof(int)); vd(ctx->mass); vd(ctx->charge); vi(ctx->ljtype); vi(ctx->moltype);
-   eat(&ctx->nmoltype, sizeof(int));
-   if (ctx->nmoltype > 0) { vi(ctx->mol_nspecies); vi(ctx->bpair_off); vi(ctx->bpairI); vi(ctx->bpairJ); }
-   eat(&ctx->nbond, sizeof(int)); eat(&ctx->nangle, sizeof(int)); eat(&ctx->ntors, sizeof(int)); eat(&ctx->nrest, sizeof(int)); eat(&ctx->ncgroup, sizeof(int));
-   eat(&ctx->excludePotentialTerm, sizeof(int));
-   eat(&ctx->ngroup, sizeof(int)); vi(ctx->gtype); vi(ctx->ginterval); vd(ctx->gTeq); vd(ctx->gtau);
-   eat(&ctx->baro_beta, sizeof(double)); eat(&ctx->baro_tau, sizeof(double));
-   eat(ctx->pgrid, sizeof(ctx->pgrid));
-   return h;
-}
-extern "C" int ddcmi_comm_preflight(ddcmi_ctx *ctx, double timeout_s, int64_t report[16])
-{
-   if (!ctx) return DDCMI_EINVAL;
-   if (report) memset(report, 0, 16 * sizeof(int64_t));
-   if (!mg_transport(ctx)) SETERR(ctx, DDCMI_EINVAL, "ddcmi_comm_preflight: the context has no communicator (ddcmi_comm_init first)");
-   (void)hipSetDevice(ctx->device);
-   if (timeout_s <= 0.0) timeout_s = 60.0;
-   hipStream_t st = ctx->stream;
-   const int nr = std::max(ctx->nranks, 1);
-   const bool hooks = getenv("DDCMI_DEBUG_HOOKS") != nullptr;
-   const int corrupt = (hooks && getenv("DDCMI_DEBUG_PREFLIGHT_CORRUPT")) ? atoi(getenv("DDCMI_DEBUG_PREFLIGHT_CORRUPT")) : -1;      /* tests: this rank spoils its message along that direction */
-   const int corrupt_rank = (hooks && getenv("DDCMI_DEBUG_PREFLIGHT_CORRUPT_RANK")) ? atoi(getenv("DDCMI_DEBUG_PREFLIGHT_CORRUPT_RANK")) : 0;
-   const bool absent = hooks && getenv("DDCMI_DEBUG_PREFLIGHT_ABSENT") && atoi(getenv("DDCMI_DEBUG_PREFLIGHT_ABSENT")) == ctx->rank;      /* tests (host transport): this rank never joins the exchange */
-   struct timespec t0; clock_gettime(CLOCK_MONOTONIC, &t0);
-   auto elapsed = [&]() { struct timespec t1; clock_gettime(CLOCK_MONOTONIC, &t1); return (t1.tv_sec - t0.tv_sec) + 1e-9 * (t1.tv_nsec - t0.tv_nsec); };
-   /* (freed on return: after mg_fatal on the timeout path, whose ncclCommAbort releases the kernels that still use them) */
-   dbuf<double> buf;      /* [0, 27 PF_N) send, [27 PF_N, 54 PF_N) receive, then 24 + 24 doubles of the all-reduce */
-   dbuf<int> ibuf;        /* MG_BLK ints in, MG_BLK nr ints out */
-   int rc = DDCMI_OK;
-   std::string msg;
-   int soff[27], scnt[27], roff[27], rcnt[27], npeer = 0, peers[27], ndir = 0;
-   for (int c = 0; c < 27; c++)
-   {
-      soff[c] = roff[c] = c * PF_N;
-      scnt[c] = mg_remote(ctx, c) ? PF_N : 0;
-      rcnt[c] = mg_remote(ctx, mg_opp(c)) ? PF_N : 0;
-      if (scnt[c])
-      {
-         ndir++;
-         bool seen = false;
-         for (int k = 0; k < npeer; k++) seen |= peers[k] == ctx->dir_dest[c];
-         if (!seen) peers[npeer++] = ctx->dir_dest[c];
-      }
-   }
-   if (report) { report[0] = npeer; report[1] = ndir; report[2] = (int64_t)PF_N * sizeof(double); for (int k = 0; k < npeer && k < 8; k++) report[8 + k] = peers[k]; }
-   std::vector<double> h(27 * PF_N + 48);
-   std::vector<int> hi(MG_BLK * (size_t)nr + MG_BLK);
-   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-   hipStream_t side = nullptr;
-   int stage = 0;      /* stages verified */
-   do
-   {
-      if (buf.ensure(54 * PF_N + 64) || ibuf.ensure(MG_BLK * (size_t)(nr + 1) + 64)) { rc = DDCMI_ENOMEM; msg = "preflight buffers"; break; }
-      double *snd = buf.p, *rcv = buf.p + 27 * PF_N, *ar = buf.p + 54 * PF_N;
-      hipLaunchKernelGGL(k_pf_fill, dim3(cdiv(27 * PF_N, 256)), dim3(256), 0, st, PF_N, snd, rcv, ctx->rank, ctx->rank == corrupt_rank ? corrupt : -1);
-      for (int k = 0; k < 24; k++) h[k] = (double)(ctx->rank + 1) * (double)(k + 1);
-      for (int k = 0; k < MG_BLK; k++) hi[k] = ctx->rank * 1000 + k;
-      { const uint64_t ph = mg_param_hash(ctx); hi[MG_BLK - 3] = (int)(unsigned)(ph & 0xffffffffull); hi[MG_BLK - 2] = (int)(unsigned)(ph >> 32); }      /* (words 29, 30: the parameters' hash instead of the pattern) */
-      if (hipMemcpyAsync(ar, h.data(), 24 * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess ||
-          hipMemcpyAsync(ibuf.p, hi.data(), MG_BLK * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess) { rc = DDCMI_ENODEVICE; msg = "preflight upload"; break; }
-      if (ctx->hcomm)
-      {
-         /* host transport: blocking transfers with the rendezvous' own deadlines and messages */
-         if (!absent && (rc = mg_xchg_data(ctx, snd, soff, scnt, 0, rcv, roff, rcnt, 1)) != DDCMI_OK) { msg = "preflight: the grouped exchange with the brick's peers failed: " + ctx->err; break; }
-         if (absent)
-         {
-            /* a rank that is stuck: its peers run into the rendezvous' deadline and name it; then it leaves for good */
-            struct timespec ts = {(time_t)timeout_s + 1, 0}; nanosleep(&ts, nullptr);
-            ctx->err = "preflight: this rank stayed away from the exchange (DDCMI_DEBUG_PREFLIGHT_ABSENT)";
-            return mg_fatal(ctx, DDCMI_ECOMM, nullptr);
-         }
-         if (hipMemcpyAsync(h.data(), ar, 24 * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { rc = DDCMI_ENODEVICE; msg = "preflight download"; break; }
-         if (ddcmi_rdzv_allreduce_f64(ctx->hcomm, h.data(), 24, 0) != DDCMI_OK) { rc = DDCMI_ECOMM; msg = std::string("preflight: the 24-double all-reduce failed: ") + ddcmi_rdzv_last_error(ctx->hcomm); break; }
-         memcpy(h.data() + 27 * PF_N, h.data(), 24 * sizeof(double));
-         if (ddcmi_rdzv_allgather(ctx->hcomm, hi.data(), hi.data() + MG_BLK, MG_BLK * sizeof(int)) != DDCMI_OK) { rc = DDCMI_ECOMM; msg = std::string("preflight: the count all-gather failed: ") + ddcmi_rdzv_last_error(ctx->hcomm); break; }
-         if (hipMemcpyAsync(h.data(), rcv, 27 * PF_N * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { rc = DDCMI_ENODEVICE; msg = "preflight download"; break; }
-      }
-      else
-      {
-         ncclComm_t comm = (ncclComm_t)ctx->comm;
-         bool evok = true;
-         for (int k = 0; k < 3; k++) evok &= hipEventCreateWithFlags(&ev[k], hipEventDisableTiming) == hipSuccess;
-         if (!evok || hipStreamCreateWithFlags(&side, hipStreamNonBlocking) != hipSuccess) { rc = DDCMI_ENODEVICE; msg = "preflight events"; break; }
-         if ((rc = mg_xchg_data(ctx, snd, soff, scnt, 0, rcv, roff, rcnt, 1)) != DDCMI_OK) { msg = "preflight: queueing the grouped exchange failed: " + ctx->err; break; }
-         (void)hipEventRecord(ev[0], st);
-         if (ncclAllReduce(ar, ar + 24, 24, ncclDouble, ncclSum, comm, st) != ncclSuccess) { rc = DDCMI_ECOMM; msg = "preflight: ncclAllReduce could not be queued"; break; }
-         (void)hipEventRecord(ev[1], st);
-         if (ncclAllGather(ibuf.p, ibuf.p + MG_BLK, MG_BLK, ncclInt, comm, st) != ncclSuccess) { rc = DDCMI_ECOMM; msg = "preflight: ncclAllGather could not be queued"; break; }
-         (void)hipEventRecord(ev[2], st);
-         bool done = false;
-         while (!done)
-         {
-            const hipError_t q = hipEventQuery(ev[2]);
-            if (q == hipSuccess) { done = true; break; }
-            if (q != hipErrorNotReady) { rc = DDCMI_ENODEVICE; msg = std::string("preflight: the stream failed: ") + hipGetErrorString(q); break; }
-            if (elapsed() > timeout_s) break;
-            struct timespec ts = {0, 200000}; nanosleep(&ts, nullptr);
-         }
-         if (rc) break;
-         if (!done)
-         {
-            /* which stage never finished; for the exchange, whose data never came (the receive buffer through a second stream: the first one is stuck) */
-            const int reached = hipEventQuery(ev[0]) != hipSuccess ? 0 : hipEventQuery(ev[1]) != hipSuccess ? 1 : 2;
-            char b[1024];
-            int o = snprintf(b, sizeof(b), "preflight: rank %d of %d: no completion within %.0f s, stuck in %s", ctx->rank, nr, timeout_s,
-                             reached == 0 ? "the grouped send/recv with the brick's peers" : reached == 1 ? "the 24-double all-reduce" : "the count all-gather");
-            if (reached == 0 && hipMemcpyAsync(h.data(), rcv, 27 * PF_N * sizeof(double), hipMemcpyDeviceToHost, side) == hipSuccess && hipStreamSynchronize(side) == hipSuccess)
-            {
-               o += snprintf(b + o, sizeof(b) - o, "; nothing arrived from");
-               for (int c = 0; c < 27 && o < (int)sizeof(b) - 64; c++)
-                  if (rcnt[c] && h[(size_t)c * PF_N + PF_N - 1] == -1.0)
-                  {
-                     char d[32]; pf_dir_name(mg_opp(c), d, sizeof(d));
-                     o += snprintf(b + o, sizeof(b) - o, " rank %d (my direction %s)", ctx->dir_dest[mg_opp(c)], d);
-                     if (report && report[3] == 0) { report[3] = 1; report[4] = ctx->dir_dest[mg_opp(c)]; report[5] = mg_opp(c); }
-                  }
-            }
-            msg = b;
-            rc = mg_fatal(ctx, DDCMI_ECOMM, nullptr);      /* (releases the kernels that wait for the peer) */
-            if (report) { report[6] = reached; report[7] = (int64_t)(elapsed() * 1e6); }
-            /* no agreement round: the fabric has just shown that it does not answer */
-            for (int k = 0; k < 3; k++) if (ev[k]) (void)hipEventDestroy(ev[k]);
-            if (side) (void)hipStreamDestroy(side);
-            ctx->err = msg;
-            return rc;
-         }
-         if (hipMemcpyAsync(h.data(), rcv, 27 * PF_N * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
-             hipMemcpyAsync(h.data() + 27 * PF_N, ar + 24, 24 * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
-             hipMemcpyAsync(hi.data() + MG_BLK, ibuf.p + MG_BLK, MG_BLK * (size_t)nr * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
-             hipStreamSynchronize(st) != hipSuccess) { rc = DDCMI_ENODEVICE; msg = "preflight download"; break; }
-      }
-      /* (1) every direction's message, element by element */
-      for (int c = 0; c < 27 && !rc; c++)
-      {
-         if (!rcnt[c]) continue;
-         const int src = ctx->dir_dest[mg_opp(c)];
-         for (int k = 0; k < PF_N; k++)
-         {
-            const double want = (double)(src * 27 + c) * 4096.0 + (double)k, got = h[(size_t)c * PF_N + k];
-            if (got != want)
-            {
-               char d[32], b[512]; pf_dir_name(mg_opp(c), d, sizeof(d));
-               snprintf(b, sizeof(b), "preflight: rank %d of %d: the message from rank %d (my direction %s, its direction code %d) is wrong at element %d of %d: got %.17g, expected %.17g",
-                        ctx->rank, nr, src, d, c, k, PF_N, got, want);
-               msg = b; rc = DDCMI_ECOMM;
-               if (report) { report[3] = 1; report[4] = src; report[5] = mg_opp(c); }
-               break;
-            }
-         }
-      }
-      if (rc) break;
-      stage = 1;
-      /* (2) sum over ranks of (r + 1)(k + 1) */
-      for (int k = 0; k < 24; k++)
-      {
-         const double want = 0.5 * (double)nr * (double)(nr + 1) * (double)(k + 1), got = h[27 * PF_N + k];
-         if (got != want)
-         {
-            char b[256]; snprintf(b, sizeof(b), "preflight: rank %d of %d: the 24-double all-reduce gave %.17g at element %d, expected %.17g", ctx->rank, nr, got, k, want);
-            msg = b; rc = DDCMI_ECOMM; break;
-         }
-      }
-      if (rc) break;
-      stage = 2;
-      /* (3) every rank's block of the all-gather */
-      for (int r = 0; r < nr && !rc; r++)
-         for (int k = 0; k < MG_BLK; k++)
-            if (k != MG_BLK - 3 && k != MG_BLK - 2 && hi[MG_BLK + (size_t)MG_BLK * r + k] != r * 1000 + k)
-            {
-               char b[256]; snprintf(b, sizeof(b), "preflight: rank %d of %d: the all-gather holds %d at word %d of rank %d's block, expected %d", ctx->rank, nr, hi[MG_BLK + (size_t)MG_BLK * r + k], k, r, r * 1000 + k);
-               msg = b; rc = DDCMI_ECOMM; break;
-            }
-      if (rc) break;
-      stage = 3;
-      /* ... and what the block carried: do the ranks run the same system? */
-      for (int r = 0; r < nr && !rc; r++)
-         if (hi[MG_BLK + (size_t)MG_BLK * r + MG_BLK - 3] != hi[MG_BLK - 3] || hi[MG_BLK + (size_t)MG_BLK * r + MG_BLK - 2] != hi[MG_BLK - 2])
-         {
-            char b[384];
-            snprintf(b, sizeof(b), "preflight: rank %d of %d: rank %d was given other parameters than this rank (box, cut-offs, neighbour settings, LJ table, species, molecule tables, "
-                     "term counts, groups, barostat or process grid differ): every rank of a run must be set up from the same deck", ctx->rank, nr, r);
-            msg = b; rc = DDCMI_EINVAL;
-            if (report) { report[3] = 1; report[4] = r; report[5] = -1; }
-         }
-   } while (0);
-   for (int k = 0; k < 3; k++) if (ev[k]) (void)hipEventDestroy(ev[k]);
-   if (side) (void)hipStreamDestroy(side);
-   if (report) { report[6] = stage; report[7] = (int64_t)(elapsed() * 1e6); }
-   if (rc) ctx->err = msg;
-   /* every rank leaves with the same verdict (a transport error above has usually ended the agreement's transport too: then its own error stands) */
-   if (rc == DDCMI_ECOMM && ctx->hcomm && msg.find("failed:") != std::string::npos) return rc;
-   const int arc = mg_agree(ctx, rc);
-   if (rc) { ctx->err = msg; return rc; }
-   if (arc) { ctx->err = "preflight: another rank's check of the communicator failed (its own message says which peer and direction): " + ctx->err; return arc; }
-   return DDCMI_OK;
 }
 void ddcmi_comm_destroy(ddcmi_ctx *ctx)
 {

@@ -78,7 +78,7 @@ int ddcmi_bl_sort_owned(ddcmi_ctx *ctx)
    if (n > 0)
    {
       hipLaunchKernelGGL(k_scatter_order, dim3(nb), dim3(256), 0, st, n, ctx->cid.p, ctx->crank.p, ctx->cell_start_o.p, ctx->order.p);
-      if (ctx->nranks > 1 || ctx->loopback || ctx->group_)      /* migrants arrive in message order: sort by gid, so that a run repeats bit for bit */
+      if (decomposed(ctx))      /* migrants arrive in message order: sort by gid, so that a run repeats bit for bit */
          hipLaunchKernelGGL(k_sort_cells_key, dim3(ncb), dim3(256), 0, st, ncell, ctx->cell_start_o.p, ctx->cell_cnt_o.p, ctx->order.p, ctx->gid.p, (const int *)nullptr);
       else
          hipLaunchKernelGGL(k_sort_cells, dim3(ncb), dim3(256), 0, st, ncell, ctx->cell_start_o.p, ctx->cell_cnt_o.p, ctx->order.p);
@@ -90,7 +90,7 @@ int ddcmi_bl_sort_owned(ddcmi_ctx *ctx)
                          ctx->species.p, ctx->group.p, ctx->gid.p, ctx->orig.p,
                          ctx->pos2.p, ctx->vx2.p, ctx->vy2.p, ctx->vz2.p, ctx->species2.p, ctx->group2.p, ctx->gid2.p, ctx->orig2.p,
                          slots ? ctx->slot_of_orig.p : (int *)nullptr,
-                         gp, (ctx->nranks == 1 && !ctx->loopback && !ctx->group_) ? ctx->nimg.p : (int *)nullptr, 1,
+                         gp, !decomposed(ctx) ? ctx->nimg.p : (int *)nullptr, 1,
                          ctx->lcg_on ? ctx->lcg.p : (const ulonglong2 *)nullptr, ctx->lcg2.p, ctx->vaf_on ? ctx->vaf.p : (const VafRec *)nullptr, ctx->vaf2.p);
       if (ctx->lcg_on) std::swap(ctx->lcg, ctx->lcg2);
       if (ctx->vaf_on) std::swap(ctx->vaf, ctx->vaf2);
@@ -200,7 +200,7 @@ static int bl_validate_tables(ddcmi_ctx *ctx)
       for (int sp = 0; sp < ctx->nspecies; sp++)
          if (ctx->moltype[sp] < 0 || ctx->moltype[sp] >= ctx->nmoltype)
             SETERR(ctx, DDCMI_EINVAL, "species %d: molecule type %d outside the %d types of ddcmi_set_molecules", sp, ctx->moltype[sp], ctx->nmoltype);
-   const bool one = ctx->nranks == 1 && !ctx->loopback && !ctx->group_;      /* (several domains: index-named tables are refused where they are set) */
+   const bool one = !decomposed(ctx);      /* (several domains: index-named tables are refused where they are set) */
    if (one && !ctx->bonded_gid && ctx->inc_nrow > ctx->nloc)
       SETERR(ctx, DDCMI_EINVAL, "a bonded term of ddcmi_set_bonded names bead %d, the uploaded state holds %d", ctx->inc_nrow - 1, ctx->nloc);
    if (one && !ctx->cons_gid && ctx->ncgroup > 0 && ctx->idx_amax_cons >= ctx->nloc)
@@ -267,7 +267,7 @@ static int schedule_tiles(ddcmi_ctx *ctx, int wg_per_cu)
    int *perm = ctx->pinned(1, cap_items + 64), *sched = perm ? perm + cap_items : nullptr;
    if (!work || !perm) SETERR(ctx, DDCMI_ENOMEM, "pinned staging for the tile schedule");
    for (int k = 0; k < 32; k++) sched[k] = 0;
-   const bool two = ctx->halo_overlap && (ctx->nranks > 1 || ctx->loopback || ctx->group_);
+   const bool two = ctx->halo_overlap && decomposed(ctx);
    /* tiles without owned beads (the margin tiles, empty space) get no workgroup at all: a workgroup that finds
     * nothing to do still has to be dispatched with its 72 KB of LDS and eight waves, and at 4 M beads 45 % of the
     * grid were such workgroups -- the per-CU timeline showed one of the two slots of a CU empty a quarter of the

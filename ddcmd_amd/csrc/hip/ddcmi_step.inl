@@ -71,9 +71,9 @@ static int launch_forces(ddcmi_ctx *ctx, bool defer_reduce = false, FuseArgs *fu
     * update launch -- for halos of received beads only, needed by the pair kernel only */
    /* (round 6: bonded terms are no obstacle any more -- their kernels take a received partner out of the receive buffer too, k_bonded_gather's bead();
     *  restraints, constraint groups and the barostat still want every halo bead in pos[]) */
-   const bool direct = !ctx->no_direct_halo && (ctx->nranks > 1 || ctx->loopback) && (ctx->comm || ctx->hcomm) && !ctx->group_ && !ctx->halo_overlap && ctx->nself_images == 0 &&
+   const bool direct = !ctx->no_direct_halo && exchanging(ctx) && !ctx->group_ && !ctx->halo_overlap && ctx->nself_images == 0 &&
                        ctx->nrest == 0 && ctx->ncgroup == 0 && !(ctx->baro_beta > 0.0) && ctx->stage_cap + 2 < 4096 && (ctx->excludePotentialTerm & 128) == 0 && ctx->updateRate > 0;
-   const bool hdisp_on = !direct && ctx->shell_skip && nh > 0 && (ctx->nranks > 1 || ctx->loopback || ctx->group_);
+   const bool hdisp_on = !direct && ctx->shell_skip && nh > 0 && decomposed(ctx);
    const int hpar = (int)(ctx->loop & 1);
    unsigned long long *hmax = hdisp_on ? (unsigned long long *)(ctx->d_results + R_DISP + 1) : nullptr;
    if (direct && !ctx->halo_fresh)
@@ -451,12 +451,9 @@ static GroupLambda front_lambda(const ddcmi_ctx *ctx, double dt)
  *   b  barostat: pressures, scale factors, box; FRONT half kick (+ drift unless constraints follow)
  *                                                                            -> velocity halo (constraints only)
  *   c  constraints: FRONT solve, drift; clock */
-static int mg_allreduce_host_values(ddcmi_ctx *ctx, double *values, int n);
 struct PackJob;
 static bool ddcmi_mg_pack_job(ddcmi_ctx *ctx, PackJob *pk);
-static int mg_allreduce_device(ddcmi_ctx *ctx, double *d, size_t n);
 int ddcmi_mg_refresh_vel(ddcmi_ctx *ctx);
-static inline bool decomposed(const ddcmi_ctx *ctx) { return ctx->nranks > 1 || ctx->loopback || ctx->group_ != nullptr; }
 static int step_pre_a(ddcmi_ctx *ctx)
 {
    if (ctx->drift_done || !(ctx->baro_beta > 0.0)) return DDCMI_OK;
@@ -703,7 +700,7 @@ int ddcmi_displacement_check(ddcmi_ctx *ctx, int *need)
    hipStream_t st = ctx->stream;
    const int n = ctx->nloc, nblk = cdiv(std::max(n, 1), DDCMI_BLOCK);
    *need = 1;
-   if (ctx->comm) { int rca = ddcmi_agree_poll(ctx); if (rca) return rca; }      /* (this path waits on the host every step: a peer whose rebuild failed is reported here, not after the mailbox's timeout) */
+   { int rca = ddcmi_agree_poll(ctx); if (rca) return rca; }      /* (this path waits on the host every step: a peer whose rebuild failed is reported here, not after the mailbox's timeout) */
    if (!ctx->list_valid || ctx->pos0.cap < (size_t)n) return DDCMI_OK;
    *need = 0;
    if (n == 0)
@@ -744,7 +741,17 @@ int ddcmi_displacement_check(ddcmi_ctx *ctx, int *need)
    *need = (2.0 * sqrt(d2max) < ctx->deltaR) ? 0 : 1;
    return DDCMI_OK;
 }
-static int mg_check_one_domain_features(ddcmi_ctx *ctx);
+/* nglfconstraint's barostat and velocity constraints given by caller-order indices are solved per domain: with several
+ * domains each rank would scale its own box from its local virial and solve constraint groups without their halo
+ * partners -- silently wrong physics.  Checked where the decomposition is set up AND at every step call, whatever the
+ * call order.  The gid forms carry the cross-domain sums and the velocity halo. */
+static int mg_check_one_domain_features(ddcmi_ctx *ctx)
+{
+   if (ctx->nranks > 1 && ((ctx->baro_beta > 0.0 && !ctx->mol_gid) || (ctx->ncgroup > 0 && !ctx->cons_gid)))
+      SETERR(ctx, DDCMI_EUNSUPPORTED, "%d domains: the barostat and the velocity constraints (NGLFCONSTRAINT) work on a single domain unless the molecules and the "
+             "constraint groups are named by gid (ddcmi_set_molecule_lists_gid, ddcmi_set_constraints_gid)", ctx->nranks);
+   return DDCMI_OK;
+}
 /* FROZEN / FIXEDVELOCITY / QUENCH groups beside constraint groups or a barostat: the constraint solver would move frozen beads and
  * overwrite set velocities; the pairing is refused at the step, before anything moves */
 static int kinds_pairing_check(ddcmi_ctx *ctx)
@@ -762,7 +769,7 @@ static int rebuild_due(ddcmi_ctx *ctx, bool *due)
    if (ctx->updateRate > 0) { *due = (ctx->loop % ctx->updateRate == 0); return DDCMI_OK; }
    int need = 0, rc = ddcmi_displacement_check(ctx, &need);
    if (rc) return rc;
-   if ((ctx->nranks > 1 || ctx->loopback) && (ctx->comm || ctx->hcomm))
+   if (exchanging(ctx))
    {
       /* check4updateNeighbor (ddcUpdateAll.c:56): anyone needs a rebuild -> everyone rebuilds */
       double v = (double)need;

@@ -164,20 +164,11 @@ static int therm_reduce(const std::vector<ddcmi_ctx *> &ranks, const std::vector
    const std::vector<double> *rows = loc.data();
    size_t nrows = loc.size();
    std::vector<std::vector<double>> got;
-   if (ranks.size() == 1 && ctx->nranks > 1 && mg_transport(ctx))
+   if (ranks.size() == 1 && ctx->nranks > 1 && mg_transport(ctx))      /* (not exchanging(): a loopback rank owns every bead, its sums are the run's) */
    {
       std::vector<double> all((size_t)ctx->nranks * nv);
-      if (ctx->hcomm) HOSTCHK(ctx, ddcmi_rdzv_allgather(ctx->hcomm, loc[0].data(), all.data(), nv * sizeof(double)));
-      else
-      {
-         { int rca = ddcmi_agree_poll(ctx); if (rca) return rca; }
-         ENSURE(ctx, ctx->therm_tab, ((size_t)ctx->nranks + 1) * nv);
-         double *d = ctx->therm_tab.p;
-         HIPCHK(ctx, hipMemcpyAsync(d, loc[0].data(), nv * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-         NCCLCHK2(ctx, ncclAllGather(d, d + nv, nv, ncclDouble, (ncclComm_t)ctx->comm, ctx->stream));
-         HIPCHK(ctx, hipMemcpyAsync(all.data(), d + nv, (size_t)ctx->nranks * nv * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-      }
+      const int rcg = mg_allgather_host_values(ctx, loc[0].data(), all.data(), nv, ctx->therm_tab);
+      if (rcg) return rcg;
       for (int r = 0; r < ctx->nranks; r++) got.emplace_back(all.begin() + (size_t)r * nv, all.begin() + (size_t)(r + 1) * nv);
       rows = got.data(); nrows = got.size();
    }
