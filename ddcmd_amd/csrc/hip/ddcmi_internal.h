@@ -161,6 +161,30 @@ struct TileSel { int mode; int lo[3], n[3]; };
 #define LEAN_HW 32             /* doubles of a lean step's row of sums: 8 pair sums, 7 kinetic sums, 0, the 10 bonded sums, 0 ... */
 #define LEAN_VSTRIDE 32      /* words: 128 B */
 struct NbLds { size_t total; int tab_off, ke_off; bool lvl, zfix; int wgs; };
+/* What one force evaluation does, decided once (plan_forces, ddcmi_step.inl) and executed by launch_forces.
+ * How the halo records reach this evaluation's pair kernel: */
+enum HaloMode
+{
+   HALO_NONE = 0,        /* nothing to refresh: no halo, or the rebuild or the last exchange in front of this evaluation placed every image and halo bead */
+   HALO_AT_OWNERS = 1,   /* a single domain's periodic images: the pair kernel stages them from their owners (NbTileArgs::self_img), nothing refreshes the records */
+   HALO_UPDATE = 2,      /* the exchange, then the update launch, on the main stream */
+   HALO_DIRECT = 3,      /* the exchange alone: the pair kernel stages the received beads from the receive buffer (ddcmi_ctx::halo_in_recv) */
+   HALO_OVERLAP = 4,     /* exchange and update launch on the second stream, under the tiles whose neighbourhoods hold owned beads only */
+   HALO_IMAGES = 5       /* the update launch alone: a single domain's images, or a domain of an in-process group, whose driver has exchanged */
+};
+/* the reduction launch behind a fused pair launch that is not lean: alone, with the periodic images at the drifted positions on
+ * the side, or with the next exchange's messages packed on the side.  RED_NONE: not fused (the kick's launch reduces), or lean */
+enum RedAfter { RED_NONE = 0, RED_PLAIN = 1, RED_IMAGES = 2, RED_PACK = 3 };
+struct StepPlan
+{
+   HaloMode halo;
+   bool direct;      /* received beads are read from the receive buffer, refreshed by this evaluation or not */
+   bool hdisp;       /* the update launch measures the received beads' displacement since the rebuild (NbTileArgs::hdisp) */
+   bool fused;       /* the integrator's pass rides in the pair kernel */
+   bool lean;        /* ... and nothing follows it: the step's sums wait in the ring (ddcmi_ctx::lean_pending) */
+   RedAfter red;
+   NbLds lds;        /* all zero where the pair kernel does not run (bit 128 of excludePotentialTerm) */
+};
 
 /* results block on the device / pinned host mirror */
 enum
@@ -265,6 +289,8 @@ struct ddcmi_ctx
    dbuf<double> lean_part, lean_kpart, lean_hist, lean_tmp, lean_bpart; size_t lean_bstride = 0; int lean_bpstride = 0, lean_bnblk = 0;
    dbuf<unsigned> d_vring;             /* largest |v|^2 (float bits) of each lean step since the rebuild, one word per step at a stride of LEAN_VSTRIDE words: the step that
                                           is being written (atomic maxima of every workgroup) shares no cache line with the words the same launch reads */
+   StepPlan plan = {};                 /* of the last force evaluation (launch_forces; step_post reads from it what follows the launch) */
+   StepPlan plan_ring[16] = {}; int64_t nplan = 0;      /* the last 16 plans, for ddcmi_debug_step_plan: all but the last step of a ddcmi_step_nglf call lie behind the last plan */
    bool images_fresh = false;          /* the list was rebuilt in front of this force evaluation: the periodic images of a single domain need no update */
    int64_t fuse_tags_of = -1;              /* the rebuild whose halo tag words the second position buffer holds (fused steps swap the buffers) */
    uint64_t rng_seed = 0;              /* Langevin groups: seed of the counter-based normal stream (RANDOM seed) */

@@ -836,9 +836,10 @@ static int mg_pack3(ddcmi_ctx *ctx, hipStream_t st)
    return DDCMI_OK;
 }
 /* the pack of the next halo refresh as a job of the fused step's reduction launch (k_reduce_jobs_images) */
-static bool ddcmi_mg_pack_job(ddcmi_ctx *ctx, PackJob *pk)
+static bool mg_pack_ready(const ddcmi_ctx *ctx) { return !ctx->group_ && ctx->list_valid && ctx->nsend > 0 && ctx->send_map.p && ctx->sendbuf.p; }
+static bool ddcmi_mg_pack_job(const ddcmi_ctx *ctx, PackJob *pk)
 {
-   if (ctx->group_ || !ctx->list_valid || ctx->nsend <= 0 || !ctx->send_map.p || !ctx->sendbuf.p) return false;
+   if (!mg_pack_ready(ctx)) return false;
    const DirTab dt = mg_dirtab(ctx);
    pk->nsend = ctx->nsend; pk->send_map = ctx->send_map.p;
    for (int c = 0; c < 27; c++) for (int a = 0; a < 3; a++) pk->shift[c][a] = dt.shift[c][a];

@@ -89,7 +89,7 @@ __global__ __launch_bounds__(NB_BLOCK, WPE) void k_nonbond(GridParams gp, NbTile
    typedef __attribute__((address_space(3))) const double lds_cdouble;
    typedef double xy_t __attribute__((ext_vector_type(2)));
    typedef __attribute__((address_space(3))) const xy_t lds_cxy;
-   const unsigned xy_off = ZOFF ? 0u : (unsigned)(__UINTPTR_TYPE__)(__attribute__((address_space(3))) void *)XY_s;      /* (the dynamic region starts at LDS address 0: launch_forces asks the runtime, lds_starts_at_zero) */
+   const unsigned xy_off = ZOFF ? 0u : (unsigned)(__UINTPTR_TYPE__)(__attribute__((address_space(3))) void *)XY_s;      /* (the dynamic region starts at LDS address 0: launch_nonbond asks the runtime, lds_starts_at_zero) */
    /* XCD-aware mapping: hardware deals workgroups round-robin over the 8 XCDs, so
     * give XCD x one contiguous tile range (schedule_tiles: equal work per XCD):
     * neighbouring tiles, which stage overlapping neighbourhoods, then share one L2.

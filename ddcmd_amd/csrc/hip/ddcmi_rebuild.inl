@@ -69,7 +69,7 @@ int ddcmi_bl_sort_owned(ddcmi_ctx *ctx)
       /* (decomposed runs: the "beads are not numbers" flag also rides in slot 30 of the direction counters, so that the halo count
        * round of this rebuild tells every rank) */
       hipLaunchKernelGGL(k_wrap_cell, dim3(nb), dim3(256), 0, st, gp, n, ctx->pos.p, ctx->cid.p, ctx->crank.p, ctx->cell_cnt_o.p, ctx->d_flags + 12,
-                         ((ctx->nranks > 1 || ctx->loopback) && ctx->dir_cnt.cap >= 32) ? ctx->dir_cnt.p + 30 : (int *)nullptr,
+                         (has_peers(ctx) && ctx->dir_cnt.cap >= 32) ? ctx->dir_cnt.p + 30 : (int *)nullptr,
                          ctx->sort_renumbers ? ctx->orig.p : (int *)nullptr, ctx->sort_renumbers ? ctx->dir_cnt.p : (int *)nullptr);
       ctx->dir28_clean = ctx->sort_renumbers;
    }
@@ -227,7 +227,7 @@ extern "C" int ddcmi_build_list(ddcmi_ctx *ctx)
    if ((rc = nb_tables(ctx))) return rc;
    /* (a rebuild places every image and halo bead from the positions it sorts: the force evaluation that follows needs no update of
     * them -- and a decomposed rank has no 3-wide records to take one from until its first per-step exchange) */
-   if (ctx->nranks > 1 || ctx->loopback) { rc = ddcmi_mg_rebuild(ctx); if (!rc) ctx->images_fresh = true; return rc; }
+   if (has_peers(ctx)) { rc = ddcmi_mg_rebuild(ctx); if (!rc) ctx->images_fresh = true; return rc; }
    ctx->phase(-1, nullptr);
    for (int pass = 0;; pass++)
    {

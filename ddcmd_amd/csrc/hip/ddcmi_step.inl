@@ -40,59 +40,105 @@ static NbLds nb_lds_layout(const ddcmi_ctx *ctx, bool fused)
    const NbLds v = lay(level, true);
    return (ctx->force_lvl || v.wgs > d.wgs) ? v : d;
 }
-/* may this context run lean steps (ddcmi_ctx::lean_pending)?  A single domain whose step is the fused pair kernel (+ the bonded kernels in front of it) */
-static bool lean_capable(const ddcmi_ctx *ctx)
+/* ---- which path a force evaluation takes: the shared conditions, then ONE plan (plan_forces) ---- */
+static bool mg_pack_ready(const ddcmi_ctx *ctx);
+static bool ddcmi_mg_pack_job(const ddcmi_ctx *ctx, PackJob *pk);
+/* every group is FREE or BERENDSEN: the integrator's pass is one kick + drift (Berendsen: host scalars from the temperature last published) */
+static bool groups_plain(const ddcmi_ctx *ctx)
 {
-   if (ctx->no_lean || ctx->group_ || ctx->updateRate <= 0 || ctx->nloc <= 0) return false;      /* (a decomposed rank: where its halo is staged from the receive buffer, launch_forces) */
-   if (ctx->nrest != 0 || ctx->ncgroup > 0 || ctx->baro_beta > 0.0 || (ctx->excludePotentialTerm & 128) != 0) return false;
-   for (int g = 0; g < ctx->ngroup; g++) if (ctx->gtype[g] != DDCMI_FREE && ctx->gtype[g] != DDCMI_BERENDSEN) return false;      /* (Berendsen: host scalars from the temperature last published) */
+   for (int g = 0; g < ctx->ngroup; g++) if (ctx->gtype[g] != DDCMI_FREE && ctx->gtype[g] != DDCMI_BERENDSEN) return false;
    return true;
 }
+/* the step is the pair kernel only (+ the bonded kernels in front of it, which take a received partner out of the receive buffer too:
+ * k_bonded_gather's bead()): restraints, constraint groups and the barostat want every halo bead in pos[]; bit 128 of
+ * excludePotentialTerm takes the pair kernel away; updateRate == 0 puts a host round trip between the steps */
+static bool pair_kernel_only(const ddcmi_ctx *ctx) { return ctx->nrest == 0 && ctx->ncgroup == 0 && !(ctx->baro_beta > 0.0) && (ctx->excludePotentialTerm & 128) == 0 && ctx->updateRate > 0; }
+/* Three questions rest on these two and differ on purpose:
+ *   fuse_ok       groups_plain, no constraint groups, no barostat, the pair kernel on -- but restraints and updateRate == 0 are welcome;
+ *   lean_capable  groups_plain AND pair_kernel_only (so: no restraints), owned beads, not a domain of an in-process group;
+ *   direct_halo   pair_kernel_only, whatever the groups (a LANGEVIN rank stages directly in front of the split kernels) -- and a transport,
+ *                 and a halo of received beads only (nself_images == 0). */
+/* may the integrator's pass ride in the pair kernel (k_nonbond<..., FUSE>)?  The force must be complete when the list walk ends and the
+ * step must need nothing between the force and the drift (bonded terms, restraints and charges are no obstacle: their kernels run in
+ * front of the pair kernel, the excluded-pair loop ends before the epilogue).  DDCMI_NO_FUSED_STEP=1: never */
+static bool fuse_ok(const ddcmi_ctx *ctx)
+{
+   static const bool off = getenv("DDCMI_NO_FUSED_STEP") != nullptr;
+   return !off && ctx->nloc > 0 && !ctx->group_ && (ctx->excludePotentialTerm & 128) == 0 && ctx->ncgroup == 0 && !(ctx->baro_beta > 0.0) && groups_plain(ctx);
+}
+/* may this context run lean steps (ddcmi_ctx::lean_pending)?  Its step is the fused pair kernel and nothing else.  DDCMI_NO_LEAN_STEP=1: never */
+static bool lean_capable(const ddcmi_ctx *ctx) { return !ctx->no_lean && !ctx->group_ && ctx->nloc > 0 && pair_kernel_only(ctx) && groups_plain(ctx); }
 /* a single domain's periodic images are staged by the pair kernel from their owners (NbTileArgs::self_img): nothing reads the image records
  * between two rebuilds, and nothing refreshes them -- where the step can be lean; elsewhere the reduction launch of every step refreshes
  * them on the side and the staging keeps its shorter path (the bilayer: 4 us per pair kernel).  DDCMI_NO_SELF_IMAGES=1: never. */
-static bool self_images(const ddcmi_ctx *ctx)
+static bool self_images(const ddcmi_ctx *ctx) { return !ctx->no_self_img && !has_peers(ctx) && lean_capable(ctx) && ctx->nhalo > 0 && ctx->stage_cap + 2 < 4096; }
+/* direct halo staging (ddcmi_ctx::halo_in_recv): the pair kernel takes the received beads out of the exchange's receive buffer, no update
+ * launch -- for halos of received beads only, needed by the pair kernel only.  DDCMI_NO_DIRECT_HALO=1: never */
+static bool direct_halo(const ddcmi_ctx *ctx) { return !ctx->no_direct_halo && exchanging(ctx) && !ctx->group_ && !ctx->halo_overlap && ctx->nself_images == 0 && pair_kernel_only(ctx) && ctx->stage_cap + 2 < 4096; }
+/* The plan of one force evaluation, from the context as it stands and the caller's wishes: may_fuse, the integrator's pass may ride
+ * in the pair kernel (with time step dt); may_lean, the step could be lean.  No side effects: launch_forces executes it. */
+static StepPlan plan_forces(const ddcmi_ctx *ctx, bool may_fuse, bool may_lean, double dt)
 {
-   return !ctx->no_self_img && ctx->nranks == 1 && !ctx->loopback && lean_capable(ctx) && ctx->nhalo > 0 && ctx->stage_cap + 2 < 4096;
+   StepPlan p = {};
+   const bool peers = has_peers(ctx), at_owners = self_images(ctx);
+   p.direct = direct_halo(ctx);
+   /* the received beads' displacement since the rebuild: measured by the update launch of a decomposed run whose pair kernel may end its rows early */
+   p.hdisp = !p.direct && ctx->shell_skip && ctx->nhalo > 0 && decomposed(ctx);
+   /* (no refresh after a rebuild: it made the images from these very positions; and never on a rank of a transport whose halo is marked fresh --
+    * its last exchange or its rebuild placed every image and halo bead, and the receive buffer may hold velocities or nothing by now) */
+   if (peers && !ctx->halo_fresh) p.halo = p.direct ? HALO_DIRECT : ctx->halo_overlap ? HALO_OVERLAP : HALO_UPDATE;
+   else if (at_owners) p.halo = HALO_AT_OWNERS;
+   else if (ctx->nhalo > 0 && !ctx->images_fresh && !(peers && !ctx->group_)) p.halo = HALO_IMAGES;
+   if ((ctx->excludePotentialTerm & 128) != 0) return p;
+   p.lds = nb_lds_layout(ctx, may_fuse);
+   p.fused = may_fuse;
+   if (may_fuse)
+   {
+      /* the integrator's pass rides in the pair kernel only with the fixed layout, and never at the price of the second workgroup per CU */
+      const NbLds plain = nb_lds_layout(ctx, false);
+      if (!(p.lds.zfix && p.lds.wgs >= plain.wgs && p.lds.wgs > 0)) { p.fused = false; p.lds = plain; }
+   }
+   /* lean: the fused launch, every tile in ONE launch, the images found at their owners (a decomposed rank: its halo staged directly; its
+    * next exchange packs its messages by a launch of its own, mg_pack3, instead of riding in the reduction launch) */
+   p.lean = may_lean && p.fused && ctx->ntile_class[1] <= 0 && (peers ? p.direct : (ctx->nhalo == 0 || at_owners)) && ctx->lean_pending < LEAN_W &&
+            ctx->lean_since < LEAN_W && (ctx->lean_since == 0 || ctx->lean_dt == dt);
+   if (p.fused && !p.lean)
+      p.red = (ctx->nhalo > 0 && !peers && !at_owners) ? RED_IMAGES : (peers && !ctx->halo_overlap && mg_pack_ready(ctx)) ? RED_PACK : RED_PLAIN;
+   return p;
 }
-static int launch_forces(ddcmi_ctx *ctx, bool defer_reduce = false, FuseArgs *fuse = nullptr /* in: the integrator's pass rides in the pair kernel; out: ->dt = 0 if this launch could not take it */,
-                         bool *lean = nullptr /* in: the caller could run this step lean (ddcmi_ctx::lean_pending); out: this launch did */)
+/* test entry point (ddcmi_test.h): the plan of the evaluation out[0] back from the last one */
+extern "C" int ddcmi_debug_step_plan(ddcmi_ctx *ctx, int out[8])
 {
-   RoctxRange rng_force("DDCENERGY P_FORCE");      /* ddcenergy.c:160-238 */
+   if (!ctx || !out || out[0] < 0 || out[0] >= 16 || out[0] >= ctx->nplan) return DDCMI_EINVAL;
+   const StepPlan &p = ctx->plan_ring[(ctx->nplan - 1 - out[0]) % 16];
+   const int v[8] = {p.halo, p.fused, p.lean, p.lds.lvl, p.lds.zfix, p.red, p.hdisp, p.direct};
+   memcpy(out, v, sizeof(v));
+   return DDCMI_OK;
+}
+
+/* ---- launch_forces and its pieces ---- */
+static void launch_halo_update(ddcmi_ctx *ctx, hipStream_t st, bool hdisp)
+{
+   /* (hdisp: the word of this step's parity is the one this step's pair kernel reads) */
+   if (ctx->nhalo > 0)
+      hipLaunchKernelGGL(k_halo_update, dim3(cdiv(ctx->nhalo, HU_PER)), dim3(HU_THREADS), 0, st, ctx->nloc, ctx->nhalo, ctx->halo_src.p, ctx->halo_shift.p,
+                         ctx->gp.L[0], ctx->gp.L[1], ctx->gp.L[2], ctx->pos.p, ctx->gid.p, false, ctx->hrecv3.p, ctx->hrecv5.p, (const int *)nullptr,
+                         hdisp ? (unsigned long long *)(ctx->d_results + R_DISP + 1) : nullptr, (int)(ctx->loop & 1));
+}
+/* *pending: the refresh runs on the second stream, and ev_halo says when it is done */
+static int refresh_halo(ddcmi_ctx *ctx, const StepPlan &p, bool *pending)
+{
    hipStream_t st = ctx->stream;
-   int n = ctx->nloc, nh = ctx->nhalo;
-   /* Decomposed runs, between rebuilds: the halo exchange (pack, one RCCL message per peer,
-    * unpack) runs on a second stream while this stream computes the tiles whose
-    * neighbourhoods hold owned beads only; the other tiles wait for it. */
-   bool halo_pending = false;
-   /* the received beads' displacement since the rebuild (NbTileArgs::hdisp): measured by the halo update of a decomposed run whose pair
-    * kernel may end its rows early; the word of this step's parity is the one this step's pair kernel reads */
-   /* direct halo staging (ddcmi_ctx::halo_in_recv): the pair kernel takes the received beads out of the exchange's receive buffer, no
-    * update launch -- for halos of received beads only, needed by the pair kernel only */
-   /* (round 6: bonded terms are no obstacle any more -- their kernels take a received partner out of the receive buffer too, k_bonded_gather's bead();
-    *  restraints, constraint groups and the barostat still want every halo bead in pos[]) */
-   const bool direct = !ctx->no_direct_halo && exchanging(ctx) && !ctx->group_ && !ctx->halo_overlap && ctx->nself_images == 0 &&
-                       ctx->nrest == 0 && ctx->ncgroup == 0 && !(ctx->baro_beta > 0.0) && ctx->stage_cap + 2 < 4096 && (ctx->excludePotentialTerm & 128) == 0 && ctx->updateRate > 0;
-   const bool hdisp_on = !direct && ctx->shell_skip && nh > 0 && decomposed(ctx);
-   const int hpar = (int)(ctx->loop & 1);
-   unsigned long long *hmax = hdisp_on ? (unsigned long long *)(ctx->d_results + R_DISP + 1) : nullptr;
-   if (direct && !ctx->halo_fresh)
+   int rc;
+   switch (p.halo)
    {
-      int rc0 = ddcmi_mg_refresh_halo(ctx, st);
-      if (rc0) return rc0;
-      ctx->halo_in_recv = true;      /* (pos[nloc..] keeps the rebuild's records from here on) */
-   }
-   else if ((ctx->nranks > 1 || ctx->loopback) && !ctx->halo_fresh && !ctx->halo_overlap)
-   {
-      int rc0 = ddcmi_mg_refresh_halo(ctx, st);
-      if (rc0) return rc0;
-      ctx->halo_in_recv = false;      /* (the update below places every received bead in pos[]) */
-      if (nh > 0)
-         hipLaunchKernelGGL(k_halo_update, dim3(cdiv(nh, HU_PER)), dim3(HU_THREADS), 0, st, n, nh, ctx->halo_src.p, ctx->halo_shift.p,
-                            ctx->gp.L[0], ctx->gp.L[1], ctx->gp.L[2], ctx->pos.p, ctx->gid.p, false, ctx->hrecv3.p, ctx->hrecv5.p, (const int *)nullptr, hmax, hpar);
-   }
-   else if ((ctx->nranks > 1 || ctx->loopback) && !ctx->halo_fresh)
-   {
+   case HALO_DIRECT: case HALO_UPDATE:
+      if ((rc = ddcmi_mg_refresh_halo(ctx, st))) return rc;
+      /* (direct: pos[nloc..] keeps the rebuild's records from here on; else the update places every received bead in pos[]) */
+      ctx->halo_in_recv = p.halo == HALO_DIRECT;
+      if (p.halo == HALO_UPDATE) launch_halo_update(ctx, st, p.hdisp);
+      break;
+   case HALO_OVERLAP:
       if (!ctx->stream2) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));      /* (the rebuild's interior search may have made it already) */
       if (!ctx->ev_drift)
       {
@@ -101,171 +147,174 @@ static int launch_forces(ddcmi_ctx *ctx, bool defer_reduce = false, FuseArgs *fu
       }
       HIPCHK(ctx, hipEventRecord(ctx->ev_drift, st));                  /* positions of this step are final */
       HIPCHK(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_drift, 0));
-      int rc0 = ddcmi_mg_refresh_halo(ctx, ctx->stream2);
-      if (rc0) return rc0;
-      if (nh > 0)
-         hipLaunchKernelGGL(k_halo_update, dim3(cdiv(nh, HU_PER)), dim3(HU_THREADS), 0, ctx->stream2, n, nh, ctx->halo_src.p, ctx->halo_shift.p,
-                            ctx->gp.L[0], ctx->gp.L[1], ctx->gp.L[2], ctx->pos.p, ctx->gid.p, false, ctx->hrecv3.p, ctx->hrecv5.p, (const int *)nullptr, hmax, hpar);
+      if ((rc = ddcmi_mg_refresh_halo(ctx, ctx->stream2))) return rc;
+      launch_halo_update(ctx, ctx->stream2, p.hdisp);
       HIPCHK(ctx, hipEventRecord(ctx->ev_halo, ctx->stream2));
-      halo_pending = true;
+      *pending = true;
+      break;
+   case HALO_IMAGES: launch_halo_update(ctx, st, p.hdisp); break;
+   case HALO_NONE: case HALO_AT_OWNERS: break;
    }
-   /* (not after a rebuild: it made the images from these very positions; and never on a rank of a transport whose halo is marked fresh --
-    * its last exchange or its rebuild placed every image and halo bead, and the receive buffer may hold velocities or nothing by now) */
-   else if (self_images(ctx)) { }      /* (the pair kernel finds the images at their owners) */
-   else if (nh > 0 && !ctx->images_fresh && !((ctx->nranks > 1 || ctx->loopback) && !ctx->group_))
-      hipLaunchKernelGGL(k_halo_update, dim3(cdiv(nh, HU_PER)), dim3(HU_THREADS), 0, st, n, nh, ctx->halo_src.p, ctx->halo_shift.p,
-                         ctx->gp.L[0], ctx->gp.L[1], ctx->gp.L[2], ctx->pos.p, ctx->gid.p, false, ctx->hrecv3.p, ctx->hrecv5.p, (const int *)nullptr, hmax, hpar);
-   ctx->images_fresh = false;
+   return DDCMI_OK;
+}
+/* fb: the bonded kernels' force records, or null */
+static NbTileArgs nb_tile_args(const ddcmi_ctx *ctx, const StepPlan &p, double4 *fb)
+{
+   NbTileArgs na;
+   na.ntile = ctx->ntile; na.stage_stride = ctx->stage_cap; na.nlj = ctx->nnb;
+   na.cap = ctx->stage_cap + 2;      /* + sentinel slot 0, kept even so every LDS array stays 16-byte aligned */
+   na.cell_start_o = ctx->cell_start_o.p; na.stage_idx = ctx->stage_idx.p; na.tile_nstage = ctx->tile_nstage.p;
+   na.cell_start = ctx->cell_start.p; na.cell_cnt = ctx->cell_cnt.p;
+   na.tile_base = ctx->tile_base.p; na.tile_width = ctx->tile_width.p; na.tile_rows = ctx->tile_rows.p;
+   na.nbr16 = ctx->nbr16.p; na.nbr_cnt = ctx->nbr_cnt.p; na.perm = ctx->tile_perm.p;
+   na.tile_work = ctx->tile_work.p; na.halo_shift = ctx->halo_shift.p; na.nloc = ctx->nloc;
+   na.disp = ctx->shell_skip ? ctx->d_results + R_DISP : nullptr; na.nbr_cum = ctx->nbr_cum.p; na.sh_r0sq = ctx->sh_r0sq; na.sh_step = ctx->sh_step;
+   na.sh_reach[0] = -1e300;
+   for (int sq = 1; sq < NSHELL; sq++) na.sh_reach[sq] = sqrt(ctx->sh_r0sq + (double)(sq - 1) * ctx->sh_step) * (1.0 - 1e-4) - ctx->rmax;
+   na.hdisp = p.hdisp ? ctx->d_results + R_DISP + 1 + (int)(ctx->loop & 1) : nullptr;
+   na.hrecv3 = ctx->halo_in_recv ? ctx->hrecv3.p : nullptr; na.halo_src = ctx->halo_src.p;
+   na.halo_full_walk = (p.direct && ctx->shell_skip) ? 1 : 0;
+   na.lvlidx = ctx->d_lvlidx.p; na.nlvl = ctx->nlvl; na.tab_off = p.lds.tab_off;
+   na.fb = fb;
+   na.self_img = p.halo == HALO_AT_OWNERS ? 1 : 0; na.vring_w = nullptr; na.vring_dt = ctx->lean_dt;
+   na.vring = (na.disp && ctx->lean_since > 0) ? ctx->d_vring.p : nullptr; na.vring_n = ctx->lean_since;
+   return na;
+}
+/* timing (ddcmi_ctx::timing): an event pair around a pair launch; *close is the second one, null where nothing is timed */
+static int timing_open(ddcmi_ctx *ctx, bool fused, hipEvent_t *close)
+{
+   *close = nullptr;
+   if (!ctx->timing) return DDCMI_OK;
+   if (ctx->ev_used + 2 > ctx->ev.size())
+   {
+      size_t old = ctx->ev.size();
+      ctx->ev.resize(old + 256);
+      for (size_t k = old; k < ctx->ev.size(); k++) HIPCHK(ctx, hipEventCreate(&ctx->ev[k]));
+   }
+   hipEvent_t e0 = ctx->ev[ctx->ev_used++];
+   *close = ctx->ev[ctx->ev_used++];
+   ctx->ev_fused.resize(ctx->ev.size() / 2);
+   ctx->ev_fused[ctx->ev_used / 2 - 1] = fused ? 1 : 0;
+   HIPCHK(ctx, hipEventRecord(e0, ctx->stream));
+   return DDCMI_OK;
+}
+static int timing_close(ddcmi_ctx *ctx, hipEvent_t close) { if (close) HIPCHK(ctx, hipEventRecord(close, ctx->stream)); return DDCMI_OK; }
+/* one k_nonbond launch.  Q: charges; PS: the list entries carry the shifted-copy bit (pack_type 2); Z: NB_ZOFF, the fixed LDS layout
+ * ({x,y} at 0, z at NB_ZOFF: neighbourhoods of up to NB_ZOFF/16 beads, which is every Martini system), or 0, the run-time layout;
+ * F: the integrator's pass rides; L: the pair table in two levels */
+template <bool Q, bool PS, int Z, bool F, bool L>
+static int launch_nonbond(ddcmi_ctx *ctx, int grid, size_t lds, const NbTileArgs &na, double *partials, const FuseArgs &fa)
+{
+   const void *fn = (const void *)k_nonbond<Q, PS, PS, NB_THREADS, NB_WPE, NB_CH, Z, F, L>;
+   size_t sb = 0;
+   if (!lds_starts_at_zero(ctx->device, fn, &sb))
+      SETERR(ctx, DDCMI_EUNSUPPORTED, "k_nonbond was built with %zu bytes of static LDS: its staged arrays no longer start at LDS address 0 (toolchain change) -- rebuild libddcmi.so with a compiler that gives it none", sb);
+   HIPCHK(ctx, dyn_lds_limit(ctx->device, fn, (int)lds));
+   hipLaunchKernelGGL((k_nonbond<Q, PS, PS, NB_THREADS, NB_WPE, NB_CH, Z, F, L>), dim3(grid), dim3(NB_THREADS), lds, ctx->stream, ctx->gp, na, ctx->npad, ctx->pos.p, ctx->d_kqtab.p,
+                      ctx->excl16.p, ctx->excl_cnt.p, L ? ctx->d_lvltab.p : ctx->d_ljtab.p, ctx->rmax * ctx->rmax, ctx->krf, ctx->crf, ctx->keR,
+                      ctx->fx.p, ctx->fy.p, ctx->fz.p, partials, fa);
+   return DDCMI_OK;
+}
+/* the instantiations that exist: fused ones with the fixed layout only (plan_forces sees to it), plain ones with either */
+template <bool Q, bool PS>
+static int launch_nonbond_as(ddcmi_ctx *ctx, const StepPlan &p, int grid, const NbTileArgs &na, double *partials, const FuseArgs &fa)
+{
+   const size_t lds = p.lds.total;
+   if (p.fused) return p.lds.lvl ? launch_nonbond<Q, PS, NB_ZOFF, true, true>(ctx, grid, lds, na, partials, fa) : launch_nonbond<Q, PS, NB_ZOFF, true, false>(ctx, grid, lds, na, partials, fa);
+   if (p.lds.zfix) return p.lds.lvl ? launch_nonbond<Q, PS, NB_ZOFF, false, true>(ctx, grid, lds, na, partials, fa) : launch_nonbond<Q, PS, NB_ZOFF, false, false>(ctx, grid, lds, na, partials, fa);
+   return p.lds.lvl ? launch_nonbond<Q, PS, 0, false, true>(ctx, grid, lds, na, partials, fa) : launch_nonbond<Q, PS, 0, false, false>(ctx, grid, lds, na, partials, fa);
+}
+/* the pair kernel's side of a force evaluation.  Bonded terms and restraints FIRST, into a zeroed array of force records (ddcmi_ctx::fb):
+ * the pair kernel then finishes every bead's force in ONE place -- in memory (plain launch: f = f_pair + f_bonded) or in registers in
+ * front of the integrator's pass (FUSE), so that systems with bonded terms take the fused step too.  Both kinds of launch form the same
+ * sum, so the fused and the split step stay bit for bit alike, and both hand the records back zeroed: no launch is ever spent on
+ * clearing them. */
+static int launch_pair_forces(ddcmi_ctx *ctx, const StepPlan &p, bool defer_reduce, const FuseArgs *fuse, bool halo_pending)
+{
+   hipStream_t st = ctx->stream;
+   const int n = ctx->nloc;
    const bool has_bonded = (ctx->nbond + ctx->nangle + ctx->ntors + ctx->nrest) > 0;
-   const double self = ((ctx->excludePotentialTerm & 128) == 0) ? ctx->self_ele : 0.0;
-   if ((ctx->excludePotentialTerm & 128) == 0)
+   int rc;
+   FuseArgs fa;
+   memset(&fa, 0, sizeof(fa));
+   if (p.fused) { fa = *fuse; fa.ke_off = p.lds.ke_off; }
+   if (has_bonded && n == 0)
+      /* a domain that holds no bead at the moment: no bonded launch -- and the sums of the last one it ran must not be reported again
+       * (forces were never affected.  tools/soak_migration_r06.py lipid) */
+      HIPCHK(ctx, hipMemsetAsync(ctx->d_results + R_SCR_BOND, 0, (R_SCR_MOLV - R_SCR_BOND) * sizeof(double), st));
+   if (has_bonded && n > 0)
    {
-      /* Bonded terms and restraints FIRST, into a zeroed array of force records (ddcmi_ctx::fb): the pair kernel then finishes every bead's
-       * force in ONE place -- in memory (plain launch: f = f_pair + f_bonded) or in registers in front of the integrator's pass (FUSE), so
-       * that systems with bonded terms take the fused step too (the lipid box paid a separate 54 us kick kernel and a force
-       * store + re-read).  Both kinds of launch form the same sum, so the fused and the split step stay bit for bit alike, and both hand
-       * the records back zeroed: no launch is ever spent on clearing them. */
-      int ntile = ctx->ntile;
-      bool useq = ctx->has_charge;
-      const bool shbit = ctx->pack_type == 2;
-      const size_t capl = (size_t)ctx->stage_cap + 2;      /* + sentinel slot 0, kept even so every LDS array stays 16-byte aligned */
-      FuseArgs fa;
-      memset(&fa, 0, sizeof(fa));
-      NbLds lay = nb_lds_layout(ctx, fuse != nullptr);
-      if (fuse)
-      {
-         /* the integrator's pass rides in the pair kernel only with the fixed layout, and never at the price of the second workgroup per CU */
-         const NbLds plain = nb_lds_layout(ctx, false);
-         if (lay.zfix && lay.wgs >= plain.wgs && lay.wgs > 0) { fa = *fuse; fa.ke_off = lay.ke_off; }
-         else { fuse->dt = 0.0; fuse = nullptr; lay = plain; }
-      }
-      /* lean (the caller could run this step lean): the fused launch, every tile in ONE launch, the images found at their owners */
-      /* (a decomposed rank: its next exchange packs its messages by a launch of its own, mg_pack3, instead of riding in the reduction launch) */
-      const bool lean_now = lean && *lean && fuse != nullptr && ctx->ntile_class[1] <= 0 && ((ctx->nranks > 1 || ctx->loopback) ? direct : (nh == 0 || self_images(ctx))) && ctx->lean_pending < LEAN_W &&
-                            ctx->lean_since < LEAN_W && (ctx->lean_since == 0 || ctx->lean_dt == fuse->dt);
-      if (lean) *lean = lean_now;
-      if (has_bonded && n == 0)
-         /* a domain that holds no bead at the moment: no bonded launch -- and the sums of the last one it ran must not be reported again (until round 6 an
-          * emptied domain kept adding its last bonded energies and virial to the run's; forces were never affected.  tools/soak_migration_r06.py lipid) */
-         HIPCHK(ctx, hipMemsetAsync(ctx->d_results + R_SCR_BOND, 0, (R_SCR_MOLV - R_SCR_BOND) * sizeof(double), st));
-      if (has_bonded && n > 0)
-      {
-         if (halo_pending) { HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev_halo, 0)); halo_pending = false; }      /* bonded partners may be halo beads */
-         /* (the record array: all zero -- every pair launch hands back zeroed what it consumed; a grown array is cleared once) */
-         if (ctx->fb.cap < (size_t)ctx->npad) { if (ctx->fb.ensure(ctx->npad)) SETERR(ctx, DDCMI_ENOMEM, "bonded force records"); ctx->fb_zeroed = 0; }
-         if (ctx->fb_zeroed < ctx->fb.cap) { HIPCHK(ctx, hipMemsetAsync(ctx->fb.p, 0, ctx->fb.cap * sizeof(double4), st)); ctx->fb_zeroed = ctx->fb.cap; }
-         ctx->fb_zeroed = 0;      /* (until the pair launches below have consumed the records) */
-         int rcb = ddcmi_launch_bonded(ctx, ctx->fb.p, lean_now ? ctx->lean_pending : -1);      /* (lean: the kernels' sums wait in the step's slot of the ring) */
-         if (rcb) return rcb;
-      }
-      /* fixed LDS layout ({x,y} at 0, z at NB_ZOFF) for neighbourhoods of up to NB_ZOFF/16 beads, which is every Martini system; else the run-time layout */
-      const bool zfix = lay.zfix, lvl = lay.lvl;
-      const size_t lds = lay.total;
-      if (lay.wgs <= 0) SETERR(ctx, DDCMI_EUNSUPPORTED, "nonbonded kernel needs %zu bytes of LDS (> 160 KiB)", lds);
-      NbTileArgs na;
-      na.ntile = ntile; na.stage_stride = ctx->stage_cap; na.cap = (int)capl; na.nlj = ctx->nnb;
-      na.cell_start_o = ctx->cell_start_o.p; na.stage_idx = ctx->stage_idx.p; na.tile_nstage = ctx->tile_nstage.p;
-      na.cell_start = ctx->cell_start.p; na.cell_cnt = ctx->cell_cnt.p;
-      na.tile_base = ctx->tile_base.p; na.tile_width = ctx->tile_width.p; na.tile_rows = ctx->tile_rows.p;
-      na.nbr16 = ctx->nbr16.p; na.nbr_cnt = ctx->nbr_cnt.p; na.perm = ctx->tile_perm.p;
-      na.tile_work = ctx->tile_work.p; na.halo_shift = ctx->halo_shift.p; na.nloc = n;
-      na.disp = ctx->shell_skip ? ctx->d_results + R_DISP : nullptr; na.nbr_cum = ctx->nbr_cum.p; na.sh_r0sq = ctx->sh_r0sq; na.sh_step = ctx->sh_step;
-      na.sh_reach[0] = -1e300;
-      for (int sq = 1; sq < NSHELL; sq++) na.sh_reach[sq] = sqrt(ctx->sh_r0sq + (double)(sq - 1) * ctx->sh_step) * (1.0 - 1e-4) - ctx->rmax;
-      na.hdisp = hdisp_on ? ctx->d_results + R_DISP + 1 + hpar : nullptr;
-      na.hrecv3 = ctx->halo_in_recv ? ctx->hrecv3.p : nullptr; na.halo_src = ctx->halo_src.p;
-      na.halo_full_walk = (direct && ctx->shell_skip) ? 1 : 0;
-      na.lvlidx = ctx->d_lvlidx.p; na.nlvl = ctx->nlvl; na.tab_off = lay.tab_off;
-      na.fb = (has_bonded && n > 0) ? ctx->fb.p : nullptr;
-      na.self_img = self_images(ctx) ? 1 : 0; na.vring_w = nullptr; na.vring_dt = ctx->lean_dt;
-      na.vring = (na.disp && ctx->lean_since > 0) ? ctx->d_vring.p : nullptr; na.vring_n = ctx->lean_since;
-      double *partials_p = ctx->partials.p;
-      if (lean && *lean)
-      {
-         const size_t stride = (size_t)(ctx->nitems + 8) * 8;
-         if (ctx->lean_pending > 0 && stride != ctx->lean_stride) SETERR(ctx, DDCMI_EINVAL, "internal: the lean steps' rows changed size without a flush");
-         ctx->lean_stride = stride;
-         ENSURE(ctx, ctx->lean_part, stride * LEAN_W); ENSURE(ctx, ctx->lean_kpart, stride * LEAN_W);
-         partials_p = ctx->lean_part.p + stride * ctx->lean_pending;
-         fa.kpartials = ctx->lean_kpart.p + stride * ctx->lean_pending;
-         ctx->lean_dt = fa.dt; na.vring_dt = fa.dt;
-         if (na.disp) na.vring_w = ctx->d_vring.p + (size_t)LEAN_VSTRIDE * ctx->lean_since;
-         ctx->lean_since++;
-      }
-#define LAUNCH_NB(Q, P, S, NT) do { if (zfix) LAUNCH_NBZ(Q, P, S, NT, NB_ZOFF); else LAUNCH_NBZ(Q, P, S, NT, 0); } while (0)
-#define LAUNCH_NBZ(Q, P, S, NT, Z) LAUNCH_NBF(Q, P, S, NT, Z, false)
-#define LAUNCH_NBF(Q, P, S, NT, Z, F) do { if (lvl) LAUNCH_NBL(Q, P, S, NT, Z, F, true); else LAUNCH_NBL(Q, P, S, NT, Z, F, false); } while (0)
-#define LAUNCH_NBL(Q, P, S, NT, Z, F, L) do { \
-         size_t sb_ = 0; \
-         if (!lds_starts_at_zero(ctx->device, (const void *)k_nonbond<Q, P, S, NT, NB_WPE, NB_CH, Z, F, L>, &sb_)) \
-            SETERR(ctx, DDCMI_EUNSUPPORTED, "k_nonbond was built with %zu bytes of static LDS: its staged arrays no longer start at LDS address 0 (toolchain change) -- rebuild libddcmi.so with a compiler that gives it none", sb_); \
-         HIPCHK(ctx, dyn_lds_limit(ctx->device, (const void *)k_nonbond<Q, P, S, NT, NB_WPE, NB_CH, Z, F, L>, (int)lds)); \
-         hipLaunchKernelGGL((k_nonbond<Q, P, S, NT, NB_WPE, NB_CH, Z, F, L>), dim3(grid), dim3(NT), lds, st, ctx->gp, na, ctx->npad, ctx->pos.p, ctx->d_kqtab.p, \
-                            ctx->excl16.p, ctx->excl_cnt.p, (L) ? ctx->d_lvltab.p : ctx->d_ljtab.p, ctx->rmax * ctx->rmax, ctx->krf, ctx->crf, ctx->keR, \
-                            ctx->fx.p, ctx->fy.p, ctx->fz.p, partials_p, fa); } while (0)
-#define LAUNCH_NB2(Q, P, S) LAUNCH_NB(Q, P, S, NB_THREADS)
-      /* class 0: tiles with all-owned neighbourhoods (every tile on a single domain);
-       * class 1: tiles that stage image/halo beads, after the halo exchange */
-      RoctxRange rng_nb("CHARMM_NONBOND");      /* martiniNonBond, bioMartini.c:989-1122 */
-      for (int cls = 0; cls < 2; cls++)
-      {
-         if (cls == 1 && halo_pending) { HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev_halo, 0)); halo_pending = false; }
-         if (ctx->ntile_class[cls] <= 0) continue;
-         const double *hd_keep = na.hdisp;
-         if (cls == 0 && halo_pending) na.hdisp = nullptr;      /* (tiles that stage owned beads only, while the exchange still writes the word) */
-         const int grid = 8 * std::max(ctx->sched_longest[cls], 1);
-         na.sched = ctx->sched.p + 16 * cls;
-         hipEvent_t e0 = nullptr, e1 = nullptr;
-         if (ctx->timing)
-         {
-            if (ctx->ev_used + 2 > ctx->ev.size())
-            {
-               size_t old = ctx->ev.size();
-               ctx->ev.resize(old + 256);
-               for (size_t k = old; k < ctx->ev.size(); k++) HIPCHK(ctx, hipEventCreate(&ctx->ev[k]));
-            }
-            e0 = ctx->ev[ctx->ev_used++]; e1 = ctx->ev[ctx->ev_used++];
-            ctx->ev_fused.resize(ctx->ev.size() / 2);
-            ctx->ev_fused[ctx->ev_used / 2 - 1] = fuse ? 1 : 0;
-            HIPCHK(ctx, hipEventRecord(e0, st));
-         }
-         if (fuse && useq && shbit) LAUNCH_NBF(true, true, true, NB_THREADS, NB_ZOFF, true);      /* (fuse: fixed LDS layout) */
-         else if (fuse && useq) LAUNCH_NBF(true, false, false, NB_THREADS, NB_ZOFF, true);
-         else if (fuse && shbit) LAUNCH_NBF(false, true, true, NB_THREADS, NB_ZOFF, true);
-         else if (fuse) LAUNCH_NBF(false, false, false, NB_THREADS, NB_ZOFF, true);
-         else if (useq && shbit) LAUNCH_NB2(true, true, true);
-         else if (useq) LAUNCH_NB2(true, false, false);
-         else if (shbit) LAUNCH_NB2(false, true, true);
-         else LAUNCH_NB2(false, false, false);
-         if (ctx->timing) HIPCHK(ctx, hipEventRecord(e1, st));
-         na.hdisp = hd_keep;
-      }
-#undef LAUNCH_NB2
-#undef LAUNCH_NB
-#undef LAUNCH_NBZ
-#undef LAUNCH_NBF
-#undef LAUNCH_NBL
-      if (na.fb) ctx->fb_zeroed = ctx->fb.cap;
-      if (ctx->timing) { ctx->t_launches++; if (fuse) ctx->t_launches_fused++; }          /* per force evaluation: the event pairs of both classes add up */
-      /* the final energies are formed in the same launch (the bonded kernels' sums are complete: they ran first) */
-      if (!defer_reduce)
-      {
-         RedJob j0 = {ctx->partials.p, ctx->nitems, 8, ctx->d_results + R_NB_LJ, 1};
-         hipLaunchKernelGGL(k_reduce_jobs, dim3(RED_SPLIT, 1), dim3(1024), 0, st, j0, j0, ctx->d_results, self, ctx->red_tmp.p);
-      }
-      ctx->forces_valid = true;
-      return DDCMI_OK;
+      if (halo_pending) { HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev_halo, 0)); halo_pending = false; }      /* bonded partners may be halo beads */
+      /* (the record array: all zero -- every pair launch hands back zeroed what it consumed; a grown array is cleared once) */
+      if (ctx->fb.cap < (size_t)ctx->npad) { if (ctx->fb.ensure(ctx->npad)) SETERR(ctx, DDCMI_ENOMEM, "bonded force records"); ctx->fb_zeroed = 0; }
+      if (ctx->fb_zeroed < ctx->fb.cap) { HIPCHK(ctx, hipMemsetAsync(ctx->fb.p, 0, ctx->fb.cap * sizeof(double4), st)); ctx->fb_zeroed = ctx->fb.cap; }
+      ctx->fb_zeroed = 0;      /* (until the pair launches below have consumed the records) */
+      if ((rc = ddcmi_launch_bonded(ctx, ctx->fb.p, p.lean ? ctx->lean_pending : -1))) return rc;      /* (lean: the kernels' sums wait in the step's slot of the ring) */
    }
-   else
+   if (p.lds.wgs <= 0) SETERR(ctx, DDCMI_EUNSUPPORTED, "nonbonded kernel needs %zu bytes of LDS (> 160 KiB)", p.lds.total);
+   NbTileArgs na = nb_tile_args(ctx, p, (has_bonded && n > 0) ? ctx->fb.p : nullptr);
+   double *partials = ctx->partials.p;
+   if (p.lean)
    {
-      if (!defer_reduce) HIPCHK(ctx, hipMemsetAsync(ctx->d_results, 0, 8 * sizeof(double), st));
-      hipLaunchKernelGGL(k_zero3, dim3(cdiv(n, 256)), dim3(256), 0, st, n, ctx->fx.p, ctx->fy.p, ctx->fz.p);
+      /* the step's rows of sums go to its slot of the ring, its largest |v|^2 to its word */
+      const size_t stride = (size_t)(ctx->nitems + 8) * 8;
+      if (ctx->lean_pending > 0 && stride != ctx->lean_stride) SETERR(ctx, DDCMI_EINVAL, "internal: the lean steps' rows changed size without a flush");
+      ctx->lean_stride = stride;
+      ENSURE(ctx, ctx->lean_part, stride * LEAN_W); ENSURE(ctx, ctx->lean_kpart, stride * LEAN_W);
+      partials = ctx->lean_part.p + stride * ctx->lean_pending;
+      fa.kpartials = ctx->lean_kpart.p + stride * ctx->lean_pending;
+      ctx->lean_dt = fa.dt; na.vring_dt = fa.dt;
+      if (na.disp) na.vring_w = ctx->d_vring.p + (size_t)LEAN_VSTRIDE * ctx->lean_since;
+      ctx->lean_since++;
    }
+   /* class 0: tiles with all-owned neighbourhoods (every tile on a single domain);
+    * class 1: tiles that stage image/halo beads, after the halo exchange */
+   RoctxRange rng_nb("CHARMM_NONBOND");      /* martiniNonBond, bioMartini.c:989-1122 */
+   const bool useq = ctx->has_charge, shbit = ctx->pack_type == 2;
+   for (int cls = 0; cls < 2; cls++)
+   {
+      if (cls == 1 && halo_pending) { HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev_halo, 0)); halo_pending = false; }
+      if (ctx->ntile_class[cls] <= 0) continue;
+      const double *hd_keep = na.hdisp;
+      if (cls == 0 && halo_pending) na.hdisp = nullptr;      /* (tiles that stage owned beads only, while the exchange still writes the word) */
+      const int grid = 8 * std::max(ctx->sched_longest[cls], 1);
+      na.sched = ctx->sched.p + 16 * cls;
+      hipEvent_t e1;
+      if ((rc = timing_open(ctx, p.fused, &e1))) return rc;
+      rc = useq ? (shbit ? launch_nonbond_as<true, true>(ctx, p, grid, na, partials, fa) : launch_nonbond_as<true, false>(ctx, p, grid, na, partials, fa))
+                : (shbit ? launch_nonbond_as<false, true>(ctx, p, grid, na, partials, fa) : launch_nonbond_as<false, false>(ctx, p, grid, na, partials, fa));
+      if (rc || (rc = timing_close(ctx, e1))) return rc;
+      na.hdisp = hd_keep;
+   }
+   if (na.fb) ctx->fb_zeroed = ctx->fb.cap;
+   if (ctx->timing) { ctx->t_launches++; if (p.fused) ctx->t_launches_fused++; }          /* per force evaluation: the event pairs of both classes add up */
+   /* the final energies are formed in the same launch (the bonded kernels' sums are complete: they ran first) */
+   if (!defer_reduce)
+   {
+      RedJob j0 = {ctx->partials.p, ctx->nitems, 8, ctx->d_results + R_NB_LJ, 1};
+      hipLaunchKernelGGL(k_reduce_jobs, dim3(RED_SPLIT, 1), dim3(1024), 0, st, j0, j0, ctx->d_results, ctx->self_ele, ctx->red_tmp.p);
+   }
+   ctx->forces_valid = true;
+   return DDCMI_OK;
+}
+/* plans the evaluation (ddcmi_ctx::plan keeps the plan for the caller and the tests) and executes it.  fuse: the integrator's pass may
+ * ride in the pair kernel; may_lean: the caller could run this step lean */
+static int launch_forces(ddcmi_ctx *ctx, bool defer_reduce = false, const FuseArgs *fuse = nullptr, bool may_lean = false)
+{
+   RoctxRange rng_force("DDCENERGY P_FORCE");      /* ddcenergy.c:160-238 */
+   const StepPlan p = ctx->plan = ctx->plan_ring[ctx->nplan++ % 16] = plan_forces(ctx, fuse != nullptr, may_lean, fuse ? fuse->dt : 0.0);
+   hipStream_t st = ctx->stream;
+   bool halo_pending = false;
+   int rc;
+   if ((rc = refresh_halo(ctx, p, &halo_pending))) return rc;
+   ctx->images_fresh = false;
+   if ((ctx->excludePotentialTerm & 128) == 0) return launch_pair_forces(ctx, p, defer_reduce, fuse, halo_pending);
+   /* no pair kernel: zeroed forces, the bonded kernels add to them */
+   if (!defer_reduce) HIPCHK(ctx, hipMemsetAsync(ctx->d_results, 0, 8 * sizeof(double), st));
+   hipLaunchKernelGGL(k_zero3, dim3(cdiv(ctx->nloc, 256)), dim3(256), 0, st, ctx->nloc, ctx->fx.p, ctx->fy.p, ctx->fz.p);
    if (halo_pending) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev_halo, 0));      /* bonded partners may be halo beads */
-   int rc = ddcmi_launch_bonded(ctx);
-   if (rc) return rc;
-   if (!defer_reduce && (has_bonded || (ctx->excludePotentialTerm & 128) != 0))
-      hipLaunchKernelGGL(k_finish_energy, dim3(1), dim3(64), 0, st, ctx->d_results, self);
+   if ((rc = ddcmi_launch_bonded(ctx))) return rc;
+   if (!defer_reduce) hipLaunchKernelGGL(k_finish_energy, dim3(1), dim3(64), 0, st, ctx->d_results, 0.0);
    ctx->forces_valid = true;
    return DDCMI_OK;
 }
@@ -451,8 +500,6 @@ static GroupLambda front_lambda(const ddcmi_ctx *ctx, double dt)
  *   b  barostat: pressures, scale factors, box; FRONT half kick (+ drift unless constraints follow)
  *                                                                            -> velocity halo (constraints only)
  *   c  constraints: FRONT solve, drift; clock */
-struct PackJob;
-static bool ddcmi_mg_pack_job(ddcmi_ctx *ctx, PackJob *pk);
 int ddcmi_mg_refresh_vel(ddcmi_ctx *ctx);
 static int step_pre_a(ddcmi_ctx *ctx)
 {
@@ -558,19 +605,6 @@ static int step_pre(ddcmi_ctx *ctx, double dt)
    if (!had_drift && cons_exchange(ctx) && (rc = ddcmi_mg_refresh_vel(ctx))) return rc;
    return step_pre_c(ctx, dt);
 }
-/* nglf.c:97-108: ddcenergy, BACK half kick, kinetic_terms, group Update */
-/* may the integrator's pass ride in the pair kernel (k_nonbond<..., FUSE>)?  The force must be complete when the list walk ends
- * and the step must need nothing between the force and the drift */
-static bool fuse_ok(const ddcmi_ctx *ctx)
-{
-   static const bool off = getenv("DDCMI_NO_FUSED_STEP") != nullptr;
-   if (off || ctx->nloc <= 0 || ctx->group_) return false;
-   if ((ctx->excludePotentialTerm & 128) != 0) return false;
-   /* (bonded terms, restraints and charges are no obstacle: their kernels run in front of the pair kernel, the excluded-pair loop ends before the epilogue) */
-   if (ctx->ncgroup > 0 || ctx->baro_beta > 0.0) return false;
-   for (int g = 0; g < ctx->ngroup; g++) if (ctx->gtype[g] != DDCMI_FREE && ctx->gtype[g] != DDCMI_BERENDSEN) return false;
-   return true;
-}
 static int step_post_cons_b(ddcmi_ctx *ctx, double dt)
 {
    int rc;
@@ -578,6 +612,14 @@ static int step_post_cons_b(ddcmi_ctx *ctx, double dt)
    GroupLambda lam = front_lambda(ctx, dt);
    return launch_kinetic(ctx, dt, 0, true, &lam, false);
 }
+/* behind a plain force launch: BACK kick, kinetic terms, the forces' reduction and the coming step's FRONT kick + drift in one kernel */
+static int kick_ke_then_drift(ddcmi_ctx *ctx, double dt, const GroupLambda &lam)
+{
+   const int rc = launch_kinetic(ctx, dt, 1, true, &lam, true);
+   if (!rc) ctx->drift_done = true;
+   return rc;
+}
+/* nglf.c:97-108: ddcenergy, BACK half kick, kinetic_terms, group Update */
 static int step_post(ddcmi_ctx *ctx, double dt, bool more_steps)
 {
    int rc;
@@ -592,9 +634,7 @@ static int step_post(ddcmi_ctx *ctx, double dt, bool more_steps)
       {
          /* (groups with different Berendsen factors this step: the split kernels, with the factors just formed) */
          if ((rc = launch_forces(ctx, true))) return rc;
-         if ((rc = launch_kinetic(ctx, dt, 1, true, &lam_f, true))) return rc;
-         ctx->drift_done = true;
-         return DDCMI_OK;
+         return kick_ke_then_drift(ctx, dt, lam_f);
       }
    }
    if (fuse)
@@ -609,7 +649,7 @@ static int step_post(ddcmi_ctx *ctx, double dt, bool more_steps)
       fa.vx = ctx->vx.p; fa.vy = ctx->vy.p; fa.vz = ctx->vz.p;
       ENSURE(ctx, ctx->kpartials, (size_t)(std::max(ctx->nitems, cdiv(ctx->nloc, DDCMI_BLOCK * KE_PER)) + 8) * 8);
       ENSURE(ctx, ctx->pos2, (size_t)ctx->nloc + ctx->nhalo);      /* (the size ddcmi_bl_reserve_halo gave both buffers: no reallocation here) */
-      if (ctx->nhalo > 0 && (ctx->nranks > 1 || ctx->loopback) && ctx->fuse_tags_of != ctx->nrebuild)
+      if (ctx->nhalo > 0 && has_peers(ctx) && ctx->fuse_tags_of != ctx->nrebuild)
       {
          /* received halo beads keep their tag word where they lie (k_halo_update rewrites x y z only): both buffers need it
           * (the periodic images of a single domain are whole copies of their owners' records) */
@@ -617,47 +657,33 @@ static int step_post(ddcmi_ctx *ctx, double dt, bool more_steps)
          ctx->fuse_tags_of = ctx->nrebuild;
       }
       fa.pos_new = ctx->pos2.p; fa.kpartials = ctx->kpartials.p;
-      /* lean: a single domain of FREE beads with nothing but the pair kernel in its step */
-      bool lean = lean_capable(ctx);
-      if ((rc = launch_forces(ctx, true, &fa, &lean))) return rc;
-      if (fa.dt != 0.0 && lean)
+      if ((rc = launch_forces(ctx, true, &fa, lean_capable(ctx)))) return rc;
+      const StepPlan &p = ctx->plan;
+      if (!p.fused) return kick_ke_then_drift(ctx, dt, lam);      /* (the launch kept the plain kernel: LDS layout; the kick follows as usual) */
+      ctx->drift_done = true;
+      std::swap(ctx->pos, ctx->pos2);
+      if (p.lean)
       {
          /* the kernel has left the step's rows of sums in the ring, moved the displacement bound on and will find the images at their owners */
-         std::swap(ctx->pos, ctx->pos2);
          ctx->lean_pending++;
-         ctx->drift_done = true;
          return ctx->lean_pending >= LEAN_W ? ddcmi_lean_flush(ctx) : DDCMI_OK;
       }
-      if (fa.dt != 0.0)
+      RedJob jf = {ctx->partials.p, ctx->nitems, 8, ctx->d_results + R_NB_LJ, 1};
+      RedJob jk = {ctx->kpartials.p, ctx->nitems, 7, ctx->d_results + R_RK, 0, dt, ctx->d_results + R_DISP};      /* + this drift's share of the displacement bound */
+      if (p.red == RED_PLAIN)
+         hipLaunchKernelGGL(k_reduce_jobs, dim3(RED_SPLIT, 2), dim3(1024), 0, ctx->stream, jf, jk, ctx->d_results, ctx->self_ele, ctx->red_tmp.p);
+      else
       {
-         RedJob jf = {ctx->partials.p, ctx->nitems, 8, ctx->d_results + R_NB_LJ, 1};
-         RedJob jk = {ctx->kpartials.p, ctx->nitems, 7, ctx->d_results + R_RK, 0, dt, ctx->d_results + R_DISP};      /* + this drift's share of the displacement bound */
-         std::swap(ctx->pos, ctx->pos2);
+         /* on the side, in the same launch: the periodic images at the drifted positions, which the next force evaluation finds fresh -- or
+          * this rank's halo messages packed from the drifted positions, so that the next step's exchange starts with the sends */
          PackJob pk;
-         memset(&pk, 0, sizeof(pk));
-         if (ctx->nhalo > 0 && ctx->nranks == 1 && !ctx->loopback && !self_images(ctx))
-         {
-            /* + the periodic images at the drifted positions, in the same launch: the next force evaluation finds them fresh */
-            ImageJob im = {ctx->nloc, ctx->nhalo, ctx->halo_src.p, ctx->halo_shift.p, ctx->gp.L[0], ctx->gp.L[1], ctx->gp.L[2], ctx->pos.p};
-            hipLaunchKernelGGL(k_reduce_jobs_images, dim3(2 * RED_SPLIT + cdiv(ctx->nhalo, 1024)), dim3(1024), 0, ctx->stream, jf, jk, ctx->d_results, ctx->self_ele, ctx->red_tmp.p, im, pk);
-            ctx->images_fresh = true;
-         }
-         else if ((ctx->nranks > 1 || ctx->loopback) && !ctx->halo_overlap && ddcmi_mg_pack_job(ctx, &pk) && pk.nsend > 0)
-         {
-            /* + this rank's halo messages packed from the drifted positions: the next step's exchange starts with the sends */
-            ImageJob im;
-            memset(&im, 0, sizeof(im));
-            hipLaunchKernelGGL(k_reduce_jobs_images, dim3(2 * RED_SPLIT + cdiv(pk.nsend, 1024)), dim3(1024), 0, ctx->stream, jf, jk, ctx->d_results, ctx->self_ele, ctx->red_tmp.p, im, pk);
-            ctx->pack_fresh = true;
-         }
-         else
-            hipLaunchKernelGGL(k_reduce_jobs, dim3(RED_SPLIT, 2), dim3(1024), 0, ctx->stream, jf, jk, ctx->d_results, ctx->self_ele, ctx->red_tmp.p);
-         ctx->drift_done = true;
-         return DDCMI_OK;
+         ImageJob im;
+         memset(&pk, 0, sizeof(pk)); memset(&im, 0, sizeof(im));
+         if (p.red == RED_IMAGES) im = ImageJob{ctx->nloc, ctx->nhalo, ctx->halo_src.p, ctx->halo_shift.p, ctx->gp.L[0], ctx->gp.L[1], ctx->gp.L[2], ctx->pos.p};
+         else ddcmi_mg_pack_job(ctx, &pk);
+         hipLaunchKernelGGL(k_reduce_jobs_images, dim3(2 * RED_SPLIT + cdiv(im.nhalo + pk.nsend, 1024)), dim3(1024), 0, ctx->stream, jf, jk, ctx->d_results, ctx->self_ele, ctx->red_tmp.p, im, pk);
+         (p.red == RED_IMAGES ? ctx->images_fresh : ctx->pack_fresh) = true;
       }
-      /* (the launch kept the plain kernel: LDS layout; the kick follows as usual) */
-      if ((rc = launch_kinetic(ctx, dt, 1, true, &lam, true))) return rc;
-      ctx->drift_done = true;
       return DDCMI_OK;
    }
    if ((rc = launch_forces(ctx, true))) return rc;
@@ -685,12 +711,8 @@ static int step_post(ddcmi_ctx *ctx, double dt, bool more_steps)
       return step_post_cons_b(ctx, dt);
    }
    if (more_steps && ctx->nloc > 0 && !(ctx->baro_beta > 0.0))      /* the barostat needs this step's virial before the next drift */
-   {
-      if ((rc = launch_kinetic(ctx, dt, 1, true, &lam, true))) return rc;
-      ctx->drift_done = true;
-   }
-   else if ((rc = launch_kinetic(ctx, dt, 1, true, &lam, false))) return rc;
-   return DDCMI_OK;
+      return kick_ke_then_drift(ctx, dt, lam);
+   return launch_kinetic(ctx, dt, 1, true, &lam, false);
 }
 
 /* updateRate == 0: does this domain's list need a rebuild?  (neighborCheck; one host

@@ -11,10 +11,12 @@
 
 /* ---- predicates -------------------------------------------------------------- */
 static inline bool mg_transport(const ddcmi_ctx *ctx) { return ctx->comm != nullptr || ctx->hcomm != nullptr; }
+/* this context's halo holds beads of other domains (loopback: a single rank whose periodic images count as such), whoever moves them */
+static inline bool has_peers(const ddcmi_ctx *ctx) { return ctx->nranks > 1 || ctx->loopback; }
 /* several domains, whoever moves the data */
-static inline bool decomposed(const ddcmi_ctx *ctx) { return ctx->nranks > 1 || ctx->loopback || ctx->group_ != nullptr; }
+static inline bool decomposed(const ddcmi_ctx *ctx) { return has_peers(ctx) || ctx->group_ != nullptr; }
 /* this context exchanges through its transport (loopback: a single rank whose periodic images travel through it) */
-static inline bool exchanging(const ddcmi_ctx *ctx) { return (ctx->nranks > 1 || ctx->loopback) && mg_transport(ctx); }
+static inline bool exchanging(const ddcmi_ctx *ctx) { return has_peers(ctx) && mg_transport(ctx); }
 /* what ddcmi_comm_stats reports: 0 none, 1 RCCL, 2 host rendezvous, 3 RCCL loopback */
 static inline int transport_kind(const ddcmi_ctx *ctx) { return ctx->comm ? (ctx->loopback ? 3 : 1) : ctx->hcomm ? 2 : 0; }
 

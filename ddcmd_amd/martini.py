@@ -590,6 +590,18 @@ class MartiniHIP(object):
         self._chk(self.lib.ddcmi_debug_lean_history(self.ctx, ctypes.byref(nst), _d(out)))
         return out[:nst.value].copy()
 
+    STEP_PLAN_FIELDS = ("halo", "fused", "lean", "level_table", "fixed_layout", "reduction", "halo_disp", "direct")
+
+    def step_plan(self, back=0):
+        """(test_api) the plan of the force evaluation `back` evaluations before the last one this context ran, as a dict of small
+        integers -- include/ddcmi_test.h, ddcmi_debug_step_plan: halo 0 none, 1 images at their owners, 2 exchange + update launch, 3 direct
+        from the receive buffer, 4 second stream, 5 update launch alone; reduction 0 none, 1 alone, 2 with the images, 3 with the next
+        exchange's messages"""
+        out = (ctypes.c_int * 8)(int(back))
+        self.lib.ddcmi_debug_step_plan.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
+        self._chk(self.lib.ddcmi_debug_step_plan(self.ctx, out))
+        return dict(zip(self.STEP_PLAN_FIELDS, list(out)))
+
     def kinetic(self):
         t = np.zeros(6)
         rk = ctypes.c_double(0)

@@ -6,6 +6,7 @@
  *   ddcmi_plan_*               the host logic of the halo exchange / domain directions, callable without a GPU (world-2 CPU tests)
  *   ddcmi_debug_branch_census  which rarely taken dihedral branches a test's geometry drives
  *   ddcmi_debug_bonded_layout  what the bonded kernels' lane layout decided for a test's term lists
+ *   ddcmi_debug_step_plan      which path a context's force evaluations took (halo mode, fused, lean, LDS layout, reduction launch)
  *   ddcmi_debug_tile_items     the work items the pair kernel was launched with (tiles, row parts) and the owned beads of their tiles
  *   ddcmi_debug_wave_reduce    the transposed wave reduction of several sums against the one-sum reduction, on the test's own numbers
  *   ddcmi_debug_recip          the four reciprocal routines and the two bare double-precision seeds, on the test's own numbers
@@ -101,6 +102,16 @@ int ddcmi_debug_thermalize_rejects(ddcmi_ctx *ctx, int select, int ntemp, const 
  * {lj, ele, virial xx yy zz xy xz yz} as the full list counts them (twice), {rk, tion xx yy zz xy xz yz}, 0, the bonded kernels'
  * {e_bond, e_angle, e_tors, e_impr, virial xx yy zz xy xz yz}, zeros.  Forms what is pending first.  sums: room for 32 steps. */
 int ddcmi_debug_lean_history(ddcmi_ctx *ctx, int *nsteps, double *sums);
+/* the plan of a force evaluation the context ran (one per ddcmi_eval_forces and per step).  out[0] on entry: which one, counted back from
+ * the last (0; at most 15, and no more than the context has run: else DDCMI_EINVAL) -- only the last step of a ddcmi_step_nglf call knows
+ * that no step follows and never fuses, so the steps that show the steady path lie behind it.  On return:
+ * [0] how the halo reached the pair kernel: 0 nothing to refresh, 1 periodic images staged from their owners, 2 exchange + update launch,
+ * 3 exchange alone, received beads staged from the receive buffer, 4 exchange + update launch on the second stream, 5 update launch alone
+ * (a single domain's images; a domain of an in-process group, whose driver exchanged); [1] the integrator's pass rode in the pair kernel;
+ * [2] the step was lean; [3] pair table in two levels; [4] fixed LDS layout ([3] [4]: 0 where no pair kernel ran); [5] the reduction launch
+ * behind a fused launch that was not lean: 1 alone, 2 with the periodic images, 3 with the next exchange's messages (0: none of these);
+ * [6] the update launch measured the received beads' displacement; [7] received beads are read from the receive buffer.  Host numbers. */
+int ddcmi_debug_step_plan(ddcmi_ctx *ctx, int out[8]);
 /* the displacement bound of the shell-limited walk: the word the reduction launches add to, and the lean steps' words since the rebuild (largest |v|^2 of each; ring[32]) */
 int ddcmi_debug_disp(ddcmi_ctx *ctx, double *disp, float *ring, int *nring);
 /* census of the pair kernel's work items after a list build, in launch order: item[q] = tile | part << 24 | (nparts - 1) << 27 as k_nonbond reads it
