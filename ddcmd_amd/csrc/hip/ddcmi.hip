@@ -596,8 +596,8 @@ __global__ void k_merge_cells(int ncell, int nloc, const int *cnt_o, const int *
 
 #include "ddcmi_transport.inl"
 #include "ddcmi_listbuild.inl"
-#include "ddcmi_nonbond.inl"
 #include "ddcmi_integrator.inl"
+#include "ddcmi_nonbond.inl"
 /* ------------------------------------------------------------------------- */
 /* context                                                                    */
 extern "C" const char *ddcmi_version(void) { return "ddcmi 0.1 (gfx950)"; }

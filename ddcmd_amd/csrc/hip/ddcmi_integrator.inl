@@ -250,6 +250,55 @@ __device__ __forceinline__ void kind_update(const GroupLambda &gl, int gr, doubl
    }
    else if (gl.fixset_mask >> gr & 1u) { x = gl.vw[gr][0]; y = gl.vw[gr][1]; z = gl.vw[gr][2]; }
 }
+/* The per-bead arithmetic of a step, ONE copy each: the split kernels below and the pair kernel's fused epilogue (ddcmi_nonbond.inl) all call
+ * these, so whichever path the StepPlan takes forms the same bits.  The fma calls are explicit: under -ffp-contract=fast nothing else fixes
+ * which product joins which sum. */
+/* the update of a bead under no thermostat, or under Berendsen's: lam scales the velocity in front of the FRONT kick only (berendsen.c:74-80) */
+template <bool BACK>
+__device__ __forceinline__ void plain_update(double a, double lam, double f0, double f1, double f2, double &x, double &y, double &z)
+{
+   if (!BACK && lam != 1.0) { x *= lam; y *= lam; z *= lam; }
+   x = fma(a, f0, x); y = fma(a, f1, y); z = fma(a, f2, z);
+}
+/* d of the Langevin update for a bead of group gr (0 in any other group): a kernel that does both updates of a bead forms it once */
+__device__ __forceinline__ double noise_amplitude(const GroupLambda &gl, int gr, double im)
+{
+   return (gl.lang_mask >> gr & 1u) ? gl.dfac[gr] * sqrt(im) : 0.0;
+}
+/* velocityUpdate of bead i (group gr, a = (dt/2)/m, d = noise_amplitude) whatever its group's kind; BACK picks the Langevin form and the noise counter */
+template <bool BACK>
+__device__ __forceinline__ void vel_update(const GroupLambda &gl, int gr, double a, double d, int i, const uint64_t *gid,
+                                           double f0, double f1, double f2, double &x, double &y, double &z)
+{
+   if (gl.kind_mask >> gr & 1u) kind_update(gl, gr, a, f0, f1, f2, x, y, z);
+   else if (gl.lang_mask >> gr & 1u)
+   {
+      double g0, g1, g2, al = gl.a[gr];
+      group_gauss3(gl, i, gid, BACK ? gl.counter_back : gl.counter_front, g0, g1, g2);
+      if (BACK) { x = al * fma(d, g0, fma(a, f0, x)); y = al * fma(d, g1, fma(a, f1, y)); z = al * fma(d, g2, fma(a, f2, z)); }
+      else { x = fma(d, g0, fma(a, f0, al * x)); y = fma(d, g1, fma(a, f1, al * y)); z = fma(d, g2, fma(a, f2, al * z)); }
+      if (gl.vcm_mask >> gr & 1u) { x += gl.vw[gr][0]; y += gl.vw[gr][1]; z += gl.vw[gr][2]; }
+   }
+   else plain_update<BACK>(a, gl.v[gr], f0, f1, f2, x, y, z);
+}
+/* kinetic_terms of one bead (energy.c:48-163): t = {1/2 m v^2, m vx^2, m vy^2, m vz^2, m vx vy, m vx vz, m vy vz}.  Assigned, not added: the
+ * epilogue keeps the terms as they are (0 + (-0.0) is not -0.0), the other callers add them to their sums */
+__device__ __forceinline__ void kinetic_terms7(double m, double x, double y, double z, double (&t)[7])
+{
+   const double vxx = x * x, vyy = y * y, vzz = z * z;
+   t[0] = 0.5 * m * (vxx + vyy + vzz);
+   t[1] = m * vxx; t[2] = m * vyy; t[3] = m * vzz;
+   t[4] = m * (x * y); t[5] = m * (x * z); t[6] = m * (y * z);
+}
+/* the drift (nglf.c:80-87) behind the barostat's scaling of the position (adjustPosn; NO_SCALE where there is none): a frozen bead takes zero
+ * velocity.  Returns |v|^2 of the velocity the bead drifts with, rounded up: its share of the displacement bound (NbTileArgs::disp) */
+static constexpr double NO_SCALE[3] = {1.0, 1.0, 1.0};
+__device__ __forceinline__ float drift_bead(const double (&scale)[3], bool frozen, double dt, double x, double y, double z, double4 &p)
+{
+   if (frozen) { p.x = scale[0] * p.x; p.y = scale[1] * p.y; p.z = scale[2] * p.z; return 0.0f; }      /* (a bead that stays has no share in the bound) */
+   p.x = fma(dt, x, scale[0] * p.x); p.y = fma(dt, y, scale[1] * p.y); p.z = fma(dt, z, scale[2] * p.z);
+   return __double2float_ru(x * x + y * y + z * z);
+}
 /* the largest |v|^2 of a workgroup's drifting beads, rounded up, into column 7 of its row of partials: the displacement bound of the
  * shell-limited walk (NbTileArgs::disp) adds dt * sqrt(max over the rows) per step (k_reduce_jobs) */
 template <int NW>
@@ -267,60 +316,38 @@ __device__ __forceinline__ void block_vmax_store(float v2, double *row)
       row[7] = (double)__int_as_float(t);
    }
 }
+/* k_kick_drift's three jobs.  nglfconstraint splits the pass around the FRONT constraint solve: SCALE_KICK = barostat scaling of the positions
+ * (adjustPosn) + kick, DRIFT_ONLY = drift with the constrained velocities; KICK_DRIFT is the plain step's kick + scaling + drift */
+enum KickDrift { SCALE_KICK, DRIFT_ONLY, KICK_DRIFT };
+template <KickDrift MODE>
 __global__ void k_kick_drift(int nloc, double dt, const double *__restrict__ invmass, const int *__restrict__ species,
                              const int *__restrict__ group, GroupLambda glambda, const uint64_t *__restrict__ gid,
                              const double *__restrict__ fx, const double *__restrict__ fy, const double *__restrict__ fz,
-                             double *__restrict__ vx, double *__restrict__ vy, double *__restrict__ vz, double4 *__restrict__ pos, int mode,
-                             double *__restrict__ vpart /* mode 3, not null: [block][8], column 7 = the block's largest |v|^2 of the drift */)
+                             double *__restrict__ vx, double *__restrict__ vy, double *__restrict__ vz, double4 *__restrict__ pos,
+                             double *__restrict__ vpart /* KICK_DRIFT, not null: [block][8], column 7 = the block's largest |v|^2 of the drift */)
 {
    const int i = blockIdx.x * blockDim.x + threadIdx.x;
    float v2 = 0.0f;
    if (i < nloc)
    {
-      bool done = false;
       const int gr = group[i] & 31;
-      const bool frozen = glambda.frozen_mask >> gr & 1u;      /* drifts with zero velocity, whatever it stores */
-      if (mode != 3)
-      {
-         /* nglfconstraint splits the pass around the FRONT constraint solve: mode 1 = barostat scaling of the
-          * positions (adjustPosn) + kick, mode 2 = drift with the constrained velocities */
-         double4 p = pos[i];
-         if (mode == 2) { if (!frozen) { p.x = fma(dt, vx[i], p.x); p.y = fma(dt, vy[i], p.y); p.z = fma(dt, vz[i], p.z); pos[i] = p; } done = true; }
-         else if (glambda.scale[0] != 1.0 || glambda.scale[1] != 1.0 || glambda.scale[2] != 1.0)
-         { p.x *= glambda.scale[0]; p.y *= glambda.scale[1]; p.z *= glambda.scale[2]; pos[i] = p; }
-      }
-      if (!done)
+      double x = vx[i], y = vy[i], z = vz[i];
+      double4 p = pos[i];
+      if (MODE == SCALE_KICK && (glambda.scale[0] != 1.0 || glambda.scale[1] != 1.0 || glambda.scale[2] != 1.0))
+      { p.x *= glambda.scale[0]; p.y *= glambda.scale[1]; p.z *= glambda.scale[2]; pos[i] = p; }
+      if (MODE != DRIFT_ONLY)
       {
          const double im = invmass[species[i]];
-         double a = (0.5 * dt) * im;
-         double lam = glambda.v[gr];
-         double x = vx[i], y = vy[i], z = vz[i];
-         if (glambda.kind_mask >> gr & 1u) kind_update(glambda, gr, a, fx[i], fy[i], fz[i], x, y, z);
-         else if (glambda.lang_mask >> gr & 1u)
-         {
-            double g0, g1, g2, d = glambda.dfac[gr] * sqrt(im), al = glambda.a[gr];
-            group_gauss3(glambda, i, gid, glambda.counter_front, g0, g1, g2);
-            x = fma(d, g0, fma(a, fx[i], al * x)); y = fma(d, g1, fma(a, fy[i], al * y)); z = fma(d, g2, fma(a, fz[i], al * z));
-            if (glambda.vcm_mask >> gr & 1u) { x += glambda.vw[gr][0]; y += glambda.vw[gr][1]; z += glambda.vw[gr][2]; }
-         }
-         else
-         {
-            if (lam != 1.0) { x *= lam; y *= lam; z *= lam; }
-            /* explicit fma: k_kick_ke_drift must produce the same bits as this kernel */
-            x = fma(a, fx[i], x); y = fma(a, fy[i], y); z = fma(a, fz[i], z);
-         }
+         vel_update<false>(glambda, gr, (0.5 * dt) * im, noise_amplitude(glambda, gr, im), i, gid, fx[i], fy[i], fz[i], x, y, z);
          vx[i] = x; vy[i] = y; vz[i] = z;
-         if (mode == 3)
-         {
-            double4 p = pos[i];
-            if (frozen) { p.x = glambda.scale[0] * p.x; p.y = glambda.scale[1] * p.y; p.z = glambda.scale[2] * p.z; }
-            else { p.x = fma(dt, x, glambda.scale[0] * p.x); p.y = fma(dt, y, glambda.scale[1] * p.y); p.z = fma(dt, z, glambda.scale[2] * p.z); }
-            pos[i] = p;
-            v2 = frozen ? 0.0f : __double2float_ru(x * x + y * y + z * z);      /* (a bead that stays has no share in the displacement bound) */
-         }
+      }
+      if (MODE != SCALE_KICK)
+      {
+         v2 = drift_bead(MODE == DRIFT_ONLY ? NO_SCALE : glambda.scale, glambda.frozen_mask >> gr & 1u, dt, x, y, z, p);
+         pos[i] = p;
       }
    }
-   if (vpart) block_vmax_store<4>(v2, vpart + (size_t)blockIdx.x * 8);      /* (uniform: every thread of the block gets here) */
+   if (MODE == KICK_DRIFT && vpart) block_vmax_store<4>(v2, vpart + (size_t)blockIdx.x * 8);      /* (uniform: every thread of the block gets here) */
 }
 __global__ void k_scale_pos(int n, double s0, double s1, double s2, double4 *pos)
 {
@@ -348,34 +375,23 @@ __global__ __launch_bounds__(DDCMI_BLOCK) void k_kick_ke(int nloc, double dt, co
       int i = (blockIdx.x * KE_PER + u) * DDCMI_BLOCK + threadIdx.x;
       if (i >= nloc) continue;
       int sp = species[i];
-      double x = vx[i], y = vy[i], z = vz[i];
+      double x = vx[i], y = vy[i], z = vz[i], t[7];
       if (do_kick)
       {
          const double im = invmass[sp];
-         double a = (0.5 * dt) * im;
          const int gr = group[i] & 31;
-         if (glambda.kind_mask >> gr & 1u) kind_update(glambda, gr, a, fx[i], fy[i], fz[i], x, y, z);
-         else if (glambda.lang_mask >> gr & 1u)
-         {
-            double g0, g1, g2, d = glambda.dfac[gr] * sqrt(im), al = glambda.a[gr];
-            group_gauss3(glambda, i, gid, glambda.counter_back, g0, g1, g2);
-            x = al * fma(d, g0, fma(a, fx[i], x)); y = al * fma(d, g1, fma(a, fy[i], y)); z = al * fma(d, g2, fma(a, fz[i], z));
-            if (glambda.vcm_mask >> gr & 1u) { x += glambda.vw[gr][0]; y += glambda.vw[gr][1]; z += glambda.vw[gr][2]; }
-         }
-         else { x = fma(a, fx[i], x); y = fma(a, fy[i], y); z = fma(a, fz[i], z); }
+         vel_update<true>(glambda, gr, (0.5 * dt) * im, noise_amplitude(glambda, gr, im), i, gid, fx[i], fy[i], fz[i], x, y, z);
          vx[i] = x; vy[i] = y; vz[i] = z;
       }
-      double m = massv[sp];
-      double vxx = x * x, vyy = y * y, vzz = z * z;
-      acc[0] += 0.5 * m * (vxx + vyy + vzz);
-      acc[1] += m * vxx; acc[2] += m * vyy; acc[3] += m * vzz;
-      acc[4] += m * (x * y); acc[5] += m * (x * z); acc[6] += m * (y * z);
+      kinetic_terms7(massv[sp], x, y, z, t);
+#pragma unroll
+      for (int k = 0; k < 7; k++) acc[k] += t[k];
    }
    block_reduce_store<7>(acc, partials + (size_t)blockIdx.x * 8);
 }
 /* The BACK half kick + kinetic terms of step n and the FRONT half kick + drift of step
  * n+1 use the same forces: inside a batch of steps they are one pass over v and f
- * (k_kick_ke followed by k_kick_drift, bit for bit). */
+ * (k_kick_ke followed by k_kick_drift<KICK_DRIFT>: the same per-bead functions in the same order). */
 __global__ __launch_bounds__(DDCMI_BLOCK) void k_kick_ke_drift(int nloc, double dt, const double *__restrict__ invmass, const double *__restrict__ massv,
                                                                const int *__restrict__ species, const int *__restrict__ group, GroupLambda glambda,
                                                                const double *__restrict__ fx, const double *__restrict__ fy, const double *__restrict__ fz,
@@ -390,45 +406,18 @@ __global__ __launch_bounds__(DDCMI_BLOCK) void k_kick_ke_drift(int nloc, double 
       int i = (blockIdx.x * KE_PER + u) * DDCMI_BLOCK + threadIdx.x;
       if (i >= nloc) continue;
       int sp = species[i];
-      const double im = invmass[sp];
-      double a = (0.5 * dt) * im;
-      double f0 = fx[i], f1 = fy[i], f2 = fz[i];
+      const double im = invmass[sp], a = (0.5 * dt) * im, f0 = fx[i], f1 = fy[i], f2 = fz[i];
       const int gr = group[i] & 31;
-      const bool lang = glambda.lang_mask >> gr & 1u;
-      const bool kind = glambda.kind_mask >> gr & 1u, frozen = glambda.frozen_mask >> gr & 1u;
-      double x, y, z, g0, g1, g2, dl = 0.0, al = 0.0;
-      if (kind) { x = vx[i]; y = vy[i]; z = vz[i]; kind_update(glambda, gr, a, f0, f1, f2, x, y, z); }
-      else if (lang)
-      {
-         dl = glambda.dfac[gr] * sqrt(im); al = glambda.a[gr];
-         group_gauss3(glambda, i, gid, glambda.counter_back, g0, g1, g2);
-         x = al * fma(dl, g0, fma(a, f0, vx[i])); y = al * fma(dl, g1, fma(a, f1, vy[i])); z = al * fma(dl, g2, fma(a, f2, vz[i]));
-         if (glambda.vcm_mask >> gr & 1u) { x += glambda.vw[gr][0]; y += glambda.vw[gr][1]; z += glambda.vw[gr][2]; }
-      }
-      else { x = fma(a, f0, vx[i]); y = fma(a, f1, vy[i]); z = fma(a, f2, vz[i]); }
-      double m = massv[sp];
-      double vxx = x * x, vyy = y * y, vzz = z * z;
-      acc[0] += 0.5 * m * (vxx + vyy + vzz);
-      acc[1] += m * vxx; acc[2] += m * vyy; acc[3] += m * vzz;
-      acc[4] += m * (x * y); acc[5] += m * (x * z); acc[6] += m * (y * z);
-      if (kind) kind_update(glambda, gr, a, f0, f1, f2, x, y, z);      /* (the FRONT update sees the same force: QUENCH applies its zeroing rule a second time) */
-      else if (lang)
-      {
-         group_gauss3(glambda, i, gid, glambda.counter_front, g0, g1, g2);
-         x = fma(dl, g0, fma(a, f0, al * x)); y = fma(dl, g1, fma(a, f1, al * y)); z = fma(dl, g2, fma(a, f2, al * z));
-         if (glambda.vcm_mask >> gr & 1u) { x += glambda.vw[gr][0]; y += glambda.vw[gr][1]; z += glambda.vw[gr][2]; }
-      }
-      else
-      {
-         double lam = glambda.v[gr];
-         if (lam != 1.0) { x *= lam; y *= lam; z *= lam; }
-         x = fma(a, f0, x); y = fma(a, f1, y); z = fma(a, f2, z);
-      }
+      const double d = noise_amplitude(glambda, gr, im);
+      double x = vx[i], y = vy[i], z = vz[i], t[7];
+      vel_update<true>(glambda, gr, a, d, i, gid, f0, f1, f2, x, y, z);
+      kinetic_terms7(massv[sp], x, y, z, t);
+#pragma unroll
+      for (int k = 0; k < 7; k++) acc[k] += t[k];
+      vel_update<false>(glambda, gr, a, d, i, gid, f0, f1, f2, x, y, z);      /* (the FRONT update sees the same force: QUENCH applies its zeroing rule a second time) */
       vx[i] = x; vy[i] = y; vz[i] = z;
-      if (!frozen) v2 = fmaxf(v2, __double2float_ru(x * x + y * y + z * z));
       double4 p = pos[i];
-      if (frozen) { p.x = glambda.scale[0] * p.x; p.y = glambda.scale[1] * p.y; p.z = glambda.scale[2] * p.z; }
-      else { p.x = fma(dt, x, glambda.scale[0] * p.x); p.y = fma(dt, y, glambda.scale[1] * p.y); p.z = fma(dt, z, glambda.scale[2] * p.z); }
+      v2 = fmaxf(v2, drift_bead(glambda.scale, glambda.frozen_mask >> gr & 1u, dt, x, y, z, p));
       pos[i] = p;
    }
    block_reduce_store<7>(acc, partials + (size_t)blockIdx.x * 8);
@@ -520,12 +509,12 @@ __global__ __launch_bounds__(DDCMI_BLOCK) void k_class_kinetic(int nloc, int ncl
          const int sp = species[i];
          if ((by_species ? sp : group[i]) != c) continue;
          const double m = massv[sp], x = vx[i], y = vy[i], z = vz[i];
-         const double K = 0.5 * m * (x * x + y * y + z * z);
-         acc[0] += K;
-         acc[1] += m * (x * x); acc[2] += m * (y * y); acc[3] += m * (z * z);
-         acc[4] += m * (x * y); acc[5] += m * (x * z); acc[6] += m * (y * z);
+         double t[7];
+         kinetic_terms7(m, x, y, z, t);
+#pragma unroll
+         for (int k = 0; k < 7; k++) acc[k] += t[k];
          acc[7] += m; acc[8] += 1.0;
-         acc[9] += K * x; acc[10] += K * y; acc[11] += K * z;
+         acc[9] += t[0] * x; acc[10] += t[0] * y; acc[11] += t[0] * z;
       }
       block_reduce_store<KD_NV>(acc, partials + ((size_t)blockIdx.x * nclass + c) * 16);
       __syncthreads();      /* the reduction's scratch is reused by the next class */

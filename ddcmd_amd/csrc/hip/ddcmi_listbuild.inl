@@ -109,7 +109,7 @@ struct NbTileArgs
    double4 *fb;
 };
 /* k_nonbond<..., FUSE>: the pair kernel's epilogue is the integrator's pass over the bead -- BACK half kick, kinetic terms, FRONT half
- * kick, drift (k_kick_ke_drift, bit for bit) -- for systems whose forces are complete when the list walk ends (no bonded terms,
+ * kick, drift (the per-bead functions of k_kick_ke_drift, ddcmi_integrator.inl) -- for systems whose forces are complete when the list walk ends (no bonded terms,
  * restraints, constraints or barostat; FREE / BERENDSEN groups).  The force never goes to memory; the drifted positions go to the
  * second position buffer (the neighbours still read the old one), which the host swaps in after the launch. */
 struct FuseArgs

@@ -540,7 +540,8 @@ __global__ __launch_bounds__(NB_BLOCK, WPE) void k_nonbond(GridParams gp, NbTile
          }
          else
          {
-            /* k_kick_ke_drift on the bead, with the force still in registers (the same operations in the same order) */
+            /* k_kick_ke_drift on the bead, with the force still in registers: its per-bead functions (ddcmi_integrator.inl), of vel_update the plain arm
+             * alone -- fuse_ok admits FREE / BERENDSEN groups with one factor, fa.lam -- and a drift without scaling or frozen beads */
             double ke[7] = {0, 0, 0, 0, 0, 0, 0};
             float v2max = 0.0f;      /* |v|^2 of the velocity the bead drifts with, rounded up: feeds the displacement bound D (NbTileArgs::disp) */
             if (active && sub == 0)
@@ -555,18 +556,14 @@ __global__ __launch_bounds__(NB_BLOCK, WPE) void k_nonbond(GridParams gp, NbTile
                   fxi += b.x; fyi += b.y; fzi += b.z;
                   ta.fb[a] = make_double4(0.0, 0.0, 0.0, 0.0);
                }
-               double x = fma(hk, fxi, fa.vx[a]), y = fma(hk, fyi, fa.vy[a]), z = fma(hk, fzi, fa.vz[a]);
-               const double vxx = x * x, vyy = y * y, vzz = z * z;
-               ke[0] = 0.5 * m * (vxx + vyy + vzz);
-               ke[1] = m * vxx; ke[2] = m * vyy; ke[3] = m * vzz;
-               ke[4] = m * (x * y); ke[5] = m * (x * z); ke[6] = m * (y * z);
-               if (lam != 1.0) { x *= lam; y *= lam; z *= lam; }
-               x = fma(hk, fxi, x); y = fma(hk, fyi, y); z = fma(hk, fzi, z);
+               double x = fa.vx[a], y = fa.vy[a], z = fa.vz[a];
+               plain_update<true>(hk, lam, fxi, fyi, fzi, x, y, z);
+               kinetic_terms7(m, x, y, z, ke);
+               plain_update<false>(hk, lam, fxi, fyi, fzi, x, y, z);
                fa.vx[a] = x; fa.vy[a] = y; fa.vz[a] = z;
-               v2max = __double2float_ru(x * x + y * y + z * z);
                double4 p = pi;
                if (!SHBIT) p.z = zexact;
-               p.x = fma(fa.dt, x, p.x); p.y = fma(fa.dt, y, p.y); p.z = fma(fa.dt, z, p.z);
+               v2max = drift_bead(NO_SCALE, false, fa.dt, x, y, z, p);
                fa.pos_new[a] = p;
             }
             /* the wave's row of kinetic sums (only this wave touches it; the rows are added in index order at the end) */

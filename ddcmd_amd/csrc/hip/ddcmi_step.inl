@@ -403,24 +403,41 @@ extern "C" int ddcmi_eval_forces(ddcmi_ctx *ctx, double *energies, double *viria
    return DDCMI_OK;
 }
 
+/* the velocity updates' per-group data of a step that has no thermostat, no noise (the counter-based stream, seed 0), no kinds and no scaling;
+ * front_lambda starts from it */
+static GroupLambda identity_lambda()
+{
+   GroupLambda lam;
+   memset(&lam, 0, sizeof(lam));
+   for (int g = 0; g < 32; g++) lam.v[g] = lam.a[g] = 1.0;
+   lam.scale[0] = lam.scale[1] = lam.scale[2] = 1.0;
+   return lam;
+}
+/* BACK half kick (do_kick) + the workgroups' kinetic terms into kpartials */
+static int launch_kick_ke(ddcmi_ctx *ctx, double dt, int do_kick, const GroupLambda &lam)
+{
+   const int nblk = cdiv(ctx->nloc, DDCMI_BLOCK * KE_PER);
+   ENSURE(ctx, ctx->kpartials, (size_t)(nblk + 8) * 8);
+   hipLaunchKernelGGL(k_kick_ke, dim3(std::max(nblk, 1)), dim3(DDCMI_BLOCK), 0, ctx->stream, ctx->nloc, dt, ctx->d_invmass.p, ctx->d_mass.p, ctx->species.p,
+                      ctx->fx.p, ctx->fy.p, ctx->fz.p, ctx->vx.p, ctx->vy.p, ctx->vz.p, ctx->kpartials.p, do_kick, ctx->group.p, lam, ctx->gid.p);
+   return DDCMI_OK;
+}
 /* kinetic_terms (+ the BACK half kick); with_forces: the same launch also reduces the
  * nonbonded partials of the force evaluation just queued and forms the final energies */
 static int launch_kinetic(ddcmi_ctx *ctx, double dt, int do_kick, bool with_forces = false, const GroupLambda *gk = nullptr, bool then_drift = false)
 {
    RoctxRange rng_ke("KINETIC_TERMS");      /* energy.c:48-163 */
    GroupLambda plain;
-   if (!gk) { memset(&plain, 0, sizeof(plain)); for (int g = 0; g < 32; g++) { plain.v[g] = 1.0; plain.a[g] = 1.0; } plain.scale[0] = plain.scale[1] = plain.scale[2] = 1.0; gk = &plain; }
-   int n = ctx->nloc, nblk = cdiv(n, DDCMI_BLOCK * KE_PER);
-   ENSURE(ctx, ctx->kpartials, (size_t)(nblk + 8) * 8);
+   if (!gk) { plain = identity_lambda(); gk = &plain; }
+   int rc, n = ctx->nloc, nblk = cdiv(n, DDCMI_BLOCK * KE_PER);
    if (then_drift)
    {
+      ENSURE(ctx, ctx->kpartials, (size_t)(nblk + 8) * 8);
       if (gk->scale[0] != 1.0 || gk->scale[1] != 1.0 || gk->scale[2] != 1.0) ctx->shell_skip = false;      /* (scaled positions: not a plain drift) */
       hipLaunchKernelGGL(k_kick_ke_drift, dim3(std::max(nblk, 1)), dim3(DDCMI_BLOCK), 0, ctx->stream, n, dt, ctx->d_invmass.p, ctx->d_mass.p, ctx->species.p, ctx->group.p, *gk,
                          ctx->fx.p, ctx->fy.p, ctx->fz.p, ctx->vx.p, ctx->vy.p, ctx->vz.p, ctx->pos.p, ctx->kpartials.p, ctx->gid.p);
    }
-   else
-   hipLaunchKernelGGL(k_kick_ke, dim3(std::max(nblk, 1)), dim3(DDCMI_BLOCK), 0, ctx->stream, n, dt, ctx->d_invmass.p, ctx->d_mass.p, ctx->species.p,
-                      ctx->fx.p, ctx->fy.p, ctx->fz.p, ctx->vx.p, ctx->vy.p, ctx->vz.p, ctx->kpartials.p, do_kick, ctx->group.p, *gk, ctx->gid.p);
+   else if ((rc = launch_kick_ke(ctx, dt, do_kick, *gk))) return rc;
    RedJob jk = {ctx->kpartials.p, nblk, 7, ctx->d_results + R_RK, 0, then_drift ? dt : 0.0, ctx->d_results + R_DISP};      /* (+ the drift's share of the displacement bound) */
    if (with_forces)
    {
@@ -454,11 +471,9 @@ static void berendsen_update(ddcmi_ctx *ctx, double dt_half)
 /* nglf.c:74-95: FRONT half kick + drift, clock advance */
 static GroupLambda front_lambda(const ddcmi_ctx *ctx, double dt)
 {
-   GroupLambda lam;
-   lam.lang_mask = 0; lam.seed = ctx->rng_seed; lam.vcm_mask = 0;
-   lam.kind_mask = lam.frozen_mask = lam.fixset_mask = lam.quench_mask = 0;
+   GroupLambda lam = identity_lambda();
+   lam.seed = ctx->rng_seed;
    lam.lcg = ctx->lcg_on ? ctx->lcg.p : nullptr;
-   lam.scale[0] = lam.scale[1] = lam.scale[2] = 1.0;
    /* the FRONT update of a step sees the loop count before its increment, the BACK update the one after */
    lam.counter_front = 2ull * (unsigned long long)ctx->loop;
    lam.counter_back = 2ull * (unsigned long long)ctx->loop + 1ull;
@@ -466,9 +481,7 @@ static GroupLambda front_lambda(const ddcmi_ctx *ctx, double dt)
    for (int g = 0; g < 32; g++)
    {
       /* lambda applies at the FRONT kick when doScaling is set (berendsen.c:74-80) */
-      lam.v[g] = (g < ctx->ngroup && ctx->gtype[g] == DDCMI_BERENDSEN && ctx->gdoScaling[g]) ? ctx->glambda[g] : 1.0;
-      lam.a[g] = 1.0; lam.dfac[g] = 0.0;
-      lam.vw[g][0] = lam.vw[g][1] = lam.vw[g][2] = 0.0;
+      if (g < ctx->ngroup && ctx->gtype[g] == DDCMI_BERENDSEN && ctx->gdoScaling[g]) lam.v[g] = ctx->glambda[g];
       const int kind = g < ctx->ngroup ? ctx->gtype[g] : DDCMI_FREE;
       if (kind == DDCMI_FROZEN || kind == DDCMI_FIXEDVELOCITY || kind == DDCMI_QUENCH) lam.kind_mask |= 1u << g;
       if (kind == DDCMI_FROZEN) lam.frozen_mask |= 1u << g;
@@ -515,6 +528,13 @@ static int step_pre_a(ddcmi_ctx *ctx)
    ctx->baro_sums[6] = (double)ctx->nloc;
    return DDCMI_OK;
 }
+/* k_kick_drift's one call site */
+static void launch_kick_drift(ddcmi_ctx *ctx, double dt, const GroupLambda &lam, KickDrift mode, double *vpart = nullptr)
+{
+   const auto k = mode == SCALE_KICK ? k_kick_drift<SCALE_KICK> : mode == DRIFT_ONLY ? k_kick_drift<DRIFT_ONLY> : k_kick_drift<KICK_DRIFT>;
+   hipLaunchKernelGGL(k, dim3(cdiv(ctx->nloc, 256)), dim3(256), 0, ctx->stream, ctx->nloc, dt, ctx->d_invmass.p, ctx->species.p, ctx->group.p, lam, ctx->gid.p,
+                      ctx->fx.p, ctx->fy.p, ctx->fz.p, ctx->vx.p, ctx->vy.p, ctx->vz.p, ctx->pos.p, vpart);
+}
 static int step_pre_b(ddcmi_ctx *ctx, double dt)
 {
    int n = ctx->nloc, nb = cdiv(n, 256);
@@ -555,14 +575,12 @@ static int step_pre_b(ddcmi_ctx *ctx, double dt)
    if (ctx->ncgroup > 0 || lam.scale[0] != 1.0 || lam.scale[1] != 1.0 || lam.scale[2] != 1.0) ctx->shell_skip = false;
    if (n > 0 && ctx->ncgroup > 0)
       /* nglfconstraint.c:538-553: FRONT kick, velocityConstraintOld(FRONT) at the (scaled) positions, drift */
-      hipLaunchKernelGGL(k_kick_drift, dim3(nb), dim3(256), 0, ctx->stream, n, dt, ctx->d_invmass.p, ctx->species.p, ctx->group.p, lam, ctx->gid.p,
-                         ctx->fx.p, ctx->fy.p, ctx->fz.p, ctx->vx.p, ctx->vy.p, ctx->vz.p, ctx->pos.p, 1, (double *)nullptr);
+      launch_kick_drift(ctx, dt, lam, SCALE_KICK);
    else if (n > 0)
    {
       double *vpart = nullptr;
       if (ctx->shell_skip) { ENSURE(ctx, ctx->kpartials, (size_t)(nb + 8) * 8); vpart = ctx->kpartials.p; }
-      hipLaunchKernelGGL(k_kick_drift, dim3(nb), dim3(256), 0, ctx->stream, n, dt, ctx->d_invmass.p, ctx->species.p, ctx->group.p, lam, ctx->gid.p,
-                         ctx->fx.p, ctx->fy.p, ctx->fz.p, ctx->vx.p, ctx->vy.p, ctx->vz.p, ctx->pos.p, 3, vpart);
+      launch_kick_drift(ctx, dt, lam, KICK_DRIFT, vpart);
       if (vpart)
       {
          RedJob jd = {vpart, nb, 0, nullptr, 0, dt, ctx->d_results + R_DISP};      /* D += dt max |v| */
@@ -573,15 +591,11 @@ static int step_pre_b(ddcmi_ctx *ctx, double dt)
 }
 static int step_pre_c(ddcmi_ctx *ctx, double dt)
 {
-   int n = ctx->nloc, nb = cdiv(n, 256);
    if (!ctx->drift_done && ctx->ncgroup > 0)
    {
       int rcc;
-      GroupLambda lam = front_lambda(ctx, dt);
       if ((rcc = ddcmi_launch_constraints(ctx, dt, 0))) return rcc;
-      if (n > 0)
-         hipLaunchKernelGGL(k_kick_drift, dim3(nb), dim3(256), 0, ctx->stream, n, dt, ctx->d_invmass.p, ctx->species.p, ctx->group.p, lam, ctx->gid.p,
-                            ctx->fx.p, ctx->fy.p, ctx->fz.p, ctx->vx.p, ctx->vy.p, ctx->vz.p, ctx->pos.p, 2, (double *)nullptr);
+      if (ctx->nloc > 0) launch_kick_drift(ctx, dt, front_lambda(ctx, dt), DRIFT_ONLY);
    }
    ctx->drift_done = false;             /* else: the previous step's last kernel already did this kick + drift */
    ctx->time += dt;
@@ -640,11 +654,10 @@ static int step_post(ddcmi_ctx *ctx, double dt, bool more_steps)
    if (fuse)
    {
       /* forces, BACK kick, kinetic terms, FRONT kick and drift in ONE pass: the pair kernel's epilogue is k_kick_ke_drift */
-      const GroupLambda &lam = lam_f;
       FuseArgs fa;
       memset(&fa, 0, sizeof(fa));
       fa.dt = dt;
-      fa.lam = ctx->ngroup > 0 ? lam.v[0] : 1.0;
+      fa.lam = ctx->ngroup > 0 ? lam_f.v[0] : 1.0;
       fa.invmass = ctx->d_invmass.p; fa.massv = ctx->d_mass.p;
       fa.vx = ctx->vx.p; fa.vy = ctx->vy.p; fa.vz = ctx->vz.p;
       ENSURE(ctx, ctx->kpartials, (size_t)(std::max(ctx->nitems, cdiv(ctx->nloc, DDCMI_BLOCK * KE_PER)) + 8) * 8);
@@ -659,7 +672,7 @@ static int step_post(ddcmi_ctx *ctx, double dt, bool more_steps)
       fa.pos_new = ctx->pos2.p; fa.kpartials = ctx->kpartials.p;
       if ((rc = launch_forces(ctx, true, &fa, lean_capable(ctx)))) return rc;
       const StepPlan &p = ctx->plan;
-      if (!p.fused) return kick_ke_then_drift(ctx, dt, lam);      /* (the launch kept the plain kernel: LDS layout; the kick follows as usual) */
+      if (!p.fused) return kick_ke_then_drift(ctx, dt, lam_f);      /* (the launch kept the plain kernel: LDS layout; the kick follows as usual) */
       ctx->drift_done = true;
       std::swap(ctx->pos, ctx->pos2);
       if (p.lean)
@@ -698,14 +711,7 @@ static int step_post(ddcmi_ctx *ctx, double dt, bool more_steps)
    {
       /* nglfconstraint.c:567-571: BACK kick, velocityConstraintOld(BACK), then kinetic_terms (a decomposed run puts the
        * velocity halo between the kick and the solve: step_post_cons_b) */
-      if (ctx->nloc > 0)
-      {
-         GroupLambda lb = lam;
-         const int nblk = cdiv(ctx->nloc, DDCMI_BLOCK * KE_PER);
-         ENSURE(ctx, ctx->kpartials, (size_t)(nblk + 8) * 8);
-         hipLaunchKernelGGL(k_kick_ke, dim3(nblk), dim3(DDCMI_BLOCK), 0, ctx->stream, ctx->nloc, dt, ctx->d_invmass.p, ctx->d_mass.p, ctx->species.p,
-                            ctx->fx.p, ctx->fy.p, ctx->fz.p, ctx->vx.p, ctx->vy.p, ctx->vz.p, ctx->kpartials.p, 1, ctx->group.p, lb, ctx->gid.p);
-      }
+      if (ctx->nloc > 0 && (rc = launch_kick_ke(ctx, dt, 1, lam))) return rc;
       if (ctx->group_) return DDCMI_OK;      /* the group driver exchanges the velocities of all domains, then calls step_post_cons_b */
       if (cons_exchange(ctx) && (rc = ddcmi_mg_refresh_vel(ctx))) return rc;
       return step_post_cons_b(ctx, dt);

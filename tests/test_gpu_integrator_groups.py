@@ -12,15 +12,20 @@ Worst deviation seen over the whole matrix on an MI355X, as a fraction of the ga
 species): see WORST, printed when the module's tests are over (pytest -s)."""
 import copy
 import ctypes
+import os
+import sys
 
 import numpy as np
 import pytest
 
+import integrator_paths_worker as paths
 import integrator_reference as ir
+from ranks import run_ranks
 from ddcmd_amd import martini
 from ddcmd_amd.martini import MartiniHIP, MartiniGroup
 
 pytestmark = pytest.mark.gpu
+HERE = os.path.dirname(os.path.abspath(__file__))
 
 CASES = [("all-32", n) for n in ir.SIZES] + [(t, n) for t in ("mixed", "holes", "free+equal-berendsen") for n in ir.TABLE_SIZES]
 CASE_IDS = ["%s-%d" % c for c in CASES]
@@ -171,6 +176,46 @@ def test_free_groups_with_and_without_the_lean_step(n, interacting, batch, no_le
     else:
         monkeypatch.delenv("DDCMI_NO_LEAN_STEP", raising=False)
     run_case(ir.make_system(n, "free", interacting), batch, interacting)
+
+
+@pytest.fixture(scope="module")
+def split_runs(tmp_path_factory):
+    """run (c) of every case, in ONE child process: DDCMI_NO_FUSED_STEP is read once per process"""
+    out = str(tmp_path_factory.mktemp("paths") / "split.npz")
+    env = dict(os.environ, DDCMI_NO_FUSED_STEP="1")
+    env.pop("DDCMI_NO_LEAN_STEP", None)
+    res = run_ranks([[sys.executable, os.path.join(HERE, "integrator_paths_worker.py"), out]], [env], timeout=300, check=True)
+    assert "integrator_paths_worker ok" in res[0].stdout
+    return dict(np.load(out))
+
+
+@pytest.mark.parametrize("table,n,lcg", paths.CASES, ids=paths.IDS)
+def test_the_step_paths_agree_bit_for_bit(table, n, lcg, split_runs, monkeypatch, request):
+    """Six interacting steps by every path the StepPlan can take, held against each other byte for byte: (a) six calls of one step
+    (k_kick_ke, then k_kick_drift), (b) one call of six (k_kick_ke_drift, or the pair kernel's fused epilogue where fuse_ok holds),
+    (c) the same under DDCMI_NO_FUSED_STEP (k_kick_ke_drift for every table; a child process), (d) all groups FREE only: the same
+    under DDCMI_NO_LEAN_STEP (the fused epilogue, its sums reduced after every step).  Compared: r, v, the group temperatures and the
+    LCG64 states behind step 6, and rk and tion of step 6 -- a batched call shows its sums at its end only.  The temperatures are read
+    once, behind step 6, in run (a) too: a read between the steps would hand Berendsen other averages than the batched runs see."""
+    s = ir.make_system(n, table, True, lcg=lcg)
+    monkeypatch.delenv("DDCMI_NO_LEAN_STEP", raising=False)
+    a = paths.six_steps(s, BATCHES["single"])
+    case = request.node.callspec.id
+    runs = {"one call of 6 steps": paths.six_steps(s, [6]),
+            "DDCMI_NO_FUSED_STEP": {k[len(case) + 1:]: v for k, v in split_runs.items() if k.startswith(case + " ")}}
+    if table == "free":
+        monkeypatch.setenv("DDCMI_NO_LEAN_STEP", "1")      # (read when the context is created)
+        runs["DDCMI_NO_LEAN_STEP"] = paths.six_steps(s, [6])
+    assert a["sums"].shape == (6, 7) and ("lcg" in a) == lcg
+    for what, b in runs.items():
+        assert sorted(b) == sorted(a), (what, sorted(b))
+        assert b["sums"].shape == (1, 7)
+        assert np.array_equal(b["sums"][0], a["sums"][5]), "%s: rk, tion of step 6 differ from the single steps' by %.3g" % (what, np.abs(b["sums"][0] - a["sums"][5]).max())
+        for name in ("r", "v", "T", "lcg")[:4 if lcg else 3]:
+            assert np.array_equal(b[name], a[name]), "%s: %s differs from the single steps'" % (what, name)
+    assert not np.array_equal(a["v"], np.stack([s.vx, s.vy, s.vz]))      # (the steps did something)
+    if lcg:
+        assert not np.array_equal(a["lcg"], s.lcg64["state"])
 
 
 def test_kinetic_sums_past_the_stride_of_their_kernels():
