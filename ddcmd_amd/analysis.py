@@ -1,4 +1,4 @@
-"""ANALYSIS types PAIRCORRELATION, VELOCITYAUTOCORRELATION, vcmWrite, zdensity, KINETICENERGYDISTN, DSF, subsetWrite and COARSEGRAIN on the host side.
+"""ANALYSIS types PAIRCORRELATION, VELOCITYAUTOCORRELATION, vcmWrite, zdensity, KINETICENERGYDISTN, DSF, subsetWrite, COARSEGRAIN and cholAnalysis on the host side.
 PairCorrelation: accumulation of the device's pair counts into g(r) and the output file, as paircorrelation_eval_geom /
 paircorrelation_output (paircorrelation.c) do.  The counting itself is ddcmi_pair_correlation (Martini*.pair_correlation); nothing
 here searches pairs.
@@ -356,6 +356,64 @@ class KineticEnergyDistn(object):
             row += "%*d" % (LOOP_WIDTH, int(loop)) + " %16.6f " % time
             row += "%12.6f %12.8f %12.8f %4.0f %4.0f %8.0f " % (ave * ec, self.min[i] * ec, self.max[i] * ec, self.tallies[i, 1], self.tallies[i, 2], total)
         return row + "\n"
+
+
+def _c_float(fmt, x):
+    """fmt % x as C's printf prints it on x86-64: the NaN of an invalid operation (0/0, 0 * inf) carries the sign bit -- "-nan"""
+    return "-nan" if x != x else fmt % x
+
+
+class CholAnalysis(object):
+    """one cholAnalysis analysis (cholAnalysis.c): the histograms of the cholesterol ring-plane offsets dR1 and dR5.  rmin, rmax and
+    delta in internal length units; nbins = lrint((rmax - rmin) / delta) and delta is formed anew as (rmax - rmin) / nbins, as the
+    reference's _parms has them (nbins < 1, where the reference divides by zero, is refused).  add() takes one evaluation combined
+    over the ranks (Martini*.chol_offsets: counts, stats = {sum, min, max} of dR1, then of dR5); evaluations accumulate until
+    clear().  data_line(loop, time) is the line appended to dataFilename, distn_text() the file snapshot.<loop>/<filename>; the
+    reference clears after writing both.  Both averages divide by the total of the first histogram, as the reference does."""
+
+    def __init__(self, rmin, rmax, delta=0.1, filename="cholAnalysis.distn", data_filename="cholAnalysis.data", eval_rate=0, outputrate=0):
+        self.rmin, self.rmax = float(rmin), float(rmax)
+        q = (self.rmax - self.rmin) / float(delta) if float(delta) != 0.0 else float("nan")
+        self.nbins = int(round(q)) if q == q and abs(q) < 2.0 ** 31 else 0      # lrint: to nearest, ties to even
+        if self.nbins < 1:
+            raise ValueError("cholAnalysis: rmin = %g, rmax = %g, delta = %g give %d bins" % (self.rmin, self.rmax, float(delta), self.nbins))
+        self.delta = (self.rmax - self.rmin) / self.nbins
+        self.filename, self.data_filename = filename, data_filename
+        self.eval_rate, self.outputrate = int(eval_rate), int(outputrate)
+        self.clear()
+
+    def clear(self):
+        self.cnt = np.zeros(2 * self.nbins, np.int64)
+        self.sum = np.zeros(2)
+        self.min, self.max = np.full(2, 1e300), np.full(2, -1e300)
+
+    def add(self, counts, stats):
+        stats = np.asarray(stats, np.float64).reshape(2, 3)
+        self.cnt += np.asarray(counts, np.int64).reshape(2 * self.nbins)
+        self.sum += stats[:, 0]
+        self.min = np.where(stats[:, 1] < self.min, stats[:, 1], self.min)
+        self.max = np.where(stats[:, 2] > self.max, stats[:, 2], self.max)
+
+    def data_line(self, loop, time):
+        """time as simulate->time holds it (internal units: the reference converts nothing here)"""
+        lc = units_convert(1.0, None, "Angstrom")
+        cnt1 = float(self.cnt[:self.nbins].sum())
+        with np.errstate(all="ignore"):
+            ave = self.sum / np.float64(cnt1)      # (no molecule: 0/0, printed as C prints it)
+        vals = [time, self.min[0] * lc, self.max[0] * lc, ave[0] * lc, self.min[1] * lc, self.max[1] * lc, ave[1] * lc]
+        return "%d " % int(loop) + " ".join(_c_float("%f", float(v)) for v in vals) + "\n"
+
+    def distn_text(self):
+        lc = units_convert(1.0, None, "Angstrom")
+        cnt1, cnt3 = float(self.cnt[:self.nbins].sum()), float(self.cnt[self.nbins:].sum())
+        lines = []
+        with np.errstate(all="ignore"):
+            w1, w3 = np.float64(1.0) / np.float64(cnt1 * self.delta), np.float64(1.0) / np.float64(cnt3 * self.delta)
+            for i in range(self.nbins):
+                r = self.rmin + (i + 0.5) * self.delta
+                v = (r * lc, np.float64(self.cnt[i]) / lc * w1, np.float64(self.cnt[i + self.nbins]) / lc * w3)
+                lines.append("".join(" " + _c_float("%e", float(x)) for x in v) + "\n")
+        return "".join(lines)
 
 
 def parse_kdist_output(text):

@@ -409,6 +409,11 @@ struct ddcmi_ctx
    /* COARSEGRAIN (ddcmi_coarsegrain.inl): the sort's (key, value) pairs, source and destination; its digit counts and their scan; the
     * workgroups' head counts and offsets; the segment table; the records */
    dbuf<unsigned> cg_key, cg_val, cg_cnt, cg_seg; dbuf<int> cg_hist; dbuf<unsigned long long> cg_rec;
+   /* cholAnalysis (ddcmi_chol.inl): the listed gids in ascending order; the permutation back to (mol, role) with the fragment
+    * counts and offsets; the molecules' positions; the present and split bytes; the packed fragments.  On the host, the list as
+    * the caller gave it last, sorted, with its permutation: the same list is not sorted or uploaded twice */
+   dbuf<unsigned long long> chol_ids, chol_frag; dbuf<int> chol_int; dbuf<double> chol_table; dbuf<unsigned char> chol_flag;
+   std::vector<uint64_t> chol_list; std::vector<unsigned long long> chol_sorted; std::vector<int> chol_perm_h; bool chol_list_fresh = false; int64_t chol_nfrag = 0;
    /* what is not a dbuf or an hbuf; those free themselves after this */
    ~ddcmi_ctx()
    {

@@ -1,6 +1,7 @@
 /* analysis.c -- see analysis.h: the supported ANALYSIS types, one row of `types` each, and the driver's walks over a deck's list. */
 #include "analysis.h"
 #include "units.h"
+#include "chol.h"
 #include <errno.h>
 #include <stdlib.h>
 #include <string.h>
@@ -993,6 +994,185 @@ static void cg_output(SIMULATE *simulate, const ddcmi_analysis *an, void *state)
 }
 static void cg_free(void *state) { CGSTATE *p = state; free(p->tab); free(p->info); free(p); }
 
+/* ANALYSIS type cholAnalysis (cholAnalysis.c: parms :41-71, eval :109-163, output :73-108): for every CHOL molecule how far the bead
+ * next to each ring triangle stands out of that triangle's plane, dR1 and dR5, in two histograms with their sum and extremes.  Every
+ * evaluation comes from the device (ddcmi_chol_offsets over the list the loader made, an->chol_gid); the ranks' counts and sums are
+ * added in rank order, the extremes combined by a maximum over the ranks, the fragments of the molecules split over ranks gathered on
+ * rank 0 in rank order (the transport subsetWrite uses) and those molecules completed there with the device lane's arithmetic
+ * (ddcmi_chol_complete).  Rank 0 accumulates; at the output it appends one line to dataFilename in the run directory (opened for
+ * append at init; the time stays in internal units, as in the reference) and writes snapshot.<loop>/<filename> under a temporary
+ * name, renamed when complete; then everything is cleared.  The startup evaluation is cleared as well.  The reference's printf of
+ * cnt1 and cnt3 to stdout is not restated: stdout belongs to rank 0's data lines.  A deck without a CHOL molecule is legal: 0/0 is
+ * printed as C prints it. */
+typedef struct { FILE *file; int nbins; double delta; int64_t *cnt, *acc; double stats[6], sum[2], min[2], max[2], *buf; ddcmi_chol_fragment *frag; int64_t fragcap; } CHSTATE;
+static void ch_parms(const OBJECT *obj, ddcmi_analysis *an, char *msg, int msglen)
+{
+   object_get(obj, "potentialName", &an->chol_potential, STRING, 1, "martini");
+   object_get(obj, "dataFilename", &an->chol_data_filename, STRING, 1, "cholAnalysis.data");
+   object_get(obj, "delta", &an->chol_delta, WITH_UNITS, 1, "0.1", "l", NULL);
+   object_get(obj, "rmin", &an->chol_rmin, WITH_UNITS, 1, "0", "l", NULL);
+   object_get(obj, "rmax", &an->chol_rmax, WITH_UNITS, 1, "0", "l", NULL);
+   if (!an->chol_potential) an->chol_potential = strdup("");
+   if (!an->chol_data_filename) an->chol_data_filename = strdup("");
+   const OBJECT *pot = object_find(an->chol_potential, "POTENTIAL");      /* the reference's two asserts */
+   char *ptype = NULL;
+   if (pot) object_get(pot, "type", &ptype, STRING, 1, "");
+   if (!pot) snprintf(msg, msglen, "ANALYSIS %s: potentialName = %s, and there is no POTENTIAL object of that name", an->name, an->chol_potential);
+   else if (!ptype || strcmp(ptype, "MARTINI") != 0)
+      snprintf(msg, msglen, "ANALYSIS %s: potentialName = %s is a POTENTIAL of type %s, not MARTINI", an->name, an->chol_potential, ptype ? ptype : "");
+   free(ptype);
+   const double q = (an->chol_rmax - an->chol_rmin) / an->chol_delta;
+   an->chol_nbins = isfinite(q) && fabs(q) < 2e9 ? (int)lrint(q) : 0;
+   if (an->chol_nbins < 1)
+   {
+      snprintf(msg, msglen, "ANALYSIS %s: rmin = %g, rmax = %g, delta = %g give %d bins (at least one is needed)", an->name, an->chol_rmin, an->chol_rmax, an->chol_delta,
+               an->chol_nbins);
+      return;
+   }
+   an->chol_delta = (an->chol_rmax - an->chol_rmin) / an->chol_nbins;
+   if (an->chol_nbins > DDCMI_CHOL_MAX_NBINS)
+      snprintf(msg, msglen, "ANALYSIS %s: %d bins need %ld bytes of the device's LDS, at most %d (8 per bin: %d bins)", an->name, an->chol_nbins,
+               DDCMI_CHOL_LDS_BYTES((long)an->chol_nbins), DDCMI_CHOL_MAX_LDS, DDCMI_CHOL_MAX_NBINS);
+   else if (!an->chol_data_filename[0] || !an->filename || !an->filename[0]) snprintf(msg, msglen, "ANALYSIS %s: an empty file name", an->name);
+}
+static void ch_clear(SIMULATE *simulate, const ddcmi_analysis *an, void *state)
+{
+   (void)simulate; (void)an;
+   CHSTATE *p = state;
+   memset(p->acc, 0, sizeof(int64_t) * 2 * (size_t)p->nbins);
+   for (int q = 0; q < 2; q++) { p->sum[q] = 0.0; p->min[q] = 1e300; p->max[q] = -1e300; }
+}
+static void *ch_init(SIMULATE *simulate, const ddcmi_analysis *an)
+{
+   CHSTATE *p = zalloc(1, sizeof(CHSTATE));
+   p->nbins = an->chol_nbins; p->delta = an->chol_delta;
+   p->cnt = zalloc(2 * (size_t)p->nbins + 1, sizeof(int64_t)); p->acc = zalloc(2 * (size_t)p->nbins + 1, sizeof(int64_t));
+   p->buf = zalloc(2 * (size_t)p->nbins + 8, sizeof(double));
+   p->fragcap = 64; p->frag = zalloc((size_t)p->fragcap, sizeof(ddcmi_chol_fragment));
+   ch_clear(simulate, an, p);
+   if (par.rank == 0)
+   {
+      p->file = fopen(an->chol_data_filename, "a");
+      if (!p->file) die("cholAnalysis_parms", "cannot open the data file");
+   }
+   return p;
+}
+static void ch_eval(SIMULATE *simulate, const ddcmi_analysis *an, void *state)
+{
+   CHSTATE *p = state;
+   ddcmi_ctx *ctx = simulate->accelerator->parms;
+   const char *where = "cholAnalysis_eval";
+   const int nb2 = 2 * p->nbins, nmol = an->chol_nmol;
+   int64_t ndone = 0, nfrag = 0;
+   memset(p->cnt, 0, sizeof(int64_t) * (size_t)nb2);
+   for (int q = 0; q < 2; q++) { p->stats[3 * q] = 0.0; p->stats[3 * q + 1] = 1e300; p->stats[3 * q + 2] = -1e300; }
+   if (ddcmi_chol_offsets(ctx, nmol, an->chol_gid, an->chol_rmin, p->delta, p->nbins, p->cnt, &ndone, p->stats, 0, NULL, &nfrag) != DDCMI_OK) die(where, ddcmi_last_error(ctx));
+   if (nfrag > p->fragcap)
+   {
+      free(p->frag);
+      p->fragcap = nfrag + nfrag / 4; p->frag = zalloc((size_t)p->fragcap, sizeof(ddcmi_chol_fragment));
+   }
+   /* (the fragments stay packed on the device: a copy, not a second pass) */
+   if (nfrag > 0 && ddcmi_chol_fragments(ctx, p->fragcap, p->frag, &nfrag) != DDCMI_OK) die(where, ddcmi_last_error(ctx));
+   /* counts, ndone and the two sums added in rank order (the integers stay below 2^53: exact); {-min, max} by a maximum */
+   double *mm = p->buf + nb2 + 3;
+   for (int k = 0; k < nb2; k++) p->buf[k] = (double)p->cnt[k];
+   p->buf[nb2] = (double)ndone; p->buf[nb2 + 1] = p->stats[0]; p->buf[nb2 + 2] = p->stats[3];
+   mm[0] = -p->stats[1]; mm[1] = p->stats[2]; mm[2] = -p->stats[4]; mm[3] = p->stats[5];
+   sum_over_ranks(p->buf, nb2 + 3, where);
+   if (par.world > 1 && ddcmi_rdzv_allreduce_f64(par.rdzv, mm, 4, 1) != DDCMI_OK) die(where, ddcmi_rdzv_last_error(par.rdzv));
+   /* the ranks' fragments on rank 0, one block behind the other in rank order */
+   ddcmi_chol_fragment *all = p->frag;
+   int64_t nall = nfrag;
+   if (par.world > 1)
+   {
+      int64_t *cnt = zalloc(par.world, sizeof(int64_t));
+      if (ddcmi_rdzv_allgather(par.rdzv, &nfrag, cnt, sizeof(int64_t)) != DDCMI_OK) die(where, ddcmi_rdzv_last_error(par.rdzv));
+      if (par.rank != 0)
+      {
+         const int peer = 0; const void *sb = p->frag; const size_t sbytes = sizeof(ddcmi_chol_fragment) * (size_t)nfrag;
+         if (ddcmi_rdzv_exchange(par.rdzv, nfrag > 0 ? 1 : 0, &peer, &sb, &sbytes, 0, NULL, NULL, NULL) != DDCMI_OK) die(where, ddcmi_rdzv_last_error(par.rdzv));
+      }
+      else
+      {
+         nall = 0;
+         for (int r = 0; r < par.world; r++) nall += cnt[r];
+         all = zalloc((size_t)nall + 1, sizeof(ddcmi_chol_fragment));
+         memcpy(all, p->frag, sizeof(ddcmi_chol_fragment) * (size_t)nfrag);
+         int *peer = zalloc(par.world, sizeof(int)); void **rb = zalloc(par.world, sizeof(void *)); size_t *rbytes = zalloc(par.world, sizeof(size_t));
+         int nr = 0; size_t off = (size_t)nfrag;
+         for (int r = 1; r < par.world; r++)
+         {
+            if (cnt[r] > 0) { peer[nr] = r; rb[nr] = all + off; rbytes[nr] = sizeof(ddcmi_chol_fragment) * (size_t)cnt[r]; nr++; }
+            off += (size_t)cnt[r];
+         }
+         if (ddcmi_rdzv_exchange(par.rdzv, 0, NULL, NULL, NULL, nr, peer, rb, rbytes) != DDCMI_OK) die(where, ddcmi_rdzv_last_error(par.rdzv));
+         free(peer); free(rb); free(rbytes);
+      }
+      free(cnt);
+   }
+   if (par.rank == 0)
+   {
+      for (int k = 0; k < nb2; k++) p->cnt[k] = (int64_t)p->buf[k];
+      ndone = (int64_t)p->buf[nb2];
+      double st[6] = {p->buf[nb2 + 1], -mm[0], mm[1], p->buf[nb2 + 2], -mm[2], mm[3]};
+      double h[9];
+      char err[512] = "";
+      if (ddcmi_get_box(ctx, h) != DDCMI_OK) die(where, ddcmi_last_error(ctx));
+      const double L[3] = {h[0], h[4], h[8]};
+      if (ddcmi_chol_complete(nall, all, nmol, an->chol_gid, L, simulate->setup->pbc, an->chol_rmin, p->delta, p->nbins, p->cnt, &ndone, st, err, sizeof(err)) != 0)
+         die(where, err);
+      if (ndone != nmol)
+      {
+         snprintf(err, sizeof(err), "%" PRId64 " of the %d CHOL molecules were found: a listed bead is owned by no rank", ndone, nmol);
+         die(where, err);
+      }
+      for (int k = 0; k < nb2; k++) p->acc[k] += p->cnt[k];
+      for (int q = 0; q < 2; q++)
+      {
+         p->sum[q] += st[3 * q];
+         if (st[3 * q + 1] < p->min[q]) p->min[q] = st[3 * q + 1];
+         if (st[3 * q + 2] > p->max[q]) p->max[q] = st[3 * q + 2];
+      }
+   }
+   if (all != p->frag) free(all);
+}
+static void ch_output(SIMULATE *simulate, const ddcmi_analysis *an, void *state)
+{
+   CHSTATE *p = state;
+   const char *where = "cholAnalysis_output";
+   if (par.rank == 0)
+   {
+      const double lc = units_convert(1.0, NULL, "Angstrom");
+      int64_t cnt1 = 0, cnt3 = 0;
+      for (int i = 0; i < p->nbins; i++) { cnt1 += p->acc[i]; cnt3 += p->acc[i + p->nbins]; }
+      const double ave1 = p->sum[0] / (double)cnt1, ave5 = p->sum[1] / (double)cnt1;      /* both by cnt1, as the reference does */
+      fprintf(p->file, "%" PRId64 " %f %f %f %f %f %f %f\n", simulate->loop, simulate->time, p->min[0] * lc, p->max[0] * lc, ave1 * lc, p->min[1] * lc, p->max[1] * lc,
+              ave5 * lc);
+      fflush(p->file);
+      char tmpname[700], dir[512], path[1300], tmppath[1300];
+      snprintf(tmpname, sizeof(tmpname), "%s.tmp", an->filename);
+      FILE *f = snapshot_fopen(simulate, tmpname, where);
+      for (int i = 0; i < p->nbins; i++)
+      {
+         const double r = (an->chol_rmin + (i + 0.5) * p->delta);
+         fprintf(f, " %e %e %e\n", r * lc, (double)p->acc[i] / lc * (1.0 / ((double)cnt1 * p->delta)), (double)p->acc[i + p->nbins] / lc * (1.0 / ((double)cnt3 * p->delta)));
+      }
+      if (fclose(f) != 0) die(where, "cannot write the output file");
+      snprintf(dir, sizeof(dir), "snapshot.%012" PRId64, simulate->loop);
+      snprintf(path, sizeof(path), "%s/%s", dir, an->filename);
+      snprintf(tmppath, sizeof(tmppath), "%s/%s", dir, tmpname);
+      if (rename(tmppath, path) != 0) die(where, "cannot rename the output file");
+   }
+   ch_clear(simulate, an, p);
+}
+static void ch_free(void *state)
+{
+   CHSTATE *p = state;
+   if (p->file) fclose(p->file);
+   free(p->cnt); free(p->acc); free(p->buf); free(p->frag); free(p);
+}
+
 /* ------------------------------------------------------------------------- */
 static const char *const dsf_heads[] = {"DynamicStructureFactor", "Dynamic_Structure_Factor", NULL};
 static const ANALYSIS_TYPE types[] = {      /* indexed by enum ddcmi_analysis_kind; DDCMI_AN_NONE has no row */
@@ -1004,6 +1184,7 @@ static const ANALYSIS_TYPE types[] = {      /* indexed by enum ddcmi_analysis_ki
    [DDCMI_AN_DSF] = {"DSF", DDCMI_AN_DSF, "rho_k.data", dsf_parms, dsf_init, dsf_eval, dsf_output, NULL, dsf_free, 0, NULL, dsf_heads},
    [DDCMI_AN_SUBSETWRITE] = {"subsetWrite", DDCMI_AN_SUBSETWRITE, "subset", sw_parms, sw_init, sw_eval, sw_output, NULL, sw_free, 1, "subset_write"},
    [DDCMI_AN_COARSEGRAIN] = {"COARSEGRAIN", DDCMI_AN_COARSEGRAIN, "cgrid", cg_parms, cg_init, cg_eval, cg_output, cg_clear, cg_free},
+   [DDCMI_AN_CHOL] = {"cholAnalysis", DDCMI_AN_CHOL, "cholAnalysis.distn", ch_parms, ch_init, ch_eval, ch_output, ch_clear, ch_free, 1, NULL},
 };
 const ANALYSIS_TYPE *analysis_type_find(const char *type_name)
 {

@@ -33,6 +33,13 @@ static char *dir_of(const char *path)
    memcpy(r, path, s - path); r[s - path] = 0;
    return r;
 }
+/* qsort of bead indices by gid */
+static const uint64_t *sort_by_gid_base;
+static int cmp_by_gid(const void *a, const void *b)
+{
+   const uint64_t x = sort_by_gid_base[*(const int *)a], y = sort_by_gid_base[*(const int *)b];
+   return x < y ? -1 : x > y;
+}
 static char *get_string(const OBJECT *o, const char *key, const char *dflt)
 {
    char *s = NULL;
@@ -1233,6 +1240,41 @@ ddcmi_setup *ddcmi_deck_load_with(const char *object_file, const char *restart_f
       object_get(co, "size", &size, INT, 1, "-1");
       if (size >= 0 && size != s->natoms) FAIL("COLLECTION size=%d but %d records read", size, s->natoms);
    }
+   /* ANALYSIS cholAnalysis: the CHOL molecules of the particle set (cholAnalysis.c:116-136 walks residueSet along gidOrder): the beads in
+    * gid order, cut into residue runs where gid & molResMask changes; a run whose first bead's species belongs to the residue named
+    * exactly CHOL gives its first seven gids.  Where the reference reads r[6] of a shorter residue, the deck is refused */
+   for (int a = 0; a < s->nanalysis; a++)
+   {
+      ddcmi_analysis *an = &s->analysis[a];
+      if (an->type != DDCMI_AN_CHOL) continue;
+      for (int r = 0; r < nresi; r++)
+         if (strcmp(resi[r].resName, "CHOL") == 0 && resi[r].natoms < 7)
+            FAIL("ANALYSIS %s: the CHOL residue has %d atoms, cholAnalysis needs seven", an->name, resi[r].natoms);
+      uint64_t *sorted = malloc(sizeof(uint64_t) * (size_t)(s->natoms + 1));
+      int *idx = malloc(sizeof(int) * (size_t)(s->natoms + 1));
+      for (int i = 0; i < s->natoms; i++) idx[i] = i;
+      sort_by_gid_base = s->gid;
+      qsort(idx, (size_t)s->natoms, sizeof(int), cmp_by_gid);
+      for (int i = 0; i < s->natoms; i++) sorted[i] = s->gid[idx[i]];
+      an->chol_gid = calloc(7 * (size_t)(s->natoms / 7 + 1), sizeof(uint64_t));
+      an->chol_nmol = 0;
+      int bad = -1, badn = 0;
+      for (int i = 0; i < s->natoms;)
+      {
+         int j = i + 1;
+         while (j < s->natoms && ((sorted[j] ^ sorted[i]) & 0xFFFFFFFFFFFF0000ull) == 0) j++;
+         const int rt = s->resitype[s->species[idx[i]]];
+         if (rt >= 0 && rt < nresi && strcmp(resi[rt].resName, "CHOL") == 0)
+         {
+            if (j - i < 7) { if (bad < 0) { bad = i; badn = j - i; } }
+            else { memcpy(an->chol_gid + 7 * (size_t)an->chol_nmol, sorted + i, 7 * sizeof(uint64_t)); an->chol_nmol++; }
+         }
+         i = j;
+      }
+      const uint64_t badgid = bad >= 0 ? sorted[bad] : 0;
+      free(sorted); free(idx);
+      if (bad >= 0) FAIL("ANALYSIS %s: the CHOL residue at gid %" PRIu64 " has %d beads, cholAnalysis needs seven", an->name, badgid, badn);
+   }
    /* a value whose unit could not be read came back as NaN somewhere above: the deck is refused, not run with it (tools/fuzz_decks.py, round 6) */
    if (units_error()[0]) FAIL("%s", units_error());
    for (int r = 0; r < nresi; r++) { free_resi(&resi[r]); free(resiNames[r]); }
@@ -1274,6 +1316,7 @@ void ddcmi_setup_free(ddcmi_setup *s)
       free(an->dist); free(an->name); free(an->type_name); free(an->filename); free(an->m); free(an->dsf_species);
       for (int k = 0; k < an->sw_nspecies; k++) free(an->sw_species[k]);
       free(an->sw_species); free(an->sw_idlist); free(an->sw_length_unit); free(an->cg_smear_string);
+      free(an->chol_potential); free(an->chol_data_filename); free(an->chol_gid);
    }
    free(s->analysis);
    for (int t = 0; t < s->ntransform; t++) { free(s->transform[t].name); free(s->transform[t].type_name); free(s->transform[t].temperature); }

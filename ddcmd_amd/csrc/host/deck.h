@@ -22,7 +22,7 @@ enum { DDCMI_GROUP_FREE = 0, DDCMI_GROUP_BERENDSEN = 1, DDCMI_GROUP_LANGEVIN = 2
 
 /* one ANALYSIS object (analysis_init, analysis.c:120-160).  type: the row of host/analysis.c's table that evaluates it; DDCMI_AN_NONE is any
  * other type (not supported: the driver names it once on stderr) */
-enum ddcmi_analysis_kind { DDCMI_AN_NONE = 0, DDCMI_AN_PAIRCORRELATION, DDCMI_AN_VAF, DDCMI_AN_VCMWRITE, DDCMI_AN_ZDENSITY, DDCMI_AN_KDIST, DDCMI_AN_DSF, DDCMI_AN_SUBSETWRITE, DDCMI_AN_COARSEGRAIN };
+enum ddcmi_analysis_kind { DDCMI_AN_NONE = 0, DDCMI_AN_PAIRCORRELATION, DDCMI_AN_VAF, DDCMI_AN_VCMWRITE, DDCMI_AN_ZDENSITY, DDCMI_AN_KDIST, DDCMI_AN_DSF, DDCMI_AN_SUBSETWRITE, DDCMI_AN_COARSEGRAIN, DDCMI_AN_CHOL };
 /* one BIN object of a KINETICENERGYDISTN analysis (kineticEnergyDistn.c:58-83): the histogram of one species' kinetic energies */
 typedef struct ddcmi_kdist_group { char *name, *species; double emin, emax; int nbins; } ddcmi_kdist_group;      /* internal energy units; nbins >= 1, emax > emin */
 typedef struct ddcmi_analysis
@@ -57,6 +57,12 @@ typedef struct ddcmi_analysis
    int cg_output_mode;          /* outputMode 1 (13 fields) or 2 (19 fields, the default); an object with 3 stays unsupported */
    int cg_nfiles;               /* nfiles is read and ignored: one file */
    char *cg_smear_string;       /* smearMethod as the deck spells it (the file's misc_info echoes it) */
+   /* from here on cholAnalysis only (cholAnalysis.c:41-71), zero / NULL otherwise.  Internal length units; nbins = lrint((rmax - rmin) / delta) >= 1
+    * and delta formed anew as (rmax - rmin) / nbins; chol_gid[7 chol_nmol]: the first seven gids of every CHOL residue of the particle set, in gid order */
+   char *chol_potential, *chol_data_filename;
+   double chol_rmin, chol_rmax, chol_delta;
+   int chol_nbins, chol_nmol;
+   uint64_t *chol_gid;
 } ddcmi_analysis;
 
 /* one TRANSFORM object of SIMULATE transform = name ... (transform_init, transform.c:30-60).  type DDCMI_TR_THERMALIZE: thermalizeTransform_parms

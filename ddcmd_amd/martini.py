@@ -77,7 +77,73 @@ def _sm_args(nspecies, kvec, select, weight, nrank=1):
 
 SUBSET_RECORD = np.dtype([("id", "<u8"), ("pinfo", "<u4"), ("r", "<f4", (3,))])      # struct ddcmi_subset_record: 24 bytes, the file's record
 CG_RECORD = np.dtype([("label", "<i8"), ("species", "<i4"), ("pad", "<i4"), ("n", "<f8"), ("mass", "<f8"), ("K", "<f8", (3,)), ("p", "<f8", (3,))])      # struct ddcmi_cg_record: 80 bytes
+CHOL_FRAGMENT = np.dtype([("mol", "<i4"), ("role", "<i4"), ("r", "<f8", (3,))])      # struct ddcmi_chol_fragment: 32 bytes
 GID_MAX = 2 ** 64 - 1
+
+
+def _chol_args(gid7, nbins, nrank=1):
+    """the arrays ddcmi_chol_offsets takes and fills: (gid[7 nmol], counts[nrank, 2 nbins], ndone[nrank], stats[nrank, 6], nfrag[nrank])"""
+    gid = np.ascontiguousarray(gid7, np.uint64).reshape(-1)
+    if gid.size % 7:
+        raise ValueError("chol_offsets: %d gids, not seven per molecule" % gid.size)
+    return (np.ascontiguousarray(np.concatenate([gid, np.zeros(1, np.uint64)])), np.zeros((nrank, 2 * max(int(nbins), 1)), np.int64), np.zeros(nrank, np.int64),
+            np.zeros((nrank, 6)), np.zeros(nrank, np.int64))
+
+
+def chol_merge(lib, setup, gid7, rmin, delta, nbins, counts, ndone, stats, frags):
+    """the ranks' results of ddcmi_chol_offsets merged as its contract says -- counts and ndone added, the sums added in rank order,
+    minimum of the minima, maximum of the maxima -- and the split molecules completed on the host from the fragments, concatenated in
+    rank order, in ascending molecule order (ddcmi_chol_complete).  Returns (counts[2 nbins], stats[6], n)."""
+    gid = np.ascontiguousarray(gid7, np.uint64).reshape(-1)
+    nmol = gid.size // 7
+    c = np.ascontiguousarray(np.asarray(counts, np.int64).reshape(-1, 2 * int(nbins)).sum(axis=0))
+    st = np.asarray(stats, np.float64).reshape(-1, 6)
+    tot = st[0].copy()
+    for r in range(1, len(st)):
+        tot[0::3] += st[r, 0::3]
+        tot[1::3] = np.minimum(tot[1::3], st[r, 1::3])
+        tot[2::3] = np.maximum(tot[2::3], st[r, 2::3])
+    tot = np.ascontiguousarray(tot)
+    n = np.array([int(np.sum(ndone))], np.int64)
+    fr = np.ascontiguousarray(np.concatenate([np.asarray(f, CHOL_FRAGMENT).reshape(-1) for f in frags]) if len(frags) else np.zeros(0, CHOL_FRAGMENT))
+    if len(fr):
+        box = np.ascontiguousarray(np.asarray(setup.h, np.float64).reshape(-1)[[0, 4, 8]])
+        err = ctypes.create_string_buffer(512)
+        rc = lib.ddcmi_chol_complete(len(fr), fr.ctypes.data_as(ctypes.c_void_p), nmol, gid.ctypes.data_as(_up), _d(box), int(getattr(setup, "pbc", 7)),
+                                     float(rmin), float(delta), int(nbins), c.ctypes.data_as(_lp), n.ctypes.data_as(_lp), _d(tot), err, 512)
+        if rc != 0:
+            raise DdcmiError(err.value.decode())
+    return c, tot, int(n[0])
+
+
+def chol_molecule(lib, r7, box, pbc, rmin, delta, nbins):
+    """(dR1, dR5, bin1, bin5) of one molecule's seven positions r7[7, 3] with the device lane's operations on the host (ddcmi_chol_molecule)"""
+    r = np.ascontiguousarray(r7, np.float64).reshape(21)
+    L = np.ascontiguousarray(box, np.float64).reshape(3)
+    d, b = np.zeros(2), np.zeros(2, np.int32)
+    lib.ddcmi_chol_molecule(_d(r), _d(L), int(pbc), float(rmin), float(delta), int(nbins), _d(d), _i(b))
+    return float(d[0]), float(d[1]), int(b[0]), int(b[1])
+
+
+def chol_molecules(setup):
+    """gid7[nmol, 7] of a Setup's CHOL molecules: the residue runs in gid order, cut where gid & molResMask changes as the bonded
+    terms cut them (expand_bonded_terms); a run is a CHOL residue when its first bead's species has the residue name CHOL (the
+    species name up to the first of 'c', 'n', 'x'); roles 0..6 are its first seven beads, an eighth is unused"""
+    import re
+    order = np.argsort(setup.gid, kind="stable")
+    g = np.asarray(setup.gid, np.uint64)[order]
+    key = g & _MOLRES
+    first = np.flatnonzero(np.concatenate(([True], key[1:] != key[:-1]))) if len(g) else np.zeros(0, np.int64)
+    cnt = np.diff(np.concatenate((first, [len(g)])))
+    is_chol = np.array([re.split("[cnx]", nm, 1)[0] == "CHOL" for nm in setup.species_name], bool)
+    out = []
+    for f, c in zip(first, cnt):
+        if not is_chol[setup.species[order[f]]]:
+            continue
+        if c < 7:
+            raise DdcmiError("CHOL residue at gid %d has %d beads, cholAnalysis needs seven" % (int(g[f]), int(c)))
+        out.append(g[f:f + 7])
+    return np.array(out, np.uint64).reshape(-1, 7)
 
 
 class CSubsetFilter(ctypes.Structure):
@@ -205,6 +271,12 @@ def _declare(lib):
     lib.ddcmi_subset_records.argtypes = [vp, ctypes.POINTER(CSubsetFilter), ctypes.c_int64, vp, _lp]
     lib.ddcmi_coarsegrain.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int64, vp, _lp]
     lib.ddcmi_thermalize.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int]
+    lib.ddcmi_chol_offsets.argtypes = [vp, ctypes.c_int64, _up, ctypes.c_double, ctypes.c_double, ctypes.c_int, _lp, _lp, _dp, ctypes.c_int64, vp, _lp]
+    lib.ddcmi_chol_fragments.argtypes = [vp, ctypes.c_int64, vp, _lp]
+    lib.ddcmi_chol_complete.argtypes = [ctypes.c_int64, vp, ctypes.c_int64, _up, _dp, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, _lp, _lp, _dp,
+                                        ctypes.c_char_p, ctypes.c_size_t]
+    lib.ddcmi_chol_molecule.argtypes = [_dp, _dp, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, _dp, _ip]
+    lib.ddcmi_chol_molecule.restype = None
     lib._ddcmi_declared = True
 
 
@@ -726,6 +798,21 @@ class MartiniHIP(object):
                                                       counts.ctypes.data_as(_lp), tallies.ctypes.data_as(_lp), _d(stats)))
         return counts, tallies, stats
 
+    def chol_offsets(self, gid7, rmin, delta, nbins, fragments=False):
+        """ANALYSIS cholAnalysis, one evaluation of this rank (ddcmi_chol_offsets): gid7[nmol, 7] the molecules' beads of roles 0..6,
+        rmin and delta in internal length units.  Returns (counts[2 nbins] int64 -- the histogram of dR1, then of dR5 --, stats[6] =
+        {sum, min, max} of dR1, then of dR5, n the molecules counted); with fragments, a fourth value: the beads of the molecules this
+        rank owns in part, a structured array of CHOL_FRAGMENT (mol, role, r) for chol_merge"""
+        gid, counts, ndone, stats, nfrag = _chol_args(gid7, nbins)
+        nmol = (gid.size - 1) // 7
+        self._chk(self.lib.ddcmi_chol_offsets(self.ctx, nmol, gid.ctypes.data_as(_up), float(rmin), float(delta), int(nbins), counts.ctypes.data_as(_lp),
+                                              ndone.ctypes.data_as(_lp), _d(stats), 0, None, nfrag.ctypes.data_as(_lp)))      # (frag NULL: the count)
+        frag = np.zeros(int(nfrag[0]), CHOL_FRAGMENT)
+        if fragments and len(frag):      # (they stay packed on the device: a copy, not a second pass)
+            self._chk(self.lib.ddcmi_chol_fragments(self.ctx, len(frag), frag.ctypes.data_as(ctypes.c_void_p), nfrag.ctypes.data_as(_lp)))
+        out = (counts[0], stats[0], int(ndone[0]))
+        return out + (frag[:int(nfrag[0])].copy(),) if fragments else out
+
     def charge_density_modes(self, mmax, select=None):
         """ANALYSIS DSF, one evaluation of this rank (ddcmi_charge_density_modes): (rho complex128 [3, mmax], count) -- rho[a, m - 1] the
         sum of q exp(i 2 pi m r_a / L_a) over the owned beads of the species select marks (None: all), count their number; the division
@@ -877,6 +964,8 @@ def _declare_domains(lib):
     lib.ddcmi_group_coarsegrain.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int,
                                             ctypes.c_int64, vp, _lp]
     lib.ddcmi_group_thermalize.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int]
+    lib.ddcmi_group_chol_offsets.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int64, _up, ctypes.c_double, ctypes.c_double, ctypes.c_int, _lp, _lp, _dp,
+                                             ctypes.c_int64, vp, _lp]
     lib._ddcmi_dom_declared = True
 
 
@@ -1096,6 +1185,32 @@ class MartiniGroup(object):
             tot[:, 1] = np.minimum(tot[:, 1], stats[r, :, 1])
             tot[:, 2] = np.maximum(tot[:, 2], stats[r, :, 2])
         return counts.sum(axis=0), tallies.sum(axis=0), tot
+
+    def chol_offsets(self, gid7, rmin, delta, nbins, per_rank=False, cap=None, out=None):
+        """ddcmi_group_chol_offsets: the domains' results merged (chol_merge: counts and ndone added, sums in rank order, extremes
+        combined) and the molecules split over domains completed on the host -- (counts[2 nbins], stats[6], n) -- or, per_rank,
+        (counts[rank], ndone[rank], stats[rank], fragments in rank order, nfrag[rank]).  cap / out: the capacity handed down (default:
+        what the fragments need) and the array they land in -- for the refusal of a buffer that is too small."""
+        gid, counts, ndone, stats, nfrag = _chol_args(gid7, nbins, self.n)
+        nmol = (gid.size - 1) // 7
+        a = (self.arr, self.n, nmol, gid.ctypes.data_as(_up), float(rmin), float(delta), int(nbins), counts.ctypes.data_as(_lp), ndone.ctypes.data_as(_lp), _d(stats))
+        if cap is None and out is None:      # the count first (frag NULL), then the ranks' packed fragments: copies, not a second pass
+            self._chk(self.lib.ddcmi_group_chol_offsets(*a, 0, None, nfrag.ctypes.data_as(_lp)))
+            frag = np.zeros(int(nfrag.sum()), CHOL_FRAGMENT)
+            off, one = 0, np.zeros(1, np.int64)
+            for r, k in zip(self.ranks, nfrag):
+                if k:
+                    part = np.zeros(int(k), CHOL_FRAGMENT)
+                    r._chk(self.lib.ddcmi_chol_fragments(r.ctx, int(k), part.ctypes.data_as(ctypes.c_void_p), one.ctypes.data_as(_lp)))
+                    frag[off:off + int(k)] = part
+                off += int(k)
+        else:
+            frag = np.zeros(max(int(cap), 1), CHOL_FRAGMENT) if out is None else out
+            self._chk(self.lib.ddcmi_group_chol_offsets(*a, len(frag) if cap is None else int(cap), frag.ctypes.data_as(ctypes.c_void_p), nfrag.ctypes.data_as(_lp)))
+        frag = frag[:int(nfrag.sum())]
+        if per_rank:
+            return counts, ndone, stats, frag, nfrag
+        return chol_merge(self.lib, self.s, gid[:-1], rmin, delta, nbins, counts, ndone, stats, [frag])
 
     def charge_density_modes(self, mmax, select=None, per_rank=False):
         """ddcmi_group_charge_density_modes: the domains' (rho, count) added in rank order -- or, per_rank, stacked [rank, ...]"""

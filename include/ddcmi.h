@@ -377,6 +377,35 @@ int ddcmi_subset_records(ddcmi_ctx *ctx, const ddcmi_subset_filter *filter, int6
 typedef struct ddcmi_cg_record { int64_t label; int32_t species; int32_t pad; double n, mass, K[3], p[3]; } ddcmi_cg_record;      /* 80 bytes */
 int ddcmi_coarsegrain(ddcmi_ctx *ctx, int nx, int ny, int nz, int nspecies, double smear_radius, int smear_method, int64_t cap, ddcmi_cg_record *rec,
                       int64_t *count);
+/* ANALYSIS cholAnalysis on the device (cholAnalysis.c:109-163, cholAnalysis_eval): for each of nmol listed molecules -- gid[7 m + role],
+ * roles 0..6 the first seven beads of a CHOL residue in gid order, the list in any molecule order -- the ring-plane offsets, in one
+ * read-only pass under the rules above.  With b(i,j) the nearest image of r_j - r_i (the rint form, open axes not wrapped):
+ *    A = b(0,1), B = b(0,2), C = b(0,3), D = b(4,5), E = b(4,3), F = b(4,6)
+ *    dR1 = ((B x C) . A) / |B x C|,   dR5 = -((E x F) . D) / |E x F|
+ * every operation rounded once, in the reference's order.  A molecule all of whose seven beads this rank owns is counted:
+ * counts[ibin(dR1)]++, counts[nbins + ibin(dR5)]++ with ibin(d) = (int)MIN(MAX((d - rmin) / delta, 0), nbins - 1) (a NaN: bin 0),
+ * (*ndone)++, stats[0..2] = {sum, min, max} of dR1 and stats[3..5] of dR5; the extremes start at the reference's 1e300 and -1e300
+ * and a NaN joins the sum and neither extreme.  A molecule of which this rank owns one to six beads is returned as fragments
+ * {mol, role, r} in (mol, role) order -- mol the index in the list, r the position a download returns; halo beads are never read --
+ * and a molecule it owns nothing of leaves no trace.  *nfrag: this rank's fragments, always.  frag NULL: nothing else.  Otherwise the
+ * fragments if cap >= *nfrag; with a smaller cap DDCMI_EINVAL, *nfrag (and counts, ndone, stats) set and frag untouched.  Over ranks:
+ * add counts and ndone, add the sums in rank order, minimum of the minima, maximum of the maxima, concatenate the fragments in rank
+ * order and complete the split molecules on the host with the lane's own arithmetic (ddcmi_chol_complete of the host layer).
+ * Internal units.  nmol = 0 is valid and touches nothing.  DDCMI_EINVAL, nothing changed: nmol < 0, a NULL array with a positive
+ * count, nbins < 1, a delta that is not finite and positive, an rmin that is not finite, a gid listed twice, no state or no box.
+ * DDCMI_EUNSUPPORTED: a box that is not orthorhombic; nbins > DDCMI_CHOL_MAX_NBINS (the two histograms share one workgroup's LDS
+ * with the workgroup's partial sums: DDCMI_CHOL_LDS_BYTES(nbins) <= DDCMI_CHOL_MAX_LDS). [sync] */
+#define DDCMI_CHOL_MAX_LDS 65536
+#define DDCMI_CHOL_LDS_BYTES(nbins) (4 * (2 * (nbins) + 1) + 196)
+#define DDCMI_CHOL_MAX_NBINS 8167
+typedef struct ddcmi_chol_fragment { int32_t mol, role; double r[3]; } ddcmi_chol_fragment;      /* 32 bytes */
+int ddcmi_chol_offsets(ddcmi_ctx *ctx, int64_t nmol, const uint64_t *gid /* [7 nmol], roles 0..6 */, double rmin, double delta, int nbins,
+                       int64_t *counts /* [2 nbins] */, int64_t *ndone, double *stats /* {sum,min,max} of dR1, then of dR5 */,
+                       int64_t cap, ddcmi_chol_fragment *frag, int64_t *nfrag);
+/* The fragments of this context's last ddcmi_chol_offsets once more: they stay packed in a device buffer of the context until its next
+ * ddcmi_chol_offsets, so a caller asks for the count first (frag NULL above) and fetches them here without a second pass.  *nfrag:
+ * their number, always; frag NULL: nothing else; cap < *nfrag: DDCMI_EINVAL and frag untouched. [sync] */
+int ddcmi_chol_fragments(ddcmi_ctx *ctx, int64_t cap, ddcmi_chol_fragment *frag, int64_t *nfrag);
 
 /* ---- transforms ------------------------------------------------------------ */
 /* TRANSFORM type THERMALIZE on the device (thermalize.c:83-269): new velocities for the owned beads.  Only the velocities change --

@@ -90,6 +90,11 @@ int ddcmi_group_subset_records(ddcmi_ctx **ctxs, int n, const ddcmi_subset_filte
  * rank order, cap the room for all of them (too small: DDCMI_EINVAL, the counts set, rec untouched) */
 int ddcmi_group_coarsegrain(ddcmi_ctx **ctxs, int n, int nx, int ny, int nz, int nspecies, double smear_radius, int smear_method, int64_t cap,
                             ddcmi_cg_record *rec, int64_t *count);
+/* ddcmi_chol_offsets for an in-process group: every domain's own result, domain after domain -- counts[r*2*nbins ...], ndone[r],
+ * stats[r*6 ...], nfrag[r] for domain r; with frag, the domains' fragments one block behind the other in rank order, cap the room
+ * for all of them (too small: DDCMI_EINVAL, everything else set, frag untouched) */
+int ddcmi_group_chol_offsets(ddcmi_ctx **ctxs, int n, int64_t nmol, const uint64_t *gid, double rmin, double delta, int nbins, int64_t *counts,
+                             int64_t *ndone, double *stats, int64_t cap, ddcmi_chol_fragment *frag, int64_t *nfrag);
 /* ddcmi_thermalize for an in-process group: every domain's own beads; RESCALE adds the domains' sums in rank order */
 int ddcmi_group_thermalize(ddcmi_ctx **ctxs, int n, int method, int select, int ntemp, const double *temperature, uint64_t seed, int64_t loop, int keep_vcm);
 /* what ddcmi_thermalize's BOLTZMANN would do with this context's owned beads, without writing a velocity: in the order of

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""ANALYSIS vcmWrite, zdensity and KINETICENERGYDISTN on the headline boxes: what one call of each entry point costs, beside one ddcmi_vaf_sample and
+"""ANALYSIS vcmWrite, zdensity, KINETICENERGYDISTN and (chol:<lattice>, default 63: 1.0 M beads, 10^5 molecules) cholAnalysis on the headline boxes: what one call of each entry point costs, beside one ddcmi_vaf_sample and
 one plain step of the same box in the same process.
    python3 tools/time_census.py [water:<lattice> | lipid:<x,y,z>] ...   (default: water:102 lipid:12,12,6 -- 4.24 M and 2.04 M beads)
 Every call is timed by HIP events recorded on the context's stream around it (the kernels and the copy of the result; median of
@@ -53,7 +53,52 @@ def timed(m, call, e0, e1, reps=20, warm=3):
     return float(np.median(dev)), min(dev), 1e3 * float(np.median(host))
 
 
-for spec in (sys.argv[1:] or ["water:102", "lipid:12,12,6"]):
+def chol_rows(lattice, nmol=100000):
+    """ANALYSIS cholAnalysis (ddcmi_chol_offsets) on a synthetic box: the water lattice of about 10^6 beads with nmol molecules planted as
+    lists of seven beads each (the pass costs the same whatever their geometry), beside what the same result cost before the pass
+    existed: ddcmi_download_particles of the same state, without the host arithmetic.  The first call sorts and uploads the list; the
+    later ones find it kept with the context."""
+    s = ddcmd_amd.make_water_setup(int(lattice))
+    m = MartiniHIP(s)
+    m.eval_forces()
+    m.step(20)
+    m.sync()
+    rng = np.random.RandomState(1)
+    gid7 = np.asarray(s.gid, np.uint64)[rng.permutation(s.natoms)[:7 * nmol]].reshape(-1, 7)
+    e0, e1 = vp(), vp()
+    assert hip.hipEventCreate(ctypes.byref(e0)) == 0 and hip.hipEventCreate(ctypes.byref(e1)) == 0
+    L = float(s.h[0])
+    t0 = time.perf_counter()
+    m.chol_offsets(gid7, -0.5 * L, L / 100, 100)
+    first = 1e3 * (time.perf_counter() - t0)
+    print("cholAnalysis: %d beads, %d molecules listed; the first call (sorts and uploads the list) %.3f ms on the host clock" % (s.natoms, len(gid7), first), flush=True)
+    cap, nout = s.natoms + 16, ctypes.c_int(0)
+    dg, dr = np.zeros(cap, np.uint64), [np.zeros(cap) for _ in range(3)]
+
+    def download():      # what the host arithmetic needs: the gids and the positions (no species, velocities or forces)
+        m._chk(m.lib.ddcmi_download_particles(m.ctx, cap, ctypes.byref(nout), dg.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), None,
+                                              *[a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) for a in dr], None, None, None, None, None, None))
+    rows = [("chol_offsets 100 bins", lambda: m.chol_offsets(gid7, -0.5 * L, L / 100, 100)),
+            ("chol_offsets 8167 bins", lambda: m.chol_offsets(gid7, -0.5 * L, L / 8167, 8167)),
+            ("chol_offsets other list", None),
+            ("ddcmi_download_particles gid, r", download)]
+    flip = [gid7, gid7[::-1].copy()]
+    for label, call in rows:
+        if call is None:      # the list changes every call: the sort and the upload every time
+            state = [0]
+
+            def call():
+                state[0] ^= 1
+                m.chol_offsets(flip[state[0]], -0.5 * L, L / 100, 100)
+        med, lo, host = timed(m, call, e0, e1)
+        print("  %-32s %8.4f ms by events (min %.4f; host clock %.4f ms)" % (label, med, lo, host), flush=True)
+    m.close()
+
+
+for spec in (sys.argv[1:] or ["water:102", "lipid:12,12,6", "chol:63"]):
+    if spec.startswith("chol:"):
+        chol_rows(spec.split(":")[1])
+        continue
     s, name = system(spec)
     m = MartiniHIP(s)
     m.eval_forces()
