@@ -82,7 +82,7 @@ c_u64_p = ctypes.POINTER(ctypes.c_uint64)
 c_char_pp = ctypes.POINTER(ctypes.c_char_p)
 
 
-AN_NONE, AN_PAIRCORRELATION, AN_VAF, AN_VCMWRITE, AN_ZDENSITY, AN_KDIST, AN_DSF, AN_SUBSETWRITE, AN_COARSEGRAIN, AN_CHOL = range(10)      # enum ddcmi_analysis_kind
+AN_NONE, AN_PAIRCORRELATION, AN_VAF, AN_VCMWRITE, AN_ZDENSITY, AN_KDIST, AN_DSF, AN_SUBSETWRITE, AN_COARSEGRAIN, AN_CHOL, AN_FORCEAVERAGE = range(11)      # enum ddcmi_analysis_kind
 
 
 class CKdistGroup(ctypes.Structure):
@@ -106,7 +106,8 @@ class CAnalysis(ctypes.Structure):
                 ("cg_n", ctypes.c_int * 3), ("cg_output_mode", ctypes.c_int), ("cg_nfiles", ctypes.c_int), ("cg_smear_string", ctypes.c_char_p),
                 ("chol_potential", ctypes.c_char_p), ("chol_data_filename", ctypes.c_char_p),
                 ("chol_rmin", ctypes.c_double), ("chol_rmax", ctypes.c_double), ("chol_delta", ctypes.c_double),
-                ("chol_nbins", ctypes.c_int), ("chol_nmol", ctypes.c_int), ("chol_gid", c_u64_p)]
+                ("chol_nbins", ctypes.c_int), ("chol_nmol", ctypes.c_int), ("chol_gid", c_u64_p),
+                ("fa_nid", ctypes.c_int), ("fa_what", ctypes.c_int), ("fa_gid", c_u64_p)]
 
 
 TR_NONE, TR_THERMALIZE = range(2)      # enum ddcmi_transform_kind

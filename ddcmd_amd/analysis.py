@@ -907,3 +907,57 @@ def read_cgrid(path):
         if crc != int(out["checksum"][k]):
             raise ValueError("%s: record %d: checksum %08x, CRC-32 of its bytes %08x" % (path, k, int(out["checksum"][k]), crc))
     return hdr, out
+
+
+class ForceAverage(object):
+    """ANALYSIS type FORCE_AVERAGE (forceAverage.c): the time average of the force, velocity or position of the beads with the listed
+    gids over a window of samples, one text line per window.  The running sums stay on the device (Martini*.track_set / track_accumulate /
+    track_read); this class counts the samples, applies the reference's gate and formats the file's texts.  Internal units: the
+    reference's conversions are commented out."""
+
+    def __init__(self, gids, data_type="force", eval_rate=1, outputrate=1):
+        self.gids = [int(g) for g in np.asarray(gids, dtype=np.uint64).reshape(-1)]
+        self.data_type = data_type.lower()
+        if self.data_type not in ("force", "velocity", "position"):
+            raise ValueError("data_type = %s is none of force, velocity, position" % data_type)      # the reference's exit(19)
+        self.eval_rate, self.outputrate = int(eval_rate), int(outputrate)
+        if self.eval_rate < 1:
+            raise ValueError("eval_rate = %d, it must be at least 1" % self.eval_rate)
+        self.nsnap = 0
+        self.m = None
+
+    def header(self):
+        return "# loop  time  " + "".join("%d  " % g for g in self.gids) + "\n"
+
+    def sample(self, m):
+        """forceAverage_eval on a MartiniHIP, a MartiniRank or a MartiniGroup: the first sample of the object hands it the list"""
+        if self.m is not m:
+            m.track_set(self.gids)
+            self.m = m
+        m.track_accumulate(self.data_type)
+        self.nsnap += 1
+
+    def clear(self):
+        """forceAverage_clear: the sums on the device and the sample count"""
+        if self.m is not None:
+            self.m.track_read(reset=True)
+        self.nsnap = 0
+
+    def text(self, loop, time, total, hits):
+        """the line of a window of self.nsnap samples with the sums total[n, 3]; every gid must have been found once per sample"""
+        for g, h in zip(self.gids, np.asarray(hits).reshape(-1)):
+            if int(h) != self.nsnap:
+                raise RuntimeError("gid %d was found %d times in %d evaluations" % (g, int(h), self.nsnap))
+        t = np.asarray(total, dtype=np.float64).reshape(-1, 3)
+        body = "".join(" %12.7f %12.7f %12.7f " % tuple(float(x) / float(self.nsnap) for x in row) for row in t)
+        return "%012d" % int(loop) + " %10.6f " % float(time) + body + "\n"
+
+    def line(self, loop, time):
+        """forceAverage_output: None while nSnapSum * eval_rate < outputrate (nothing is cleared); otherwise the line, and the window is
+        cleared"""
+        if self.nsnap * self.eval_rate < self.outputrate:
+            return None
+        total, hits = self.m.track_read() if self.m is not None else (np.zeros((len(self.gids), 3)), np.zeros(len(self.gids), np.int64))
+        out = self.text(loop, time, total, hits)
+        self.clear()
+        return out

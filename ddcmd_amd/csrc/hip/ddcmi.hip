@@ -1435,6 +1435,7 @@ extern "C" int ddcmi_timing_fused(ddcmi_ctx *ctx, int64_t *launches, double *tot
 #include "ddcmi_ssf.inl"
 #include "ddcmi_subset.inl"
 #include "ddcmi_chol.inl"
+#include "ddcmi_track.inl"
 #include "ddcmi_coarsegrain.inl"
 #include "ddcmi_debug_primitives.inl"
 #include "ddcmi_debug_reductions.inl"

@@ -414,6 +414,11 @@ struct ddcmi_ctx
     * the caller gave it last, sorted, with its permutation: the same list is not sorted or uploaded twice */
    dbuf<unsigned long long> chol_ids, chol_frag; dbuf<int> chol_int; dbuf<double> chol_table; dbuf<unsigned char> chol_flag;
    std::vector<uint64_t> chol_list; std::vector<unsigned long long> chol_sorted; std::vector<int> chol_perm_h; bool chol_list_fresh = false; int64_t chol_nfrag = 0;
+   /* FORCE_AVERAGE (ddcmi_track.inl): the tracked gids, ascending and unique, with their running sums [3 nu] and hit counts [nu], which
+    * stay on the device from one evaluation to the next.  On the host, the list as the caller gave it, the unique gids, and the place of
+    * every listed gid among them; track_what: the quantity the current window sums (-1: nothing added yet) */
+   dbuf<unsigned long long> track_ids, track_hits; dbuf<double> track_sum;
+   std::vector<uint64_t> track_list; std::vector<unsigned long long> track_sorted; std::vector<int> track_slot; int track_what = -1;
    /* what is not a dbuf or an hbuf; those free themselves after this */
    ~ddcmi_ctx()
    {

@@ -1173,6 +1173,132 @@ static void ch_free(void *state)
    free(p->cnt); free(p->acc); free(p->buf); free(p->frag); free(p);
 }
 
+/* ANALYSIS type FORCE_AVERAGE (forceAverage.c: parms :28-73, eval :76-145, output :148-190, clear :193-205): the time average of the
+ * force, the velocity or the position of the beads idParticle lists, one line per window appended to `filename` in the run directory
+ * (opened for append, with the header line, at init).  The running sums live on the device (ddcmi_track_set / _accumulate / _read):
+ * an evaluation is one launch and counts the sample, and the host does not wait.  At the output, under the reference's gate
+ * nSnapSum * eval_rate >= outputrate, every rank reads its partial sums; they are added over the ranks in rank order, every gid's
+ * hits over the ranks must equal nSnapSum, rank 0 writes the line in internal units (the reference's conversions are commented out)
+ * and everything is cleared.  The startup evaluation is cleared as well.
+ * A context tracks one list.  Several FORCE_AVERAGE objects take turns: the object whose list is on the device is fa_owner, and an
+ * object that evaluates while another one owns the device first moves the owner's sums to the owner's host accumulators (one read
+ * with reset) and sets its own list.  A deck with one such object never reads between two outputs.  The host adds whole device
+ * sums; with objects that alternate at every evaluation each device sum is one sample, so the bits are those of one running sum. */
+typedef struct { FILE *file; int n, nsnap; double *sum, *buf; int64_t *hits, *part; } FASTATE;
+static FASTATE *fa_owner = NULL;
+static void fa_parms(const OBJECT *obj, ddcmi_analysis *an, char *msg, int msglen)
+{
+   char *dt = NULL;
+   object_get(obj, "eval_rate", &an->eval_rate, INT, 1, "1");       /* forceAverage_parms' defaults, not analysis_init's 0 */
+   object_get(obj, "outputrate", &an->outputrate, INT, 1, "1");
+   object_get(obj, "data_type", &dt, STRING, 1, "force");
+   an->fa_nid = object_getv(obj, "idParticle", (void **)&an->fa_gid, U64, IGNORE_IF_NOT_FOUND);
+   const char *data_type = dt ? dt : "";
+   if (strcasecmp(data_type, "force") == 0) an->fa_what = 0;
+   else if (strcasecmp(data_type, "velocity") == 0) an->fa_what = 1;
+   else if (strcasecmp(data_type, "position") == 0) an->fa_what = 2;
+   else snprintf(msg, msglen, "ANALYSIS %s: data_type = %s is none of force, velocity, position", an->name, data_type);      /* the reference's exit(19) */
+   if (!an->fa_gid || an->fa_nid < 0)
+   {
+      an->fa_nid = 0;
+      snprintf(msg, msglen, "ANALYSIS %s: no idParticle key (the gids of the beads to follow)", an->name);      /* ABORT_IF_NOT_FOUND */
+   }
+   else if (an->fa_nid > DDCMI_TRACK_MAX_IDS) snprintf(msg, msglen, "ANALYSIS %s: idParticle lists %d gids, the device tracks at most %d", an->name, an->fa_nid, DDCMI_TRACK_MAX_IDS);
+   else if (an->eval_rate < 1) snprintf(msg, msglen, "ANALYSIS %s: eval_rate = %d, it must be at least 1", an->name, an->eval_rate);
+   else if (!an->filename || !an->filename[0]) snprintf(msg, msglen, "ANALYSIS %s: an empty file name", an->name);
+   free(dt);
+}
+/* the device's sums into the owner's host accumulators, and the device's cleared */
+static void fa_spill(SIMULATE *simulate, const char *where)
+{
+   FASTATE *p = fa_owner;
+   ddcmi_ctx *ctx = simulate->accelerator->parms;
+   if (!p) return;
+   if (ddcmi_track_read(ctx, p->n, p->buf, p->part, 1) != DDCMI_OK) die(where, ddcmi_last_error(ctx));
+   for (int k = 0; k < 3 * p->n; k++) p->sum[k] += p->buf[k];
+   for (int k = 0; k < p->n; k++) p->hits[k] += p->part[k];
+}
+static void fa_acquire(SIMULATE *simulate, const ddcmi_analysis *an, FASTATE *p, const char *where)
+{
+   ddcmi_ctx *ctx = simulate->accelerator->parms;
+   if (fa_owner == p) return;
+   fa_spill(simulate, where);
+   fa_owner = NULL;
+   if (ddcmi_track_set(ctx, an->fa_nid, an->fa_gid) != DDCMI_OK) die(where, ddcmi_last_error(ctx));
+   fa_owner = p;
+}
+static void fa_clear(SIMULATE *simulate, const ddcmi_analysis *an, void *state)
+{
+   (void)an;
+   FASTATE *p = state;
+   if (fa_owner == p) fa_spill(simulate, "forceAverage_clear");
+   memset(p->sum, 0, sizeof(double) * 3 * (size_t)p->n);
+   memset(p->hits, 0, sizeof(int64_t) * (size_t)p->n);
+   p->nsnap = 0;
+}
+static void *fa_init(SIMULATE *simulate, const ddcmi_analysis *an)
+{
+   FASTATE *p = zalloc(1, sizeof(FASTATE));
+   p->n = an->fa_nid;
+   p->sum = zalloc(3 * (size_t)p->n + 1, sizeof(double)); p->buf = zalloc(4 * (size_t)p->n + 1, sizeof(double));
+   p->hits = zalloc((size_t)p->n + 1, sizeof(int64_t)); p->part = zalloc((size_t)p->n + 1, sizeof(int64_t));
+   if (par.rank == 0)
+   {
+      p->file = fopen(an->filename, "a");
+      if (!p->file) die("forceAverage_parms", "cannot open the output file");
+      fprintf(p->file, "# loop  time  ");
+      for (int i = 0; i < p->n; i++) fprintf(p->file, "%llu  ", (unsigned long long)an->fa_gid[i]);
+      fprintf(p->file, "\n");
+      fflush(p->file);
+   }
+   fa_acquire(simulate, an, p, "forceAverage_parms");
+   return p;
+}
+static void fa_eval(SIMULATE *simulate, const ddcmi_analysis *an, void *state)
+{
+   FASTATE *p = state;
+   ddcmi_ctx *ctx = simulate->accelerator->parms;
+   fa_acquire(simulate, an, p, "forceAverage_eval");
+   if (ddcmi_track_accumulate(ctx, an->fa_what) != DDCMI_OK) die("forceAverage_eval", ddcmi_last_error(ctx));
+   p->nsnap++;
+}
+static void fa_output(SIMULATE *simulate, const ddcmi_analysis *an, void *state)
+{
+   FASTATE *p = state;
+   const char *where = "forceAverage_output";
+   if ((int64_t)p->nsnap * an->eval_rate < (int64_t)an->outputrate) return;
+   if (fa_owner == p) fa_spill(simulate, where);
+   const int n = p->n;
+   for (int k = 0; k < 3 * n; k++) p->buf[k] = p->sum[k];
+   for (int k = 0; k < n; k++) p->buf[3 * n + k] = (double)p->hits[k];      /* (below 2^53: exact) */
+   sum_over_ranks(p->buf, 4 * n, where);
+   for (int k = 0; k < n; k++)
+      if (p->buf[3 * n + k] != (double)p->nsnap)
+      {
+         char err[256];
+         snprintf(err, sizeof(err), "gid %llu was found %.0f times in %d evaluations: a tracked bead is owned by no rank, or by several", (unsigned long long)an->fa_gid[k],
+                  p->buf[3 * n + k], p->nsnap);
+         die(where, err);
+      }
+   if (par.rank == 0)
+   {
+      fprintf(p->file, "%12.12" PRIu64, (uint64_t)simulate->loop);      /* loopFormat() */
+      fprintf(p->file, " %10.6f ", simulate->time);
+      for (int k = 0; k < n; k++)
+         fprintf(p->file, " %12.7f %12.7f %12.7f ", p->buf[3 * k] / (double)p->nsnap, p->buf[3 * k + 1] / (double)p->nsnap, p->buf[3 * k + 2] / (double)p->nsnap);
+      fprintf(p->file, "\n");
+      fflush(p->file);
+   }
+   fa_clear(simulate, an, p);
+}
+static void fa_free(void *state)
+{
+   FASTATE *p = state;
+   if (fa_owner == p) fa_owner = NULL;      /* (the context's list goes with the context) */
+   if (p->file) fclose(p->file);
+   free(p->sum); free(p->buf); free(p->hits); free(p->part); free(p);
+}
+
 /* ------------------------------------------------------------------------- */
 static const char *const dsf_heads[] = {"DynamicStructureFactor", "Dynamic_Structure_Factor", NULL};
 static const ANALYSIS_TYPE types[] = {      /* indexed by enum ddcmi_analysis_kind; DDCMI_AN_NONE has no row */
@@ -1185,6 +1311,7 @@ static const ANALYSIS_TYPE types[] = {      /* indexed by enum ddcmi_analysis_ki
    [DDCMI_AN_SUBSETWRITE] = {"subsetWrite", DDCMI_AN_SUBSETWRITE, "subset", sw_parms, sw_init, sw_eval, sw_output, NULL, sw_free, 1, "subset_write"},
    [DDCMI_AN_COARSEGRAIN] = {"COARSEGRAIN", DDCMI_AN_COARSEGRAIN, "cgrid", cg_parms, cg_init, cg_eval, cg_output, cg_clear, cg_free},
    [DDCMI_AN_CHOL] = {"cholAnalysis", DDCMI_AN_CHOL, "cholAnalysis.distn", ch_parms, ch_init, ch_eval, ch_output, ch_clear, ch_free, 1, NULL},
+   [DDCMI_AN_FORCEAVERAGE] = {"FORCE_AVERAGE", DDCMI_AN_FORCEAVERAGE, "force.dat", fa_parms, fa_init, fa_eval, fa_output, fa_clear, fa_free},
 };
 const ANALYSIS_TYPE *analysis_type_find(const char *type_name)
 {

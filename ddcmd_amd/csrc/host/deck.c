@@ -1275,6 +1275,28 @@ ddcmi_setup *ddcmi_deck_load_with(const char *object_file, const char *restart_f
       free(sorted); free(idx);
       if (bad >= 0) FAIL("ANALYSIS %s: the CHOL residue at gid %" PRIu64 " has %d beads, cholAnalysis needs seven", an->name, badgid, badn);
    }
+   /* ANALYSIS FORCE_AVERAGE: every listed gid is an atom of the collection (forceAverage.c:117-127: rank 0 waits in MPI_Recv for a bead
+    * that no task finds) */
+   for (int a = 0; a < s->nanalysis; a++)
+   {
+      const ddcmi_analysis *an = &s->analysis[a];
+      if (an->type != DDCMI_AN_FORCEAVERAGE) continue;
+      uint64_t *sorted = malloc(sizeof(uint64_t) * (size_t)(s->natoms + 1));
+      int *idx = malloc(sizeof(int) * (size_t)(s->natoms + 1));
+      for (int i = 0; i < s->natoms; i++) idx[i] = i;
+      sort_by_gid_base = s->gid;
+      qsort(idx, (size_t)s->natoms, sizeof(int), cmp_by_gid);
+      for (int i = 0; i < s->natoms; i++) sorted[i] = s->gid[idx[i]];
+      int missing = -1;
+      for (int k = 0; k < an->fa_nid && missing < 0; k++)
+      {
+         int lo = 0, hi = s->natoms;      /* the first atom whose gid is >= the listed one */
+         while (lo < hi) { const int mid = lo + (hi - lo) / 2; if (sorted[mid] < an->fa_gid[k]) lo = mid + 1; else hi = mid; }
+         if (lo >= s->natoms || sorted[lo] != an->fa_gid[k]) missing = k;
+      }
+      free(sorted); free(idx);
+      if (missing >= 0) FAIL("ANALYSIS %s: idParticle names gid %" PRIu64 ", and no atom of the collection carries it", an->name, an->fa_gid[missing]);
+   }
    /* a value whose unit could not be read came back as NaN somewhere above: the deck is refused, not run with it (tools/fuzz_decks.py, round 6) */
    if (units_error()[0]) FAIL("%s", units_error());
    for (int r = 0; r < nresi; r++) { free_resi(&resi[r]); free(resiNames[r]); }
@@ -1317,6 +1339,7 @@ void ddcmi_setup_free(ddcmi_setup *s)
       for (int k = 0; k < an->sw_nspecies; k++) free(an->sw_species[k]);
       free(an->sw_species); free(an->sw_idlist); free(an->sw_length_unit); free(an->cg_smear_string);
       free(an->chol_potential); free(an->chol_data_filename); free(an->chol_gid);
+      free(an->fa_gid);
    }
    free(s->analysis);
    for (int t = 0; t < s->ntransform; t++) { free(s->transform[t].name); free(s->transform[t].type_name); free(s->transform[t].temperature); }

@@ -22,7 +22,7 @@ enum { DDCMI_GROUP_FREE = 0, DDCMI_GROUP_BERENDSEN = 1, DDCMI_GROUP_LANGEVIN = 2
 
 /* one ANALYSIS object (analysis_init, analysis.c:120-160).  type: the row of host/analysis.c's table that evaluates it; DDCMI_AN_NONE is any
  * other type (not supported: the driver names it once on stderr) */
-enum ddcmi_analysis_kind { DDCMI_AN_NONE = 0, DDCMI_AN_PAIRCORRELATION, DDCMI_AN_VAF, DDCMI_AN_VCMWRITE, DDCMI_AN_ZDENSITY, DDCMI_AN_KDIST, DDCMI_AN_DSF, DDCMI_AN_SUBSETWRITE, DDCMI_AN_COARSEGRAIN, DDCMI_AN_CHOL };
+enum ddcmi_analysis_kind { DDCMI_AN_NONE = 0, DDCMI_AN_PAIRCORRELATION, DDCMI_AN_VAF, DDCMI_AN_VCMWRITE, DDCMI_AN_ZDENSITY, DDCMI_AN_KDIST, DDCMI_AN_DSF, DDCMI_AN_SUBSETWRITE, DDCMI_AN_COARSEGRAIN, DDCMI_AN_CHOL, DDCMI_AN_FORCEAVERAGE };
 /* one BIN object of a KINETICENERGYDISTN analysis (kineticEnergyDistn.c:58-83): the histogram of one species' kinetic energies */
 typedef struct ddcmi_kdist_group { char *name, *species; double emin, emax; int nbins; } ddcmi_kdist_group;      /* internal energy units; nbins >= 1, emax > emin */
 typedef struct ddcmi_analysis
@@ -63,6 +63,10 @@ typedef struct ddcmi_analysis
    double chol_rmin, chol_rmax, chol_delta;
    int chol_nbins, chol_nmol;
    uint64_t *chol_gid;
+   /* from here on FORCE_AVERAGE only (forceAverage.c:28-73), zero / NULL otherwise.  fa_gid[fa_nid]: idParticle as written, duplicates kept;
+    * fa_what: data_type 0 force, 1 velocity, 2 position (any case).  eval_rate and outputrate above default to 1 for this type */
+   int fa_nid, fa_what;
+   uint64_t *fa_gid;
 } ddcmi_analysis;
 
 /* one TRANSFORM object of SIMULATE transform = name ... (transform_init, transform.c:30-60).  type DDCMI_TR_THERMALIZE: thermalizeTransform_parms

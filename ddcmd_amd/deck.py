@@ -189,7 +189,7 @@ def load_deck(object_file, restart_file=None, extra_objects=None):
         s.integrator_type = c.integrator_type.decode()
         s.accelerator_type = c.accelerator_type.decode()
         s.units = {k: getattr(c, "u_" + k).decode() for k in ("pressure", "volume", "temperature", "energy", "time", "length")}
-        # SIMULATE analysis = ...: one dict per ANALYSIS object, in list order (types PAIRCORRELATION, VELOCITYAUTOCORRELATION, vcmWrite, zdensity, KINETICENERGYDISTN, DSF, subsetWrite with format = binaryCharmm, COARSEGRAIN with outputMode 1 or 2 and cholAnalysis, with their parameters, internal units)
+        # SIMULATE analysis = ...: one dict per ANALYSIS object, in list order (types PAIRCORRELATION, VELOCITYAUTOCORRELATION, vcmWrite, zdensity, KINETICENERGYDISTN, DSF, subsetWrite with format = binaryCharmm, COARSEGRAIN with outputMode 1 or 2, cholAnalysis and FORCE_AVERAGE, with their parameters, internal units)
         s.analysis = []
         for a in (c.analysis[i] for i in range(int(c.nanalysis))):
             d = {"name": a.name.decode(), "type": (a.type_name or b"").decode(), "eval_rate": int(a.eval_rate), "outputrate": int(a.outputrate),
@@ -219,6 +219,8 @@ def load_deck(object_file, restart_file=None, extra_objects=None):
                 d.update(potential_name=a.chol_potential.decode(), data_filename=a.chol_data_filename.decode(), rmin=float(a.chol_rmin), rmax=float(a.chol_rmax),
                          delta=float(a.chol_delta), nbins=int(a.chol_nbins),
                          gid7=_arr(a.chol_gid, 7 * int(a.chol_nmol), np.uint64).reshape(-1, 7))
+            if a.type == _lib.AN_FORCEAVERAGE:      # gids: idParticle as written, duplicates kept; eval_rate and outputrate default to 1
+                d.update(gids=_arr(a.fa_gid, int(a.fa_nid), np.uint64), data_type=("force", "velocity", "position")[a.fa_what])
             s.analysis.append(d)
         # SIMULATE transform = ...: one dict per TRANSFORM object, in list order (type THERMALIZE with its parameters; temperatures in internal
         # energy units, -1 for a class the object does not name; rate 0: no rate key)

@@ -277,9 +277,13 @@ def _declare(lib):
                                         ctypes.c_char_p, ctypes.c_size_t]
     lib.ddcmi_chol_molecule.argtypes = [_dp, _dp, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, _dp, _ip]
     lib.ddcmi_chol_molecule.restype = None
+    lib.ddcmi_track_set.argtypes = [vp, ctypes.c_int64, _up]
+    lib.ddcmi_track_accumulate.argtypes = [vp, ctypes.c_int]
+    lib.ddcmi_track_read.argtypes = [vp, ctypes.c_int64, _dp, _lp, ctypes.c_int]
     lib._ddcmi_declared = True
 
 
+TRACK_WHAT = {"force": 0, "velocity": 1, "position": 2}      # ddcmi_track_accumulate
 THERMALIZE_METHODS = {"BOLTZMANN": 0, "RESCALE": 1, "JUTTNER": 2}
 THERMALIZE_SELECTS = {"global": 0, "species": 1, "group": 2}
 
@@ -813,6 +817,25 @@ class MartiniHIP(object):
         out = (counts[0], stats[0], int(ndone[0]))
         return out + (frag[:int(nfrag[0])].copy(),) if fragments else out
 
+    def track_set(self, gids):
+        """ANALYSIS FORCE_AVERAGE: the gids whose beads this context follows (ddcmi_track_set), in any order, duplicates allowed; a new
+        list clears the sums, an empty one removes the list"""
+        g = np.ascontiguousarray(np.asarray(gids, dtype=np.uint64).reshape(-1))
+        self._chk(self.lib.ddcmi_track_set(self.ctx, g.size, g.ctypes.data_as(_up) if g.size else None))
+        self._ntrack = int(g.size)
+
+    def track_accumulate(self, what):
+        """one sample (ddcmi_track_accumulate): the owned beads with tracked gids add their force ("force" or 0), velocity ("velocity", 1)
+        or position ("position", 2) to the running sums on the device; asynchronous"""
+        self._chk(self.lib.ddcmi_track_accumulate(self.ctx, TRACK_WHAT[what.lower()] if isinstance(what, str) else int(what)))
+
+    def track_read(self, reset=False):
+        """(sum[n, 3], hits[n]) of this rank in the order of track_set (ddcmi_track_read); reset: the sums are zeroed afterwards"""
+        n = getattr(self, "_ntrack", 0)
+        tot, hits = np.zeros((n, 3)), np.zeros(n, np.int64)
+        self._chk(self.lib.ddcmi_track_read(self.ctx, n, _d(tot), hits.ctypes.data_as(_lp), int(bool(reset))))
+        return tot, hits
+
     def charge_density_modes(self, mmax, select=None):
         """ANALYSIS DSF, one evaluation of this rank (ddcmi_charge_density_modes): (rho complex128 [3, mmax], count) -- rho[a, m - 1] the
         sum of q exp(i 2 pi m r_a / L_a) over the owned beads of the species select marks (None: all), count their number; the division
@@ -1211,6 +1234,24 @@ class MartiniGroup(object):
         if per_rank:
             return counts, ndone, stats, frag, nfrag
         return chol_merge(self.lib, self.s, gid[:-1], rmin, delta, nbins, counts, ndone, stats, [frag])
+
+    def track_set(self, gids):
+        """MartiniHIP.track_set on every domain: each keeps its own sums of the beads it owns at each sample"""
+        for r in self.ranks:
+            r.track_set(gids)
+
+    def track_accumulate(self, what):
+        """MartiniHIP.track_accumulate on every domain; no communication"""
+        for r in self.ranks:
+            r.track_accumulate(what)
+
+    def track_read(self, reset=False, per_rank=False):
+        """the domains' (sum[n, 3], hits[n]) added in rank order -- or, per_rank, stacked [rank, ...]"""
+        parts = [r.track_read(reset) for r in self.ranks]
+        tot, hits = np.stack([p[0] for p in parts]), np.stack([p[1] for p in parts])
+        if per_rank:
+            return tot, hits
+        return self._sum_in_rank_order(tot), hits.sum(axis=0)
 
     def charge_density_modes(self, mmax, select=None, per_rank=False):
         """ddcmi_group_charge_density_modes: the domains' (rho, count) added in rank order -- or, per_rank, stacked [rank, ...]"""

@@ -406,6 +406,30 @@ int ddcmi_chol_offsets(ddcmi_ctx *ctx, int64_t nmol, const uint64_t *gid /* [7 n
  * ddcmi_chol_offsets, so a caller asks for the count first (frag NULL above) and fetches them here without a second pass.  *nfrag:
  * their number, always; frag NULL: nothing else; cap < *nfrag: DDCMI_EINVAL and frag untouched. [sync] */
 int ddcmi_chol_fragments(ddcmi_ctx *ctx, int64_t cap, ddcmi_chol_fragment *frag, int64_t *nfrag);
+/* ANALYSIS FORCE_AVERAGE on the device (forceAverage.c:76-145): running sums of the force, the velocity or the position of the beads
+ * with listed gids, which stay on the device from one evaluation to the next -- an evaluation is one small launch and no host wait.
+ * The three calls are not collective and are legal for the contexts of an in-process group as well.
+ * ddcmi_track_set: the n tracked gids in the caller's order; any order, duplicates (the reference searches once per list entry) and
+ * gids above 2^32 are legal.  The context keeps the list ascending and unique on the device and the caller's order on the host.  A
+ * new list clears the accumulators; n = 0 removes the list and frees its buffers.  n > DDCMI_TRACK_MAX_IDS: DDCMI_EUNSUPPORTED (the
+ * device buffers, 40 bytes per gid, stay below 40 MB).  n < 0, or a NULL list with n > 0: DDCMI_EINVAL, nothing changed. */
+#define DDCMI_TRACK_MAX_IDS (1 << 20)
+int ddcmi_track_set(ddcmi_ctx *ctx, int64_t n, const uint64_t *gid);
+/* forceAverage_eval: one pass over this rank's owned beads; the bead that carries a listed gid adds its three components to that
+ * gid's running sum and 1 to its 64-bit hit count.  what 0: the force of the last force evaluation, 1: the stored velocity, 2: the
+ * position -- each the bits ddcmi_download_state returns at this point (the position wrapped as it wraps).  One gid has one owner,
+ * so one lane writes a slot: a plain load, add and store, no atomics.  Asynchronous on the context's stream, no communication; it
+ * changes nothing of the run and is legal at any point between steps, like the passes above.  A domain that holds no bead, or a
+ * context without a list, does nothing and succeeds.  DDCMI_EINVAL, nothing changed: a what other than 0, 1, 2; no uploaded state;
+ * what = 0 without a valid force evaluation (ddcmi_step_nglf's refusal); a what other than the one the window already holds -- a
+ * window, from one clearing of the accumulators to the next, averages one quantity. */
+int ddcmi_track_accumulate(ddcmi_ctx *ctx, int what /*0 force, 1 velocity, 2 position*/);
+/* this rank's sums and hit counts in the caller's order, sum[3 k .. 3 k + 2] and hits[k] for the k-th listed gid (duplicates get
+ * equal values); n must be the list's length.  reset != 0 then zeroes the accumulators: the next window.  The accumulators belong to
+ * the rank, not to the bead: a tracked bead that migrates goes on adding at its new owner, and nothing travels with it.  A gid no
+ * owned bead carried has sum 0 and hits 0 here; over the ranks the hits of a gid that exists add up to the number of accumulations,
+ * and the window's sum is the ranks' sums added in rank order. [sync] */
+int ddcmi_track_read(ddcmi_ctx *ctx, int64_t n, double *sum /* [3 n] */, int64_t *hits /* [n] */, int reset);
 
 /* ---- transforms ------------------------------------------------------------ */
 /* TRANSFORM type THERMALIZE on the device (thermalize.c:83-269): new velocities for the owned beads.  Only the velocities change --

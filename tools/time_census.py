@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""ANALYSIS vcmWrite, zdensity, KINETICENERGYDISTN and (chol:<lattice>, default 63: 1.0 M beads, 10^5 molecules) cholAnalysis on the headline boxes: what one call of each entry point costs, beside one ddcmi_vaf_sample and
+"""ANALYSIS vcmWrite, zdensity, KINETICENERGYDISTN, (chol:<lattice>, default 63: 1.0 M beads, 10^5 molecules) cholAnalysis and (track:<lattice>, 64: 1.05 M beads) FORCE_AVERAGE on the headline boxes: what one call of each entry point costs, beside one ddcmi_vaf_sample and
 one plain step of the same box in the same process.
    python3 tools/time_census.py [water:<lattice> | lipid:<x,y,z>] ...   (default: water:102 lipid:12,12,6 -- 4.24 M and 2.04 M beads)
 Every call is timed by HIP events recorded on the context's stream around it (the kernels and the copy of the result; median of
@@ -95,7 +95,37 @@ def chol_rows(lattice, nmol=100000):
     m.close()
 
 
-for spec in (sys.argv[1:] or ["water:102", "lipid:12,12,6", "chol:63"]):
+def track_rows(lattice):
+    """ANALYSIS FORCE_AVERAGE: one ddcmi_track_accumulate on the water box with 64 and with 65536 tracked gids (picked at random, so
+    the list's gid range covers the box and every bead searches), beside one ddcmi_momentum_by_class of the same state, the cheapest
+    census pass.  The accumulation does not wait for the device: the events around the call time the launch alone, and the host clock
+    the enqueue.  Under `rocprofv3 --kernel-trace --stats` the two list sizes are told apart by their instantiation: the 64 gids sum
+    the velocity (k_track_accumulate<1>), the 65536 the force (<0>); both read three double arrays on a hit."""
+    s = ddcmd_amd.make_water_setup(int(lattice))
+    m = MartiniHIP(s)
+    m.eval_forces()
+    m.step(20)
+    m.sync()
+    e0, e1 = vp(), vp()
+    assert hip.hipEventCreate(ctypes.byref(e0)) == 0 and hip.hipEventCreate(ctypes.byref(e1)) == 0
+    rng = np.random.RandomState(2)
+    print("FORCE_AVERAGE: %d beads" % s.natoms, flush=True)
+    med, lo, host = timed(m, m.momentum_by_class, e0, e1)
+    print("  %-32s %8.4f ms by events (min %.4f; host clock %.4f ms)" % ("ddcmi_momentum_by_class", med, lo, host), flush=True)
+    for nid, what in ((64, "velocity"), (65536, "force")):
+        m.track_set(np.asarray(s.gid, np.uint64)[rng.permutation(s.natoms)[:nid]])
+        med, lo, host = timed(m, lambda: m.track_accumulate(what), e0, e1)
+        tot, hits = m.track_read(reset=True)
+        assert hits.min() == hits.max() == 23      # 3 warm-up calls and 20 timed ones found every gid
+        print("  %-32s %8.4f ms by events (min %.4f; host clock %.4f ms)  %.4f GB of gids read, %.2f TB/s"
+              % ("track_accumulate %d gids %s" % (nid, what), med, lo, host, 8 * s.natoms / 1e9, 8 * s.natoms / (1e-3 * med) / 1e12), flush=True)
+    m.close()
+
+
+for spec in (sys.argv[1:] or ["water:102", "lipid:12,12,6", "chol:63", "track:64"]):
+    if spec.startswith("track:"):
+        track_rows(spec.split(":")[1])
+        continue
     if spec.startswith("chol:"):
         chol_rows(spec.split(":")[1])
         continue
