@@ -181,7 +181,14 @@ class CSetup(ctypes.Structure):
         ("nanalysis", ctypes.c_int), ("analysis", ctypes.POINTER(CAnalysis)),
         ("group_vset", c_int_p), ("group_v", c_double_p), ("group_Fz", c_double_p),
         ("ntransform", ctypes.c_int), ("transform", ctypes.POINTER(CTransform)),
+        ("group_override", ctypes.c_int),
     ]
+
+
+class CIntegratorType(ctypes.Structure):
+    """Mirror of struct ddcmi_integrator_type (deck.h): one row of the table of INTEGRATOR types."""
+    _fields_ = [("name", ctypes.c_char_p), ("barostat_keys", ctypes.c_int), ("barostat_form", ctypes.c_int), ("group_override", ctypes.c_int),
+                ("host_eligible", ctypes.c_int), ("iclass", ctypes.c_int)]
 
 
 def _declare(lib):
@@ -190,6 +197,11 @@ def _declare(lib):
     lib.ddcmi_setup_free.restype = None
     lib.ddcmi_setup_free.argtypes = [ctypes.POINTER(CSetup)]
     lib.ddcmi_setup_sizeof.restype = ctypes.c_int
+    lib.ddcmi_integrator_ntypes.restype = ctypes.c_int
+    lib.ddcmi_integrator_type_find.restype = ctypes.POINTER(CIntegratorType)
+    lib.ddcmi_integrator_type_find.argtypes = [ctypes.c_char_p]
+    lib.ddcmi_integrator_type_names.restype = None
+    lib.ddcmi_integrator_type_names.argtypes = [ctypes.c_char_p, ctypes.c_int]
     lib.units_convert.restype = ctypes.c_double
     lib.units_convert.argtypes = [ctypes.c_double, ctypes.c_char_p, ctypes.c_char_p]
     lib.units_ke.restype = ctypes.c_double

@@ -497,6 +497,70 @@ static int read_atoms(ddcmi_setup *s, const char *basepath, int nfiles_hint, cha
    return 0;
 }
 
+/* The INTEGRATOR types of this path.  integrator.c:37-167 pairs NGLF / NVTGLF with nglf() on the host, NGLFGPU with nglfGPU, NGLFGPULANGEVIN
+ * with nglfGPULangevin (nglfGPU.cu:422-507: isotropic barostat, every bead under group 0's Langevin thermostat), and the four names of the
+ * NGLFCONSTRAINT family (:103-129) with nglfconstraint (nglfconstraint.c:510-574, the GROUP objects' own thermostats, changeVolume whatever
+ * `isotropic` says), nglfconstraintGPU (nglfconstraintGPU.cu:1154-1280: the free kick over every bead) and nglfconstraintGPULangevin /
+ * ...LCG64 (:1282-1546: the Langevin kick over every bead with group 0's tau, kBT and vcm).  The two Langevin names differ in the
+ * reference by where the normals come from (curand against the particles' LCG64 streams); here both draw from what the deck's RANDOM
+ * object selects. */
+const ddcmi_integrator_type ddcmi_integrator_types[] = {
+   /* name                              keys  barostat form         group override          host  itype */
+   {"NGLF",                             0,    DDCMI_BARO_SEMI,      DDCMI_GROUPS_ASIS,      1,    DDCMI_ICLASS_NGLF},
+   {"NVTGLF",                           0,    DDCMI_BARO_SEMI,      DDCMI_GROUPS_ASIS,      1,    DDCMI_ICLASS_NVTGLF},
+   {"NGLFGPU",                          0,    DDCMI_BARO_SEMI,      DDCMI_GROUPS_ASIS,      0,    DDCMI_ICLASS_NGLF},
+   {"NGLFHIP",                          0,    DDCMI_BARO_SEMI,      DDCMI_GROUPS_ASIS,      0,    DDCMI_ICLASS_NGLF},
+   {"NGLFGPULANGEVIN",                  1,    DDCMI_BARO_ISOTROPIC, DDCMI_GROUPS_LANGEVIN0_OWN_VCM, 0, DDCMI_ICLASS_NGLFCONSTRAINT},
+   {"NGLFCONSTRAINT",                   1,    DDCMI_BARO_SEMI,      DDCMI_GROUPS_ASIS,      0,    DDCMI_ICLASS_NGLFCONSTRAINT},
+   {"NGLFCONSTRAINTGPU",                1,    DDCMI_BARO_BY_KEY,    DDCMI_GROUPS_FREE,      0,    DDCMI_ICLASS_NGLFCONSTRAINT},
+   {"NGLFCONSTRAINTGPULANGEVIN",        1,    DDCMI_BARO_BY_KEY,    DDCMI_GROUPS_LANGEVIN0, 0,    DDCMI_ICLASS_NGLFCONSTRAINT},
+   {"NGLFCONSTRAINTGPULANGEVINLCG64",   1,    DDCMI_BARO_BY_KEY,    DDCMI_GROUPS_LANGEVIN0, 0,    DDCMI_ICLASS_NGLFCONSTRAINT},
+};
+int ddcmi_integrator_ntypes(void) { return (int)(sizeof(ddcmi_integrator_types) / sizeof(ddcmi_integrator_types[0])); }
+const ddcmi_integrator_type *ddcmi_integrator_type_find(const char *name)
+{
+   for (int k = 0; name && k < ddcmi_integrator_ntypes(); k++)
+      if (strcmp(name, ddcmi_integrator_types[k].name) == 0) return &ddcmi_integrator_types[k];
+   return NULL;
+}
+void ddcmi_integrator_type_names(char *buf, int len)
+{
+   int at = 0;
+   if (len > 0) buf[0] = 0;
+   for (int k = 0; k < ddcmi_integrator_ntypes() && at < len; k++)
+   {
+      int w = snprintf(buf + at, (size_t)(len - at), "%s%s", k ? ", " : "", ddcmi_integrator_types[k].name);
+      if (w < 0) break;
+      at += w;
+   }
+}
+int ddcmi_integrator_groups(const ddcmi_setup *s, int *type, double *Teq, double *tau, int *interval, double *vcm, char *err, int errlen)
+{
+   const ddcmi_integrator_type *it = ddcmi_integrator_type_find(s->integrator_type);
+   if (!it)
+   {
+      char names[400];
+      ddcmi_integrator_type_names(names, sizeof(names));
+      snprintf(err, errlen, "INTEGRATOR type %s is not on this path (%s are)", s->integrator_type ? s->integrator_type : "?", names);
+      return -1;
+   }
+   const int lang0 = it->group_override == DDCMI_GROUPS_LANGEVIN0 || it->group_override == DDCMI_GROUPS_LANGEVIN0_OWN_VCM;
+   if (lang0 && (s->ngroup < 1 || s->group_type[0] != DDCMI_GROUP_LANGEVIN))
+   {
+      snprintf(err, errlen, "%s needs the first GROUP to be of type LANGEVIN", it->name);
+      return -1;
+   }
+   for (int g = 0; g < s->ngroup; g++)
+   {
+      const int from = lang0 ? 0 : g, vfrom = it->group_override == DDCMI_GROUPS_LANGEVIN0 ? 0 : g;
+      type[g] = it->group_override == DDCMI_GROUPS_FREE ? DDCMI_GROUP_FREE : lang0 ? DDCMI_GROUP_LANGEVIN : s->group_type[g];
+      Teq[g] = s->group_Teq[from]; tau[g] = s->group_tau[from];
+      interval[g] = it->group_override == DDCMI_GROUPS_ASIS ? s->group_interval[g] : 1;
+      for (int c = 0; vcm && c < 3; c++) vcm[3 * g + c] = s->group_vcm ? s->group_vcm[3 * vfrom + c] : 0.0;
+   }
+   return 0;
+}
+
 ddcmi_setup *ddcmi_deck_load(const char *object_file, const char *restart_file, char *err, int errlen)
 {
    return ddcmi_deck_load_with(object_file, restart_file, NULL, err, errlen);
@@ -605,13 +669,22 @@ ddcmi_setup *ddcmi_deck_load_with(const char *object_file, const char *restart_f
       OBJECT *io = object_find(iname, "INTEGRATOR");
       if (!io) FAIL("INTEGRATOR %s not found", iname);
       s->integrator_type = get_string(io, "type", "NGLF");
-      s->npt_isotropic = strcmp(s->integrator_type, "NGLFGPULANGEVIN") == 0;      /* changeVolumeGPUisotropic, molecularPressureGPU.cu:204-239 */
-      if (strcmp(s->integrator_type, "NGLFCONSTRAINT") == 0 || s->npt_isotropic)
+      /* an unknown type loads like a type without keys: integrator_init refuses it by name */
+      const ddcmi_integrator_type *it = ddcmi_integrator_type_find(s->integrator_type);
+      s->group_override = it ? (int)it->group_override : DDCMI_GROUPS_ASIS;
+      if (it && it->barostat_keys)
       {
          object_get(io, "T", &s->npt_T, WITH_UNITS, 1, "310", "T", NULL);
          object_get(io, "P0", &s->npt_P0, WITH_UNITS, 1, "0.0", "pressure", NULL);
          object_get(io, "beta", &s->npt_beta, WITH_UNITS, 1, "0.0", "1/pressure", NULL);
          object_get(io, "tauBarostat", &s->npt_tau, WITH_UNITS, 1, "0.0", "t", NULL);
+      }
+      s->npt_isotropic = it && it->barostat_form == DDCMI_BARO_ISOTROPIC;
+      if (it && it->barostat_form == DDCMI_BARO_BY_KEY)      /* nglfconstraint_parms, nglfconstraint.c:95; its CPU path never reads the value */
+      {
+         int iso = 0;
+         object_get(io, "isotropic", &iso, INT, 1, "0");
+         s->npt_isotropic = iso != 0;
       }
       free(iname);
       char *aname = get_string(sim, "accelerator", "NoAccelerator");

@@ -182,7 +182,39 @@ typedef struct ddcmi_setup
    /* SIMULATE transform = name ... (simulate.c): every TRANSFORM object in the list, in list order */
    int ntransform;
    ddcmi_transform *transform;
+   /* the INTEGRATOR type's group override (its row of ddcmi_integrator_types): DDCMI_GROUPS_ASIS, _FREE, _LANGEVIN0 or _LANGEVIN0_OWN_VCM.  group_type and the
+    * groups' parameters above stay as the deck wrote them; ddcmi_integrator_groups gives the groups as the integrator runs them */
+   int group_override;
 } ddcmi_setup;
+
+/* The INTEGRATOR types of this path (integrator.c:37-167), one row each.  The loader, integrator_init and the refusal of any other type
+ * read this table and nothing else. */
+enum ddcmi_barostat_form { DDCMI_BARO_SEMI = 0,      /* changeVolume / changeVolumeGPU: x and y together, z alone */
+                           DDCMI_BARO_ISOTROPIC,     /* changeVolumeGPUisotropic (molecularPressureGPU.cu:204-239) */
+                           DDCMI_BARO_BY_KEY };      /* the `isotropic` key (INT, default 0) chooses between the two */
+enum ddcmi_group_override { DDCMI_GROUPS_ASIS = 0,   /* every GROUP object's own thermostat */
+                            DDCMI_GROUPS_FREE,       /* every bead gets the free kick (freeVelocityUpdateInterleavedGPU over all beads) */
+                            DDCMI_GROUPS_LANGEVIN0,  /* every bead under group 0's tau, kBT and vcm; group 0 must be LANGEVIN */
+                            DDCMI_GROUPS_LANGEVIN0_OWN_VCM };      /* the same with every group's own vcm: NGLFGPULANGEVIN as this path has always run it */
+enum ddcmi_integrator_class { DDCMI_ICLASS_NGLF = 0, DDCMI_ICLASS_NVTGLF, DDCMI_ICLASS_NGLFCONSTRAINT };      /* the itype integrator_init sets */
+typedef struct ddcmi_integrator_type
+{
+   const char *name;
+   int barostat_keys;                        /* T, P0, beta, tauBarostat are read (nglfconstraint_parms); the constraint lists and the barostat are set up */
+   enum ddcmi_barostat_form barostat_form;
+   enum ddcmi_group_override group_override;
+   int host_eligible;                        /* DDCMI_CPU_INTEGRATOR=1 may run it as nglf() on the host */
+   enum ddcmi_integrator_class iclass;
+} ddcmi_integrator_type;
+extern const ddcmi_integrator_type ddcmi_integrator_types[];
+int ddcmi_integrator_ntypes(void);
+const ddcmi_integrator_type *ddcmi_integrator_type_find(const char *name);      /* NULL: not on this path */
+/* "A, B, ... , Z": the names of the table in its order, for the refusal */
+void ddcmi_integrator_type_names(char *buf, int len);
+/* The groups as the INTEGRATOR type of `s` runs them: type[g] one of DDCMI_GROUP_*, Teq, tau, interval and vcm[3 g ..] per group (each array
+ * ngroup long, vcm 3 ngroup; vcm may be NULL).  Returns 0, or -1 with the refusal in err (an unknown type; an override to group 0's Langevin
+ * thermostat on a deck whose first GROUP is not LANGEVIN) */
+int ddcmi_integrator_groups(const ddcmi_setup *s, int *type, double *Teq, double *tau, int *interval, double *vcm, char *err, int errlen);
 
 /* lcg64_default over n particles in order (lcg64.c:98-110, primes.c:35-63 with prime_init(30000, task, ntasks), ddcMD.c:70) */
 void ddcmi_lcg64_default(int n, const uint64_t *label, unsigned task, unsigned ntasks, uint64_t *state, uint32_t *multID, uint32_t *prime);

@@ -427,49 +427,67 @@ INTEGRATOR *integrator_init(void *parent, const char *name, const char *type)
    INTEGRATOR *in = calloc(1, sizeof(INTEGRATOR));
    in->name = strdup(name); in->type = strdup(type); in->parent = parent;
    const ddcmi_setup *su = parent ? ((SIMULATE *)parent)->setup : NULL;
-   const int gpulang = su && strcmp(type, "NGLFGPULANGEVIN") == 0;
-   const int npt_ok = su && (strcmp(type, "NGLFCONSTRAINT") == 0 || gpulang);
-   if (gpulang)
+   /* the row of deck.c's table of INTEGRATOR types: which keys were read, the barostat's form, what becomes of the GROUP objects'
+    * thermostats, whether nglf() on the host may take the step */
+   const ddcmi_integrator_type *it = ddcmi_integrator_type_find(type);
+   if (!it)
    {
-      /* nglfGPULangevin (nglfGPU.cu:422-507): EVERY bead gets the Langevin update with the parameters of the
-       * first group (:469-473), whatever the GROUP objects say; the barostat is the isotropic one.  The
-       * reference leaves its T/P0/beta/tauBarostat uninitialised (nglf_parms, nglfGPU.cu:41-50): here they
+      char names[400], msg[700];
+      ddcmi_integrator_type_names(names, sizeof(names));
+      snprintf(msg, sizeof(msg), "INTEGRATOR type %s is not on this path (%s are)", type, names);
+      die("integrator_init", msg);
+   }
+   if (su && it->group_override != DDCMI_GROUPS_ASIS)
+   {
+      /* nglfGPULangevin (nglfGPU.cu:422-507) and nglfconstraintGPULangevin (nglfconstraintGPU.cu:1302-1312): EVERY bead gets the Langevin
+       * update with the parameters of the first group, whatever the GROUP objects say; nglfconstraintGPU (:1154-1280): every bead gets the
+       * free kick.  The reference leaves nglfGPULangevin's T/P0/beta/tauBarostat uninitialised (nglf_parms, nglfGPU.cu:41-50): here they
        * are read from the INTEGRATOR object like nglfconstraint_parms does. */
       ddcmi_ctx *ctx = accelerator_getAccelerator(NULL)->parms;
-      if (su->ngroup < 1 || su->group_type[0] != DDCMI_GROUP_LANGEVIN) die("integrator_init", "NGLFGPULANGEVIN needs the first GROUP to be of type LANGEVIN");
-      int gt[32]; double gT[32], gtau[32]; int giv[32];
-      for (int g = 0; g < su->ngroup && g < 32; g++) { gt[g] = DDCMI_LANGEVIN; gT[g] = su->group_Teq[0]; gtau[g] = su->group_tau[0]; giv[g] = 1; }
-      if (ddcmi_set_groups(ctx, su->ngroup, gt, gT, gtau, giv) != DDCMI_OK || ddcmi_set_barostat_isotropic(ctx, 1) != DDCMI_OK) die("integrator_init", ddcmi_last_error(ctx));
-   }
-   if (npt_ok || strcmp(type, "NGLF") == 0 || strcmp(type, "NVTGLF") == 0 || strcmp(type, "NGLFGPU") == 0 || strcmp(type, "NGLFHIP") == 0)
-   {
-      /* NGLFCONSTRAINT = nglf + velocity constraints + the barostat of changeVolume (nglfconstraint.c:510-574) */
-      if (npt_ok) nglfconstraintHIP_parms(accelerator_getAccelerator(NULL)->parms, su);
-      in->itype = npt_ok ? NGLFCONSTRAINT : (strcmp(type, "NVTGLF") == 0 ? NVTGLF : NGLF);
-      in->eval_integrator = (void (*)(void *, void *, void *))nglfHIP;
-      in->uses_gpu = 1;                                    /* state stays on the device between print steps (masters.c:389-403) */
-      const char *cpu = getenv("DDCMI_CPU_INTEGRATOR");
-      if (cpu && atoi(cpu) != 0 && (strcmp(type, "NGLF") == 0 || strcmp(type, "NVTGLF") == 0))
+      int gt[32], giv[32]; double gT[32], gtau[32], gvcm[96]; char msg[400];
+      if (su->ngroup > 32) die("integrator_init", "more than 32 GROUP objects");
+      if (ddcmi_integrator_groups(su, gt, gT, gtau, giv, gvcm, msg, sizeof(msg)) != 0) die("integrator_init", msg);
+      for (int g = 0; g < su->ngroup; g++) gt[g] = gt[g] == DDCMI_GROUP_LANGEVIN ? DDCMI_LANGEVIN : DDCMI_FREE;
+      if (ddcmi_set_groups(ctx, su->ngroup, gt, gT, gtau, giv) != DDCMI_OK) die("integrator_init", ddcmi_last_error(ctx));
+      if (it->group_override != DDCMI_GROUPS_LANGEVIN0_OWN_VCM)
       {
-         /* the reference's own pairing for these type strings (integrator.c:59-64): nglf() on the host, the
-          * potential on the accelerator.  The default keeps the whole step on the device. */
-         for (int g = 0; g < su->ngroup; g++)      /* refused here, before any output file is opened: nglf() below kicks FREE and BERENDSEN groups only */
-            if (su->group_type[g] != DDCMI_GROUP_FREE && su->group_type[g] != DDCMI_GROUP_BERENDSEN)
-            {
-               char msg[400];
-               snprintf(msg, sizeof(msg), "GROUP %s: the host integrator (DDCMI_CPU_INTEGRATOR=1) handles FREE and BERENDSEN groups only: LANGEVIN, FROZEN, FIXEDVELOCITY and QUENCH groups run on the device integrator", su->group_name[g]);
-               die("integrator_init", msg);
-            }
-         in->eval_integrator = (void (*)(void *, void *, void *))nglf;
-         in->uses_gpu = 0;
-         printf("INTEGRATOR %s on the host (nglf.c), potential on the accelerator\n", type);
+         /* the reference overrides silently; a deck's owner is told once which of its GROUP objects do not run as written */
+         static const char *kind[] = {"FREE", "BERENDSEN", "LANGEVIN", "of another type", "FROZEN", "FIXEDVELOCITY", "QUENCH", "EXTFORCE"};
+         const int lang = it->group_override == DDCMI_GROUPS_LANGEVIN0;
+         if (lang && ddcmi_set_group_vcm(ctx, su->ngroup, gvcm) != DDCMI_OK) die("integrator_init", ddcmi_last_error(ctx));
+         for (int g = 0; g < su->ngroup && par.rank == 0; g++)
+         {
+            const int t = su->group_type[g];
+            int same = t == (lang ? DDCMI_GROUP_LANGEVIN : DDCMI_GROUP_FREE);
+            if (lang && same) same = su->group_Teq[g] == su->group_Teq[0] && su->group_tau[g] == su->group_tau[0] && (!su->group_vcm || memcmp(&su->group_vcm[3 * g], su->group_vcm, 3 * sizeof(double)) == 0);
+            if (same) continue;
+            if (lang) fprintf(stderr, "ddcmi_md: INTEGRATOR type %s: GROUP %s (%s) runs as LANGEVIN with the Teq, tau and vcm of GROUP %s\n", type, su->group_name[g], kind[t & 7], su->group_name[0]);
+            else fprintf(stderr, "ddcmi_md: INTEGRATOR type %s: GROUP %s (%s) runs as FREE\n", type, su->group_name[g], kind[t & 7]);
+         }
       }
    }
-   else
+   if (su && it->barostat_keys && su->npt_isotropic && ddcmi_set_barostat_isotropic(accelerator_getAccelerator(NULL)->parms, 1) != DDCMI_OK)
+      die("integrator_init", ddcmi_last_error(accelerator_getAccelerator(NULL)->parms));
+   /* NGLFCONSTRAINT = nglf + velocity constraints + the barostat of changeVolume (nglfconstraint.c:510-574) */
+   if (su && it->barostat_keys) nglfconstraintHIP_parms(accelerator_getAccelerator(NULL)->parms, su);
+   in->itype = it->iclass == DDCMI_ICLASS_NGLFCONSTRAINT ? NGLFCONSTRAINT : (it->iclass == DDCMI_ICLASS_NVTGLF ? NVTGLF : NGLF);
+   in->eval_integrator = (void (*)(void *, void *, void *))nglfHIP;
+   in->uses_gpu = 1;                                    /* state stays on the device between print steps (masters.c:389-403) */
+   const char *cpu = getenv("DDCMI_CPU_INTEGRATOR");
+   if (cpu && atoi(cpu) != 0 && it->host_eligible)
    {
-      char msg[256];
-      snprintf(msg, sizeof(msg), "INTEGRATOR type %s is not on this path (NGLF, NVTGLF, NGLFGPU, NGLFHIP, NGLFGPULANGEVIN, NGLFCONSTRAINT are)", type);
-      die("integrator_init", msg);
+      /* the reference's own pairing for these type strings (integrator.c:59-64): nglf() on the host, the
+       * potential on the accelerator.  The default keeps the whole step on the device. */
+      for (int g = 0; g < su->ngroup; g++)      /* refused here, before any output file is opened: nglf() below kicks FREE and BERENDSEN groups only */
+         if (su->group_type[g] != DDCMI_GROUP_FREE && su->group_type[g] != DDCMI_GROUP_BERENDSEN)
+         {
+            char msg[400];
+            snprintf(msg, sizeof(msg), "GROUP %s: the host integrator (DDCMI_CPU_INTEGRATOR=1) handles FREE and BERENDSEN groups only: LANGEVIN, FROZEN, FIXEDVELOCITY and QUENCH groups run on the device integrator", su->group_name[g]);
+            die("integrator_init", msg);
+         }
+      in->eval_integrator = (void (*)(void *, void *, void *))nglf;
+      in->uses_gpu = 0;
+      printf("INTEGRATOR %s on the host (nglf.c), potential on the accelerator\n", type);
    }
    return in;
 }

@@ -87,6 +87,8 @@ static int eval_expr(const char *s, double *factor, int dim[NDIM])
             if (strcmp(sym, dimnames[d]) == 0) { f = external_si[d]; dm[d] = 1; found = 1; }
          if (!found && strcmp(sym, "velocity") == 0)      /* the external velocity, l/t (velocityAutocorrelation.c:258 asks for velocity^2) */
          { f = external_si[0] / external_si[2]; dm[0] = 1; dm[2] = -1; found = 1; }
+         if (!found && strcmp(sym, "pressure") == 0)      /* the external pressure, m/l/t^2: the default unit of P0 and, as 1/pressure, of beta (nglfconstraint.c:91-92) */
+         { f = external_si[1] / (external_si[0] * external_si[2] * external_si[2]); dm[0] = -1; dm[1] = 1; dm[2] = -2; found = 1; }
          if (!found)
             for (const unit_symbol *u = table; u->name; u++)
                if (strcmp(sym, u->name) == 0) { f = u->si; memcpy(dm, u->dim, sizeof(dm)); found = 1; break; }

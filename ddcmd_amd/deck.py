@@ -11,6 +11,11 @@ _INT_ARRAYS_SPECIES = ("ljtype", "moltype", "resitype", "atomoffset")
 GROUP_FREE, GROUP_BERENDSEN, GROUP_LANGEVIN, GROUP_OTHER = 0, 1, 2, 3
 GROUP_FROZEN, GROUP_FIXEDVELOCITY, GROUP_QUENCH = 4, 5, 6      # include/ddcmi.h's kinds; 3 stays refused
 GROUP_EXTFORCE = 7      # read by the loader (group_Fz); the device has no such kind yet: MartiniHIP refuses it by name
+# what the INTEGRATOR type makes of the GROUP objects' thermostats (deck.h, enum ddcmi_group_override): as they are; every bead FREE
+# (NGLFCONSTRAINTGPU); every bead under group 0's Langevin thermostat (NGLFCONSTRAINTGPULANGEVIN[LCG64]); the same with each group's own
+# vcm (NGLFGPULANGEVIN)
+GROUPS_ASIS, GROUPS_FREE, GROUPS_LANGEVIN0, GROUPS_LANGEVIN0_OWN_VCM = 0, 1, 2, 3
+BARO_SEMI, BARO_ISOTROPIC, BARO_BY_KEY = 0, 1, 2
 
 
 class Setup(object):
@@ -77,6 +82,7 @@ class Setup(object):
         self.lcg_from_file = 0
         self.npt_T = self.npt_P0 = self.npt_beta = self.npt_tau = 0.0
         self.npt_isotropic = 0
+        self.group_override = GROUPS_ASIS      # load_deck: the override of the INTEGRATOR type's row; martini.integrator_plan reads the type itself
         self.nresicons = 0
         self.nrest, self.rest_origin = 0, 0
         self.rest_gid = np.zeros(0, np.uint64)
@@ -127,6 +133,7 @@ def load_deck(object_file, restart_file=None, extra_objects=None):
             s.lcg_from_file = int(c.lcg_from_file)
         s.npt_T, s.npt_P0, s.npt_beta, s.npt_tau = float(c.npt_T), float(c.npt_P0), float(c.npt_beta), float(c.npt_tau)
         s.npt_isotropic = int(c.npt_isotropic)
+        s.group_override = int(c.group_override)
         s.nresicons = int(c.nresicons)
         s.nrest, s.rest_origin = int(c.nrest), int(c.rest_origin)
         s.rest_gid = _arr(c.rest_gid, s.nrest, np.uint64) if s.nrest else np.zeros(0, np.uint64)
@@ -234,6 +241,20 @@ def load_deck(object_file, restart_file=None, extra_objects=None):
     finally:
         lib.ddcmi_setup_free(p)
     return s
+
+
+def integrator_types():
+    """The table of INTEGRATOR types of this path (deck.c), in its order: one dict per row -- name, barostat_keys (T, P0, beta, tauBarostat
+    are read), barostat_form (BARO_*), group_override (GROUPS_*), host_eligible"""
+    lib = _lib.load_library()
+    buf = ctypes.create_string_buffer(1024)
+    lib.ddcmi_integrator_type_names(buf, 1024)
+    rows = []
+    for name in buf.value.decode().split(", "):
+        r = lib.ddcmi_integrator_type_find(name.encode()).contents
+        rows.append({"name": name, "barostat_keys": bool(r.barostat_keys), "barostat_form": int(r.barostat_form),
+                     "group_override": int(r.group_override), "host_eligible": bool(r.host_eligible)})
+    return rows
 
 
 def units_convert(value, frm=None, to=None):

@@ -515,10 +515,49 @@ def molecule_lists(s):
     return int(first.size), mol_off, np.ascontiguousarray(order[sel], dtype=np.int32)
 
 
+def integrator_plan(s):
+    """What the INTEGRATOR type of a Setup makes of its groups, constraints and barostat -- the driver's integrator_init, from the same
+    table of types (deck.c).  Returns a dict: group_type / group_Teq / group_tau / group_interval / group_vcm as the integrator runs them
+    (NGLFCONSTRAINTGPU: every group FREE; NGLFCONSTRAINTGPULANGEVIN[LCG64]: every group LANGEVIN with group 0's Teq, tau and vcm;
+    NGLFGPULANGEVIN: the same with each group's own vcm), overridden (the groups whose deck type or parameters do not run as written),
+    constraints (the type sets up the residues' constraint lists and the Setup has some), isotropic (the barostat's form).  A type that is
+    not in the table, or group 0's thermostat asked for where group 0 is not LANGEVIN, raises DdcmiError by name."""
+    from . import deck
+    rows = {r["name"]: r for r in deck.integrator_types()}
+    name = str(getattr(s, "integrator_type", "NGLF"))
+    if name not in rows:
+        raise DdcmiError("INTEGRATOR type %s is not on this path (%s are)" % (name, ", ".join(rows)))
+    row = rows[name]
+    ov, ng = row["group_override"], int(s.ngroup)
+    gt = np.array(s.group_type, dtype=np.int32)
+    Teq, tau = np.array(s.group_Teq, dtype=np.float64), np.array(s.group_tau, dtype=np.float64)
+    iv = np.array(s.group_interval, dtype=np.int32)
+    vcm = getattr(s, "group_vcm", None)
+    vcm = np.zeros((ng, 3)) if vcm is None or np.size(vcm) != 3 * ng else np.array(vcm, dtype=np.float64).reshape(ng, 3)
+    written = (gt.copy(), Teq.copy(), tau.copy(), vcm.copy())
+    if ov in (deck.GROUPS_LANGEVIN0, deck.GROUPS_LANGEVIN0_OWN_VCM):
+        if ng < 1 or int(gt[0]) != deck.GROUP_LANGEVIN:
+            raise DdcmiError("%s needs the first GROUP to be of type LANGEVIN" % name)
+        gt[:], Teq[:], tau[:], iv[:] = deck.GROUP_LANGEVIN, Teq[0], tau[0], 1
+        if ov == deck.GROUPS_LANGEVIN0:
+            vcm[:] = vcm[0]
+    elif ov == deck.GROUPS_FREE:
+        gt[:], iv[:] = deck.GROUP_FREE, 1
+    if ov == deck.GROUPS_FREE:
+        changed = written[0] != gt
+    else:
+        changed = (written[0] != gt) | (written[1] != Teq) | (written[2] != tau) | np.any(written[3] != vcm, axis=1)
+    iso = bool(getattr(s, "npt_isotropic", 0))      # the loader has applied the row's barostat form (and the `isotropic` key where the row reads it)
+    return {"type": name, "group_override": ov, "group_type": gt, "group_Teq": Teq, "group_tau": tau, "group_interval": iv, "group_vcm": vcm.ravel(),
+            "overridden": [int(g) for g in np.flatnonzero(changed)],
+            "constraints": bool(row["barostat_keys"]) and int(getattr(s, "nresicons", 0)) > 0, "isotropic": iso}
+
+
 class MartiniHIP(object):
     """One device context running the Martini hot path for a Setup."""
 
-    def __init__(self, setup, device=0, upload=True, bonded_by_gid=False, constraints=False, test_api=False, constraint_groups=None):
+    def __init__(self, setup, device=0, upload=True, bonded_by_gid=False, constraints=None, test_api=False, constraint_groups=None):
+        # constraints: None -- as the driver does: the INTEGRATOR types that read the barostat keys set up the residues' constraint lists
         # constraint_groups: (pair_off, pairI, pairJ, dist) over caller-order atom indices, in place of expand_constraints(setup)
         # test_api: the context lives in libddcmi_test.so (same objects + the entry points of include/ddcmi_test.h)
         self.lib = _lib.load_test_library() if test_api else _lib.load_library()
@@ -560,12 +599,15 @@ class MartiniHIP(object):
                                                 nt, _i(t["tors_ijkl"]), _i(t["tors_func"]), _i(t["tors_n"]), _d(t["tors_k"]), _d(t["tors_delta"]),
                                                 int(s.excludePotentialTerm)))
         self._chk(self.lib.ddcmi_set_neighbor(self.ctx, s.deltaR, int(s.updateRate)))
-        gt = i32(s.group_type)      # FREE / BERENDSEN / LANGEVIN / FROZEN / FIXEDVELOCITY / QUENCH: as they are
+        plan = self.plan = integrator_plan(s)      # the INTEGRATOR type's row: NGLFCONSTRAINTGPU and the ...LANGEVIN types override the groups
+        if constraints is None:
+            constraints = plan["constraints"]
+        gt = i32(plan["group_type"])      # FREE / BERENDSEN / LANGEVIN / FROZEN / FIXEDVELOCITY / QUENCH: as they are, unless the type overrides them
         if np.any((gt == 3) | (gt == 7)):         # EXTFORCE (7: read by the loader, not built on the device) and any other GROUP type of a deck: never run as FREE
             raise DdcmiError("GROUP %s: its type (EXTFORCE or another) is none of FREE, BERENDSEN, LANGEVIN, FROZEN, FIXEDVELOCITY, QUENCH"
                              % ", ".join(str(s.group_name[g]) if g < len(s.group_name) else str(g) for g in np.flatnonzero((gt == 3) | (gt == 7))))
-        self._chk(self.lib.ddcmi_set_groups(self.ctx, s.ngroup, _i(gt), _d(f64(s.group_Teq)), _d(f64(s.group_tau)), _i(i32(s.group_interval))))
-        vcm = getattr(s, "group_vcm", None)
+        self._chk(self.lib.ddcmi_set_groups(self.ctx, s.ngroup, _i(gt), _d(f64(plan["group_Teq"])), _d(f64(plan["group_tau"])), _i(i32(plan["group_interval"]))))
+        vcm = plan["group_vcm"] if getattr(s, "group_vcm", None) is not None else None
         if vcm is not None and np.any(np.asarray(vcm) != 0.0):      # LANGEVIN groups: the velocity the friction relaxes towards (langevin.c:167)
             self._vcm = f64(np.ravel(vcm))
             self._chk(self.lib.ddcmi_set_group_vcm(self.ctx, s.ngroup, _d(self._vcm)))
@@ -573,7 +615,7 @@ class MartiniHIP(object):
             self.set_group_velocity(s.group_vset, s.group_v)
         self._chk(self.lib.ddcmi_set_random(self.ctx, int(getattr(s, "rng_seed", 0))))
         if float(getattr(s, "npt_beta", 0.0)) > 0.0:      # INTEGRATOR type=NGLFCONSTRAINT: barostat on the molecular pressure
-            self.set_barostat(float(s.npt_T), float(s.npt_P0), float(s.npt_beta), float(s.npt_tau), isotropic=bool(getattr(s, "npt_isotropic", 0)),
+            self.set_barostat(float(s.npt_T), float(s.npt_P0), float(s.npt_beta), float(s.npt_tau), isotropic=plan["isotropic"],
                               by_gid=bonded_by_gid)
         if constraints or constraint_groups is not None:  # INTEGRATOR type=NGLFCONSTRAINT: velocity constraints
             if constraint_groups is None:
@@ -636,7 +678,7 @@ class MartiniHIP(object):
         self._chk(self.lib.ddcmi_upload_state(self.ctx, self.n, _d(a[0]), _d(a[1]), _d(a[2]), _d(v[0]), _d(v[1]), _d(v[2]),
                                               gid.ctypes.data_as(_up), _i(sp), _i(gr)))
         lcg = getattr(s, "lcg64", None)
-        if lcg is not None and type(self) is MartiniHIP and len(lcg) == self.n and np.any(np.asarray(s.group_type) == 2):
+        if lcg is not None and type(self) is MartiniHIP and len(lcg) == self.n and np.any(np.asarray(self.plan["group_type"]) == 2):
             self.set_random_lcg64(lcg)      # RANDOM type=LCG64 in the deck: the Langevin groups of a one-domain run draw from the particles' own streams
 
     def build_list(self):
@@ -1049,7 +1091,7 @@ class DomainMixin(object):
 class MartiniRank(MartiniHIP, DomainMixin):
     """One rank of a decomposed run: uploads only the beads `index` selects."""
 
-    def __init__(self, setup, index, device=0, constraints=False, test_api=False, constraint_groups=None):
+    def __init__(self, setup, index, device=0, constraints=None, test_api=False, constraint_groups=None):
         MartiniHIP.__init__(self, setup, device=device, upload=False, bonded_by_gid=True, constraints=constraints, test_api=test_api,
                             constraint_groups=constraint_groups)
         self.index = np.asarray(index)
@@ -1065,7 +1107,7 @@ class MartiniRank(MartiniHIP, DomainMixin):
         self._chk(self.lib.ddcmi_upload_state(self.ctx, self.n, _d(a[0]), _d(a[1]), _d(a[2]), _d(a[3]), _d(a[4]), _d(a[5]),
                                               gid.ctypes.data_as(_up), _i(sp), _i(gr)))
         lcg = getattr(s, "lcg64", None)
-        if lcg is not None and self.n > 0 and np.any(np.asarray(s.group_type) == 2):
+        if lcg is not None and self.n > 0 and np.any(np.asarray(self.plan["group_type"]) == 2):
             self.set_random_lcg64(lcg[ix])      # the records migrate with their beads from here on
 
     def comm_init(self, rank, nranks, uid, grid):
@@ -1101,7 +1143,7 @@ class MartiniGroup(object):
     """px*py*pz domains emulated inside one process on one GPU (device copies
     instead of RCCL): exercises migration, halo tables and per-step halo refresh."""
 
-    def __init__(self, setup, grid, device=0, constraints=False, constraint_groups=None):
+    def __init__(self, setup, grid, device=0, constraints=None, constraint_groups=None):
         self.s = setup
         self.grid = tuple(grid)
         self.n = grid[0] * grid[1] * grid[2]
