@@ -14,7 +14,7 @@
  * The per-bead arithmetic is the reference's, operation by operation, with every product kept from contraction into an FMA
  * (zd_rounded: the library is built with -ffp-contract=fast), so that a float64 restatement on the host lands in the same bin at an edge.  The position is the
  * one ddcmi_download_state hands out: slot position, shifted once by the box side where it left a periodic box since the last
- * rebuild (k_export_pos); the reference bins its positions as they are, and so does this -- no further wrap.  A coordinate outside
+ * rebuild (export_coord); the reference bins its positions as they are, and so does this -- no further wrap.  A coordinate outside
  * the box reaches the reference's clamp: a label read as unsigned that is >= nz goes to nz - 1 (negative t below -1 included;
  * -1 < t < 0 truncates to bin 0).  The conversion to int saturates at +-2^30 (C leaves it undefined there), NaN goes to -2^30. */
 
@@ -48,8 +48,7 @@ __device__ __forceinline__ double zd_rounded(double x) { asm volatile("" : "+v"(
 /* r.z of zdensity.c:90 from the slot's z */
 __device__ __forceinline__ double zd_t(const ZdParms &zp, double z)
 {
-   if (zp.wrap) { if (z > 0.5 * zp.L) z -= zp.L; if (z < -0.5 * zp.L) z += zp.L; }      /* k_export_pos */
-   const double a = zd_rounded(z * zp.deltai);
+   const double a = zd_rounded(export_coord(z, zp.L, zp.wrap) * zp.deltai);
    return a - zp.scaled_corner;
 }
 /* zdensity.c:105-133: the two bins and weights of a smeared bead */
@@ -138,11 +137,7 @@ static int census_zdensity_check(ddcmi_ctx *ctx, const char *fn, int nz, int sme
    ARGCHK(ctx, nz < 1, "%s: nz = %d", fn, nz);
    ARGCHK(ctx, smear_method != 0 && smear_method != 1, "%s: smear_method = %d (0 impulse, 1 hat)", fn, smear_method);
    if (nz > CENSUS_MAX_NZ) SETERR(ctx, DDCMI_EUNSUPPORTED, "%s: nz = %d, at most %d", fn, nz, CENSUS_MAX_NZ);
-   const int off[6] = {1, 2, 3, 5, 6, 7};
-   for (int k = 0; k < 6; k++)
-      if (fabs(ctx->h[off[k]]) > 1e-10) SETERR(ctx, DDCMI_EUNSUPPORTED, "%s: only orthorhombic boxes are supported (h[%d]=%g)", fn, off[k], ctx->h[off[k]]);
-   if (!(ctx->h[8] > 0.0)) SETERR(ctx, DDCMI_EINVAL, "%s needs a box (ddcmi_set_box)", fn);
-   return DDCMI_OK;
+   return census_box_check(ctx, fn, 4);
 }
 /* this rank's sums [sync] */
 static int census_momentum_one(ddcmi_ctx *ctx, double *mv, double *m)
@@ -157,40 +152,33 @@ static int census_momentum_one(ddcmi_ctx *ctx, double *mv, double *m)
 static int census_zdensity_one(ddcmi_ctx *ctx, int nz, double smear_radius, int smear_method, double *density)
 {
    (void)hipSetDevice(ctx->device);
-   hipStream_t st = ctx->stream;
    const int n = ctx->nloc;
    if (n <= 0) { for (int k = 0; k < nz; k++) density[k] = 0.0; return DDCMI_OK; }      /* (a domain that holds no bead) */
    const bool smear = smear_radius > 0.0;
    ZdParms zp;
    zp.nz = nz; zp.method = smear_method; zp.wrap = (ctx->pbc >> 2) & 1;
-   zp.L = ctx->h[8];
+   const double L = zp.L = ctx->h[8];
    const double corner = ctx->h[8] * -0.5;      /* box->corner = h0 * reducedcorner (box.c:69), reducedcorner = -0.5 on this path */
-   zp.deltai = nz / zp.L;
+   zp.deltai = nz / L;
    zp.scaled_corner = corner * zp.deltai;
    zp.half = zp.inv = 0.0;
    if (smear)
    {
-      const double a = 2.0 * smear_radius, b = zp.L / (1.0 * nz), lSmear = a < b ? a : b;
+      const double a = 2.0 * smear_radius, b = L / (1.0 * nz), lSmear = a < b ? a : b;
       zp.inv = 1.0 / lSmear; zp.half = 0.5 * lSmear;
    }
    int per_wg, nwg;
    census_split(n, CENSUS_MAX_WG, &per_wg, &nwg);
-   ENSURE(ctx, ctx->census_part, (size_t)(nwg + 1) * nz);      /* (the counts' 32-bit partials take half of the room) */
-   double *d_out = ctx->census_part.p + (size_t)nwg * nz;
+   CensusScratch cs;      /* (the counts' 32-bit partials take half of the room) */
+   const int part = cs.seg(8, (size_t)nwg * nz), out = cs.seg(8, nz);
+   int rc = cs.ensure(ctx);
+   if (rc) return rc;
+   double *d_part = cs.at<double>(part), *d_out = cs.at<double>(out);
    if (smear)
-   {
-      hipLaunchKernelGGL(k_census_zdensity<true>, dim3(nwg), dim3(CENSUS_THREADS), (size_t)CENSUS_WAVES * nz * sizeof(double), st, n, per_wg, zp, ctx->pos.p, (void *)ctx->census_part.p);
-      hipLaunchKernelGGL((k_census_final<RowsSum, double>), dim3(cdiv(nz, 64)), dim3(64), 0, st, nwg, nz, ctx->census_part.p, d_out, 0, nullptr, nullptr);
-   }
+      hipLaunchKernelGGL(k_census_zdensity<true>, dim3(nwg), dim3(CENSUS_THREADS), (size_t)CENSUS_WAVES * nz * sizeof(double), ctx->stream, n, per_wg, zp, ctx->pos.p, (void *)d_part);
    else
-   {
-      hipLaunchKernelGGL(k_census_zdensity<false>, dim3(nwg), dim3(CENSUS_THREADS), (size_t)nz * sizeof(unsigned), st, n, per_wg, zp, ctx->pos.p, (void *)ctx->census_part.p);
-      hipLaunchKernelGGL((k_census_final<RowsSum, double>), dim3(cdiv(nz, 64)), dim3(64), 0, st, nwg, 0, nullptr, nullptr, nz, (const unsigned *)ctx->census_part.p, d_out);
-   }
-   HIPCHK(ctx, hipGetLastError());
-   HIPCHK(ctx, hipMemcpyAsync(density, d_out, (size_t)nz * sizeof(double), hipMemcpyDeviceToHost, st));
-   HIPCHK(ctx, hipStreamSynchronize(st));
-   return DDCMI_OK;
+      hipLaunchKernelGGL(k_census_zdensity<false>, dim3(nwg), dim3(CENSUS_THREADS), (size_t)nz * sizeof(unsigned), ctx->stream, n, per_wg, zp, ctx->pos.p, (void *)d_part);
+   return census_finish<RowsSum, double>(ctx, nwg, smear ? nz : 0, d_part, d_out, density, smear ? 0 : nz, (const unsigned *)d_part, d_out, density);
 }
 
 extern "C" int ddcmi_momentum_by_class(ddcmi_ctx *ctx, int ngroup, int nspecies, double *mv, double *m)

@@ -9,8 +9,8 @@
  * finishes on the host with the lane's own arithmetic (host/chol_math.h, shared with host/chol.c).
  *
  *   k_chol_gather   over the owned beads.  A bead whose gid lies outside [least, greatest listed gid] is skipped (the prefilter: the
- *                   C-ABI names beads by gid alone, so the host cannot tell their species); the others binary-search the ascending
- *                   listed gids (subset_in_list's search); a hit writes the wrapped position to table[mol][role] and a byte to
+ *                   C-ABI names beads by gid alone, so the host cannot tell their species); the others search the ascending
+ *                   listed gids (gid_in_range, gid_find); a hit writes the wrapped position to table[mol][role] and a byte to
  *                   present[mol][role].  Every (mol, role) has one writer -- a gid is listed once and owned once -- so no atomics;
  *                   both arrays are zeroed on the stream first.
  *   k_chol_eval     one lane per molecule, census_split over the molecules.  Seven present: dR1, dR5 (chol_offsets_of), their bins
@@ -18,9 +18,8 @@
  *                   into the wave's LDS row, rows and workgroups combined by RowsSumMinMax / k_census_final.  One to six present:
  *                   split[mol] = 1.  None: nothing.  A NaN offset (collinear beads) goes to bin 0, joins the sum and enters
  *                   neither extreme, as the reference's macros and comparisons have it.
- *   k_chol_frag_count, ddcmi_scan_exclusive, k_chol_frag_pack
- *                   the present (mol, role) of split molecules, compacted stably in (mol, role) order: ballot and popcount per
- *                   wave, the scan over the workgroups' counts, 32-byte records.
+ *   the fragments   the present (mol, role) of split molecules through the frame's compaction (CholFragSel): stable in (mol, role)
+ *                   order, 32-byte records.
  * LDS of k_chol_eval: CENSUS_WAVES x 6 doubles, then 2 nbins + 1 counters (the last one counts the molecules done):
  * DDCMI_CHOL_LDS_BYTES(nbins) <= DDCMI_CHOL_MAX_LDS, i.e. nbins <= 8167. */
 
@@ -39,21 +38,12 @@ __global__ __launch_bounds__(256) void k_chol_gather(int n, CholParms cp, unsign
    const int i = blockIdx.x * 256 + threadIdx.x;
    if (i >= n) return;
    const unsigned long long g = gid[i];
-   if (g < gmin || g > gmax) return;
-   int lo = 0, hi = nl;      /* the first entry >= g */
-   while (lo < hi)
-   {
-      const int mid = lo + ((hi - lo) >> 1);
-      if (ids[mid] < g) lo = mid + 1; else hi = mid;
-   }
-   if (lo >= nl || ids[lo] != g) return;
-   const int slot = perm[lo];
+   int at;
+   if (!gid_in_range(g, gmin, gmax) || !gid_find(ids, 0, nl, g, &at)) return;
+   const int slot = perm[at];
    if (slot < 0 || slot >= nl) return;      /* (the host's permutation: the stores stay in bounds whatever it holds) */
-   const double4 p4 = pos[i];
-   double r[3] = {p4.x, p4.y, p4.z};
-#pragma unroll
-   for (int a = 0; a < 3; a++)
-      if (cp.pbc >> a & 1) { if (r[a] > 0.5 * cp.L[a]) r[a] -= cp.L[a]; if (r[a] < -0.5 * cp.L[a]) r[a] += cp.L[a]; }      /* k_export_particles */
+   double r[3];
+   census_position(cp, pos[i], r);
    table[3 * (size_t)slot] = r[0]; table[3 * (size_t)slot + 1] = r[1]; table[3 * (size_t)slot + 2] = r[2];
    present[slot] = 1;
 }
@@ -125,61 +115,22 @@ __global__ __launch_bounds__(CENSUS_THREADS) void k_chol_eval(int nmol, int per_
    for (int k = threadIdx.x; k < nslot; k += CENSUS_THREADS) out_c[k] = cnt_s[k];
 }
 
-__device__ __forceinline__ bool chol_frag_selected(int s, int nl, const unsigned char *present, const unsigned char *split)
+/* the compaction's functor (k_compact_count, k_compact_pack) over the 7 nmol (mol, role) slots: the present ones of split molecules;
+ * rec: nrec records of four 8-byte words {mol | role << 32, r[0], r[1], r[2]} (struct ddcmi_chol_fragment) */
+struct CholFragSel
 {
-   return s < nl && present[s] != 0 && split[s / 7] != 0;
-}
-/* over the 7 nmol (mol, role) slots: a workgroup's count of the fragments in its census_split range */
-__global__ __launch_bounds__(CENSUS_THREADS) void k_chol_frag_count(int nl, int per_wg, const unsigned char *__restrict__ present,
-                                                                    const unsigned char *__restrict__ split, int *__restrict__ wg_count)
-{
-   __shared__ unsigned wave_s[CENSUS_WAVES];
-   const int beg = blockIdx.x * per_wg, end = min(nl, beg + per_wg);
-   unsigned mine = 0u;      /* the wave's count: the same in all its lanes */
-   for (int base = beg; base < end; base += CENSUS_THREADS)      /* (uniform trip count: every lane reaches the ballot) */
-      mine += (unsigned)__popcll(__ballot(chol_frag_selected(base + (int)threadIdx.x, end, present, split)));
-   if ((threadIdx.x & 63) == 0) wave_s[threadIdx.x >> 6] = mine;
-   __syncthreads();
-   if (threadIdx.x == 0)
+   const unsigned char *present, *split; const double *table; unsigned long long *rec;
+   struct Item {};
+   __device__ __forceinline__ bool selected(int s, Item &) const { return present[s] != 0 && split[s / 7] != 0; }
+   __device__ __forceinline__ void store(int s, unsigned place, const Item &) const
    {
-      unsigned t = 0u;
-#pragma unroll
-      for (int w = 0; w < CENSUS_WAVES; w++) t += wave_s[w];
-      wg_count[blockIdx.x] = (int)t;
+      unsigned long long *o = rec + 4 * (size_t)place;
+      o[0] = (unsigned long long)(unsigned)(s / 7) | (unsigned long long)(unsigned)(s % 7) << 32;
+      o[1] = (unsigned long long)__double_as_longlong(table[3 * (size_t)s]);
+      o[2] = (unsigned long long)__double_as_longlong(table[3 * (size_t)s + 1]);
+      o[3] = (unsigned long long)__double_as_longlong(table[3 * (size_t)s + 2]);
    }
-}
-/* rec: nrec records of four 8-byte words {mol | role << 32, r[0], r[1], r[2]} (struct ddcmi_chol_fragment) */
-__global__ __launch_bounds__(CENSUS_THREADS) void k_chol_frag_pack(int nl, int per_wg, const unsigned char *__restrict__ present, const unsigned char *__restrict__ split,
-                                                                   const double *__restrict__ table, const int *__restrict__ wg_off, unsigned nrec,
-                                                                   unsigned long long *__restrict__ rec)
-{
-   __shared__ unsigned wave_s[2][CENSUS_WAVES];      /* the waves' counts of this block of slots and of the next: one barrier per block */
-   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-   const int beg = blockIdx.x * per_wg, end = min(nl, beg + per_wg);
-   unsigned run = (unsigned)wg_off[blockIdx.x];
-   int par = 0;
-   for (int base = beg; base < end; base += CENSUS_THREADS, par ^= 1)      /* (uniform trip count) */
-   {
-      const int s = base + (int)threadIdx.x;
-      const bool sel = chol_frag_selected(s, end, present, split);
-      const unsigned long long same = __ballot(sel);
-      if (lane == 0) wave_s[par][wave] = (unsigned)__popcll(same);
-      __syncthreads();
-      unsigned before = 0u, all = 0u;
-#pragma unroll
-      for (int w = 0; w < CENSUS_WAVES; w++) { const unsigned c = wave_s[par][w]; all += c; if (w < wave) before += c; }
-      const unsigned place = run + before + (unsigned)__popcll(same & ((1ull << lane) - 1ull));
-      if (sel && place < nrec)      /* (place < nrec whenever the bytes are the ones k_chol_frag_count saw) */
-      {
-         unsigned long long *o = rec + 4 * (size_t)place;
-         o[0] = (unsigned long long)(unsigned)(s / 7) | (unsigned long long)(unsigned)(s % 7) << 32;
-         o[1] = (unsigned long long)__double_as_longlong(table[3 * (size_t)s]);
-         o[2] = (unsigned long long)__double_as_longlong(table[3 * (size_t)s + 1]);
-         o[3] = (unsigned long long)__double_as_longlong(table[3 * (size_t)s + 2]);
-      }
-      run += all;
-   }
-}
+};
 
 /* ---- host side ---------------------------------------------------------- */
 static_assert(sizeof(ddcmi_chol_fragment) == 32, "a fragment is 32 bytes: {int32 mol, role; double r[3]}");
@@ -216,10 +167,7 @@ static int chol_check(ddcmi_ctx *ctx, const char *fn, int64_t nmol, const uint64
    ARGCHK(ctx, !std::isfinite(rmin), "%s: rmin = %g", fn, rmin);
    ARGCHK(ctx, nmol > 0 && (!counts || !ndone || !stats || !nfrag), "%s: NULL output array (counts %p, ndone %p, stats %p, nfrag %p)", fn, counts, ndone, stats, nfrag);
    ARGCHK(ctx, frag && cap < 0, "%s: cap = %lld", fn, (long long)cap);
-   const int off[6] = {1, 2, 3, 5, 6, 7};
-   for (int k = 0; k < 6; k++)
-      if (fabs(ctx->h[off[k]]) > 1e-10) SETERR(ctx, DDCMI_EUNSUPPORTED, "%s: only orthorhombic boxes are supported (h[%d]=%g)", fn, off[k], ctx->h[off[k]]);
-   if (!(ctx->h[0] > 0.0) || !(ctx->h[4] > 0.0) || !(ctx->h[8] > 0.0)) SETERR(ctx, DDCMI_EINVAL, "%s needs a box (ddcmi_set_box)", fn);
+   if ((rc = census_box_check(ctx, fn, 7))) return rc;
    if (DDCMI_CHOL_LDS_BYTES((long)nbins) > DDCMI_CHOL_MAX_LDS)
       SETERR(ctx, DDCMI_EUNSUPPORTED, "%s: %d bins need %ld bytes of LDS, at most %d (8 per bin: %d bins)", fn, nbins, DDCMI_CHOL_LDS_BYTES((long)nbins),
              DDCMI_CHOL_MAX_LDS, DDCMI_CHOL_MAX_NBINS);
@@ -239,18 +187,19 @@ static int chol_one(ddcmi_ctx *ctx, int64_t nmol64, double rmin, double delta, i
    for (int q = 0; q < 2; q++) { stats[3 * q] = 0.0; stats[3 * q + 1] = 1e300; stats[3 * q + 2] = -1e300; }
    if (n <= 0) return DDCMI_OK;      /* (a domain that holds no bead) */
    CholParms cp;
-   cp.rmin = rmin; cp.delta = delta; cp.nbins = nbins; cp.pbc = ctx->pbc;
-   for (int a = 0; a < 3; a++) { cp.L[a] = ctx->h[4 * a]; cp.invL[a] = 1.0 / cp.L[a]; }
+   cp.rmin = rmin; cp.delta = delta; cp.nbins = nbins; census_set_box(ctx, cp);
+   for (int a = 0; a < 3; a++) cp.invL[a] = 1.0 / cp.L[a];
    int per_wg, nwg, per_wgf, nwgf;
    census_split(nmol, CENSUS_MAX_WG, &per_wg, &nwg);
    census_split(nl, CENSUS_MAX_WG, &per_wgf, &nwgf);
-   /* chol_ids: the ascending gids; chol_int: perm[nl] | wg_count[nwgf] | wg_off[nwgf] | total; chol_table: r[nl][3]; chol_flag: present[nl] | split[nmol] */
+   /* chol_ids: the ascending gids; chol_int: perm[nl] | wg_count[nwgf] | wg_off[nwgf + 1]; chol_table: r[nl][3]; chol_flag: present[nl] | split[nmol] */
    const bool fresh = ctx->chol_list_fresh || ctx->chol_ids.cap < (size_t)nl || ctx->chol_int.cap < (size_t)nl + 2 * (size_t)nwgf + 1;
    ENSURE(ctx, ctx->chol_ids, (size_t)nl);
    ENSURE(ctx, ctx->chol_int, (size_t)nl + 2 * (size_t)nwgf + 1);
    ENSURE(ctx, ctx->chol_table, 3 * (size_t)nl);
    ENSURE(ctx, ctx->chol_flag, (size_t)nl + nmol);
-   int *d_perm = ctx->chol_int.p, *d_cnt = d_perm + nl, *d_off = d_cnt + nwgf, *d_total = d_off + nwgf;
+   int *d_perm = ctx->chol_int.p;
+   unsigned *d_cnt = (unsigned *)(d_perm + nl), *d_off = d_cnt + nwgf;
    unsigned char *d_present = ctx->chol_flag.p, *d_split = d_present + nl;
    if (fresh)
    {
@@ -260,33 +209,31 @@ static int chol_one(ddcmi_ctx *ctx, int64_t nmol64, double rmin, double delta, i
    }
    HIPCHK(ctx, hipMemsetAsync(ctx->chol_table.p, 0, 3 * (size_t)nl * sizeof(double), st));
    HIPCHK(ctx, hipMemsetAsync(ctx->chol_flag.p, 0, (size_t)nl + nmol, st));
-   /* census_part, in doubles: part_d | out_d | out_c | part_c */
-   const size_t o_od = (size_t)nwg * 6, o_oc = o_od + 6, o_pc = o_oc + nslot, total = o_pc + ((size_t)nwg * nslot + 1) / 2;
-   ENSURE(ctx, ctx->census_part, total);
-   double *base = ctx->census_part.p;
+   CensusScratch cs;
+   const int s_pd = cs.seg(8, (size_t)nwg * 6), s_od = cs.seg(8, 6), s_oc = cs.seg(8, nslot), s_pc = cs.seg(4, (size_t)nwg * nslot);
+   int rc = cs.ensure(ctx);
+   if (rc) return rc;
    hipLaunchKernelGGL(k_chol_gather, dim3(cdiv(n, 256)), dim3(256), 0, st, n, cp, ctx->chol_sorted.front(), ctx->chol_sorted.back(), nl, ctx->pos.p,
                       (const unsigned long long *)ctx->gid.p, ctx->chol_ids.p, d_perm, ctx->chol_table.p, d_present);
    hipLaunchKernelGGL(k_chol_eval, dim3(nwg), dim3(CENSUS_THREADS), (size_t)DDCMI_CHOL_LDS_BYTES(nbins), st, nmol, per_wg, cp, ctx->chol_table.p, d_present, d_split,
-                      base, (unsigned *)(base + o_pc));
-   hipLaunchKernelGGL((k_census_final<RowsSumMinMax, long long>), dim3(cdiv(nslot, 64)), dim3(64), 0, st, nwg, 6, base, base + o_od, nslot,
-                      (const unsigned *)(base + o_pc), (long long *)(base + o_oc));
-   hipLaunchKernelGGL(k_chol_frag_count, dim3(nwgf), dim3(CENSUS_THREADS), 0, st, nl, per_wgf, d_present, d_split, d_cnt);
-   int rc = ddcmi_scan_exclusive(ctx, d_cnt, d_off, nwgf, d_total);
-   if (rc) return rc;
-   HIPCHK(ctx, hipGetLastError());
-   std::vector<int64_t> hc((size_t)nslot);
-   int nf = 0;
-   HIPCHK(ctx, hipMemcpyAsync(stats, base + o_od, 6 * sizeof(double), hipMemcpyDeviceToHost, st));
-   HIPCHK(ctx, hipMemcpyAsync(hc.data(), base + o_oc, (size_t)nslot * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-   HIPCHK(ctx, hipMemcpyAsync(&nf, d_total, sizeof(int), hipMemcpyDeviceToHost, st));
-   HIPCHK(ctx, hipStreamSynchronize(st));
+                      cs.at<double>(s_pd), cs.at<unsigned>(s_pc));
+   CholFragSel frags = {d_present, d_split, ctx->chol_table.p, nullptr};
+   compact_count(st, nl, per_wgf, nwgf, frags, d_cnt, d_off);
+   std::vector<long long> hc((size_t)nslot);      /* counts | ndone: an array and a word of the caller's */
+   unsigned nf = 0u;
+   if ((rc = census_finish<RowsSumMinMax, long long>(ctx, nwg, 6, cs.at<double>(s_pd), cs.at<double>(s_od), stats, nslot, cs.at<unsigned>(s_pc), cs.at<long long>(s_oc),
+                                                      hc.data(), [&]() -> int {
+                                                         HIPCHK(ctx, hipMemcpyAsync(&nf, d_off + nwgf, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+                                                         return DDCMI_OK;
+                                                      }))) return rc;
    for (int k = 0; k < 2 * nbins; k++) counts[k] = hc[k];
    *ndone = hc[(size_t)2 * nbins];
    *nfrag = nf;
-   if (nf <= 0) return DDCMI_OK;
+   if (nf == 0u) return DDCMI_OK;
    ctx->chol_nfrag = nf;
    ENSURE(ctx, ctx->chol_frag, 4 * (size_t)nf);
-   hipLaunchKernelGGL(k_chol_frag_pack, dim3(nwgf), dim3(CENSUS_THREADS), 0, st, nl, per_wgf, d_present, d_split, ctx->chol_table.p, d_off, (unsigned)nf, ctx->chol_frag.p);
+   frags.rec = ctx->chol_frag.p;
+   compact_pack(st, nl, per_wgf, nwgf, frags, d_off, nf);
    HIPCHK(ctx, hipGetLastError());
    return DDCMI_OK;
 }
@@ -327,19 +274,8 @@ extern "C" int ddcmi_chol_fragments(ddcmi_ctx *ctx, int64_t cap, ddcmi_chol_frag
 extern "C" int ddcmi_group_chol_offsets(ddcmi_ctx **ctxs, int n, int64_t nmol, const uint64_t *gid, double rmin, double delta, int nbins, int64_t *counts,
                                         int64_t *ndone, double *stats, int64_t cap, ddcmi_chol_fragment *frag, int64_t *nfrag)
 {
-   int rc = analysis_group(ctxs, n, "chol_offsets",
-                           [=](ddcmi_ctx *c, const char *fn) { return chol_check(c, fn, nmol, gid, rmin, delta, nbins, counts, ndone, stats, cap, frag, nfrag); },
-                           [=](ddcmi_ctx *c, size_t r) { return chol_one(c, nmol, rmin, delta, nbins, counts + r * 2 * (size_t)nbins, ndone + r, stats + 6 * r, nfrag + r); });
-   if (rc || nmol == 0 || !frag) return rc;
-   int64_t total = 0;
-   for (int r = 0; r < n; r++) total += nfrag[r];
-   if (cap < total) SETERR(ctxs[0], DDCMI_EINVAL, "ddcmi_group_chol_offsets: capacity %lld < %lld fragments", (long long)cap, (long long)total);
-   ddcmi_group *g = ctxs[0]->group_;
-   int64_t off = 0;
-   for (int r = 0; r < n; r++)
-   {
-      if ((rc = chol_copy_fragments(g->ranks[r], nfrag[r], frag + off))) { if (r) ctxs[0]->err = g->ranks[r]->err; return rc; }
-      off += nfrag[r];
-   }
-   return DDCMI_OK;
+   return analysis_group_records(ctxs, n, "chol_offsets", "fragments",
+                                 [=](ddcmi_ctx *c, const char *fn) { return chol_check(c, fn, nmol, gid, rmin, delta, nbins, counts, ndone, stats, cap, frag, nfrag); },
+                                 [=](ddcmi_ctx *c, size_t r) { return chol_one(c, nmol, rmin, delta, nbins, counts + r * 2 * (size_t)nbins, ndone + r, stats + 6 * r, nfrag + r); },
+                                 nmol != 0 && frag, cap, nfrag, [=](ddcmi_ctx *c, size_t r, int64_t off) { return chol_copy_fragments(c, nfrag[r], frag + off); });
 }

@@ -15,19 +15,18 @@
  *                    over them in (digit, workgroup) order, k_cg_scatter (a lane's place: the scanned offset + the items of that digit
  *                    in the workgroup's earlier blocks + those in the earlier waves of its block (LDS) + those in the lower lanes
  *                    of its wave -- eight ballots give the lanes that share the digit, a popcount the rank: the ranking of
- *                    ddcmi_subset.inl's compaction, per digit).  Equal keys keep their order, so a segment lists its contributions
+ *                    the frame's compaction, per digit).  Equal keys keep their order, so a segment lists its contributions
  *                    by ascending slot * 8 + corner.
- *   the segments     an item heads a segment when its key differs from the one before it; the heads are compacted as the subset
- *                    pass compacts its beads (k_cg_head_count, k_subset_scan, k_cg_head_pack).  The sentinel's items are the last
- *                    segment: it is not a record.
+ *   the segments     an item heads a segment when its key differs from the one before it; the heads go through the frame's
+ *                    compaction (CgHeadSel).  The sentinel's items are the last segment: it is not a record.
  *   k_cg_reduce      segment s belongs to lane s % 64 of wave s / 64.  Up to CG_SHORT items: that lane adds them in order, starting
  *                    from +0.  More: the wave takes it, lane l adds items l, l + 64, ... in order, wave_sum_dpp combines the lanes.
  *                    The association is a function of the segment's length alone.  Every item recomputes its eight terms from the
  *                    bead (cg_item, the code that made its key), so that the sort carries 8 bytes per contribution; the lane writes
  *                    the 80-byte record.
  * Every term is a rounded product (zd_rounded keeps the back end from fusing it into the addition), in the reference's operations:
- * weight = (wx wy) wz, m, 0.5 m (v v) and m v times the weight.  The position is the slot's, wrapped once on periodic axes as a download
- * returns it; r = x (n / L) - corner (n / L); the cells are the reference's ((int)r, or floor(r + 0.5) - 1 and floor(r + 0.5) with -1 -> n - 1
+ * weight = (wx wy) wz, m, 0.5 m (v v) and m v times the weight.  The position is the one a download returns (census_coord);
+ * r = x (n / L) - corner (n / L); the cells are the reference's ((int)r, or floor(r + 0.5) - 1 and floor(r + 0.5) with -1 -> n - 1
  * and n -> 0 on every axis, open ones too), then clamped into [0, n): a bead on the upper face, one the wrap leaves at L / 2, a NaN
  * (cell 0, as pc_axis). */
 
@@ -47,8 +46,7 @@ struct CgBeads { const double4 *pos; const double *vx, *vy, *vz, *massv; const i
 __device__ __forceinline__ void cg_axis(const CgParms &cp, int a, double x, int c, int &ig, double &w)
 {
    const int n = cp.n[a];
-   if (cp.pbc >> a & 1) { if (x > 0.5 * cp.L[a]) x -= cp.L[a]; if (x < -0.5 * cp.L[a]) x += cp.L[a]; }      /* k_export_pos */
-   const double r = zd_rounded(x * cp.deltai[a]) - cp.scaled_corner[a];
+   const double r = zd_rounded(census_coord(cp, a, x) * cp.deltai[a]) - cp.scaled_corner[a];
    if (!cp.smear) { ig = zd_int(r); w = 1.0; }
    else
    {
@@ -166,52 +164,19 @@ __global__ __launch_bounds__(CENSUS_THREADS) void k_cg_scatter(int m, int per_wg
       __syncthreads();
    }
 }
-__device__ __forceinline__ bool cg_head(const unsigned *__restrict__ key, int i) { return i == 0 || key[i] != key[i - 1]; }
-/* k_subset_count / k_subset_pack with the predicate cg_head; seg[place] = the head's index, seg[nseg] = m */
-__global__ __launch_bounds__(CENSUS_THREADS) void k_cg_head_count(int m, int per_wg, const unsigned *__restrict__ key, unsigned *__restrict__ wg_count)
+/* the compaction's functor (k_compact_count, k_compact_pack): item i of the sorted keys heads a segment; seg[place] = the head's
+ * index, and item 0, always a head, leaves seg[nseg] = m, the end of the last segment */
+struct CgHeadSel
 {
-   __shared__ unsigned wave_s[CENSUS_WAVES];
-   const int beg = blockIdx.x * per_wg, end = min(m, beg + per_wg);
-   unsigned mine = 0u;
-   for (int base = beg; base < end; base += CENSUS_THREADS)      /* (uniform trip count) */
+   const unsigned *key; unsigned *seg; unsigned nseg, m;
+   struct Item {};
+   __device__ __forceinline__ bool selected(int i, Item &) const { return i == 0 || key[i] != key[i - 1]; }
+   __device__ __forceinline__ void store(int i, unsigned place, const Item &) const
    {
-      const int i = base + (int)threadIdx.x;
-      mine += (unsigned)__popcll(__ballot(i < end && cg_head(key, i)));
+      seg[place] = (unsigned)i;
+      if (i == 0) seg[nseg] = m;
    }
-   if ((threadIdx.x & 63) == 0) wave_s[threadIdx.x >> 6] = mine;
-   __syncthreads();
-   if (threadIdx.x == 0)
-   {
-      unsigned t = 0u;
-#pragma unroll
-      for (int w = 0; w < CENSUS_WAVES; w++) t += wave_s[w];
-      wg_count[blockIdx.x] = t;
-   }
-}
-__global__ __launch_bounds__(CENSUS_THREADS) void k_cg_head_pack(int m, int per_wg, const unsigned *__restrict__ key, const unsigned *__restrict__ wg_off, unsigned nseg,
-                                                                 unsigned *__restrict__ seg)
-{
-   __shared__ unsigned wave_s[2][CENSUS_WAVES];
-   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-   const int beg = blockIdx.x * per_wg, end = min(m, beg + per_wg);
-   unsigned run = wg_off[blockIdx.x];
-   int par = 0;
-   if (blockIdx.x == 0 && threadIdx.x == 0) seg[nseg] = (unsigned)m;
-   for (int base = beg; base < end; base += CENSUS_THREADS, par ^= 1)      /* (uniform trip count) */
-   {
-      const int i = base + (int)threadIdx.x;
-      const bool sel = i < end && cg_head(key, i);
-      const unsigned long long same = __ballot(sel);
-      if (lane == 0) wave_s[par][wave] = (unsigned)__popcll(same);
-      __syncthreads();
-      unsigned before = 0u, all = 0u;
-#pragma unroll
-      for (int w = 0; w < CENSUS_WAVES; w++) { const unsigned c = wave_s[par][w]; all += c; if (w < wave) before += c; }
-      const unsigned place = run + before + (unsigned)__popcll(same & ((1ull << lane) - 1ull));
-      if (sel && place < nseg) seg[place] = (unsigned)i;
-      run += all;
-   }
-}
+};
 /* rec: nrec records of ten 8-byte words {label, species, n, mass, K[3], p[3]}; seg[nrec] is the end of the last record's segment */
 __global__ __launch_bounds__(CENSUS_THREADS) void k_cg_reduce(int nrec, int nloc, CgParms cp, CgBeads b, const unsigned *__restrict__ key, const unsigned *__restrict__ val,
                                                               const unsigned *__restrict__ seg, unsigned long long *__restrict__ rec)
@@ -275,10 +240,7 @@ static int cg_check(ddcmi_ctx *ctx, const char *fn, const CgReq &q, int64_t cap,
    ARGCHK(ctx, q.nspecies != ctx->nspecies, "%s: nspecies = %d, the context has %d species", fn, q.nspecies, ctx->nspecies);
    ARGCHK(ctx, q.smear_method != 0 && q.smear_method != 1, "%s: smear_method = %d (0 impulse, 1 hat)", fn, q.smear_method);
    ARGCHK(ctx, !std::isfinite(q.smear_radius), "%s: smear_radius = %g", fn, q.smear_radius);
-   if (!(ctx->h[0] > 0.0) || !(ctx->h[4] > 0.0) || !(ctx->h[8] > 0.0)) SETERR(ctx, DDCMI_EINVAL, "%s needs a box (ddcmi_set_box)", fn);
-   const int off[6] = {1, 2, 3, 5, 6, 7};
-   for (int k = 0; k < 6; k++)
-      if (fabs(ctx->h[off[k]]) > 1e-10) SETERR(ctx, DDCMI_EUNSUPPORTED, "%s: only orthorhombic boxes are supported (h[%d]=%g)", fn, off[k], ctx->h[off[k]]);
+   if ((rc = census_box_check(ctx, fn, 7, true))) return rc;
    const double nkeys = (double)q.n[0] * q.n[1] * q.n[2] * q.nspecies;
    if (nkeys > (double)DDCMI_CG_MAX_KEYS)
       SETERR(ctx, DDCMI_EUNSUPPORTED, "%s: %d x %d x %d cells x %d species = %.0f keys, at most %d", fn, q.n[0], q.n[1], q.n[2], q.nspecies, nkeys, DDCMI_CG_MAX_KEYS);
@@ -294,12 +256,12 @@ static int cg_one(ddcmi_ctx *ctx, const CgReq &q, int64_t cap, ddcmi_cg_record *
    *count = 0;
    if (n <= 0) return DDCMI_OK;      /* (a domain that holds no bead) */
    CgParms cp;
-   cp.ns = q.nspecies; cp.pbc = ctx->pbc; cp.smear = q.smear_radius > 0.0; cp.method = q.smear_method; cp.nc = cp.smear ? 8 : 1;
+   cp.ns = q.nspecies; census_set_box(ctx, cp); cp.smear = q.smear_radius > 0.0; cp.method = q.smear_method; cp.nc = cp.smear ? 8 : 1;
    cp.sentinel = (unsigned)q.n[0] * (unsigned)q.n[1] * (unsigned)q.n[2] * (unsigned)q.nspecies;
    for (int a = 0; a < 3; a++)
    {
       const double L = ctx->h[4 * a], corner = L * -0.5;      /* box->corner = h0 * reducedcorner, reducedcorner = -0.5 on this path */
-      cp.n[a] = q.n[a]; cp.L[a] = L;
+      cp.n[a] = q.n[a];
       cp.deltai[a] = q.n[a] / L;
       cp.scaled_corner[a] = corner * cp.deltai[a];
       cp.half[a] = cp.inv[a] = 0.0;
@@ -334,8 +296,8 @@ static int cg_one(ddcmi_ctx *ctx, const CgReq &q, int64_t cap, ddcmi_cg_record *
       if (rc) return rc;
       hipLaunchKernelGGL(k_cg_scatter, dim3(nwg), dim3(CENSUS_THREADS), 0, st, m, per_wg, 8 * p, key[cur], val[cur], d_off, key[cur ^ 1], val[cur ^ 1]);
    }
-   hipLaunchKernelGGL(k_cg_head_count, dim3(nwg), dim3(CENSUS_THREADS), 0, st, m, per_wg, key[cur], d_cnt);
-   hipLaunchKernelGGL(k_subset_scan, dim3(1), dim3(64), 0, st, nwg, d_cnt, d_wgoff);
+   CgHeadSel heads = {key[cur], nullptr, 0u, (unsigned)m};
+   compact_count(st, m, per_wg, nwg, heads, d_cnt, d_wgoff);
    HIPCHK(ctx, hipGetLastError());
    unsigned nseg = 0u, last = 0u;
    HIPCHK(ctx, hipMemcpyAsync(&nseg, d_wgoff + nwg, sizeof(unsigned), hipMemcpyDeviceToHost, st));
@@ -348,7 +310,8 @@ static int cg_one(ddcmi_ctx *ctx, const CgReq &q, int64_t cap, ddcmi_cg_record *
    if (nrec == 0u) return DDCMI_OK;
    ENSURE(ctx, ctx->cg_seg, (size_t)nseg + 1);
    ENSURE(ctx, ctx->cg_rec, 10 * (size_t)nrec);
-   hipLaunchKernelGGL(k_cg_head_pack, dim3(nwg), dim3(CENSUS_THREADS), 0, st, m, per_wg, key[cur], d_wgoff, nseg, ctx->cg_seg.p);
+   heads.seg = ctx->cg_seg.p; heads.nseg = nseg;
+   compact_pack(st, m, per_wg, nwg, heads, d_wgoff, nseg);
    hipLaunchKernelGGL(k_cg_reduce, dim3(cdiv((long)nrec, CENSUS_THREADS)), dim3(CENSUS_THREADS), 0, st, (int)nrec, n, cp, b, key[cur], val[cur], ctx->cg_seg.p, ctx->cg_rec.p);
    HIPCHK(ctx, hipGetLastError());
    HIPCHK(ctx, hipMemcpyAsync(rec, ctx->cg_rec.p, sizeof(ddcmi_cg_record) * (size_t)nrec, hipMemcpyDeviceToHost, st));
@@ -363,23 +326,12 @@ extern "C" int ddcmi_coarsegrain(ddcmi_ctx *ctx, int nx, int ny, int nz, int nsp
    return analysis_single(ctx, "coarsegrain", true, [=](ddcmi_ctx *c, const char *fn) { return cg_check(c, fn, q, cap, rec, count); },
                           [=](ddcmi_ctx *c) { return cg_one(c, q, cap, rec, count); });
 }
-/* in-process group: count[r] of every domain; with rec, the domains' records one block behind the other in rank order, cap their sum's
- * room.  The counts of all domains come first, so that a buffer that is too small stays untouched. */
+/* in-process group (analysis_group_records): count[r] of every domain; with rec, the domains' records in rank order, cap their sum's room */
 extern "C" int ddcmi_group_coarsegrain(ddcmi_ctx **ctxs, int n, int nx, int ny, int nz, int nspecies, double smear_radius, int smear_method, int64_t cap,
                                        ddcmi_cg_record *rec, int64_t *count)
 {
    const CgReq q = {{nx, ny, nz}, nspecies, smear_radius, smear_method};
-   if (ctxs && n >= 1 && ctxs[0] && !ctxs[0]->group_)
-      SETERR(ctxs[0], DDCMI_EINVAL, "ddcmi_group_coarsegrain: not the contexts of an in-process group: use ddcmi_coarsegrain");
-   int rc = analysis_group(ctxs, n, "coarsegrain", [=](ddcmi_ctx *c, const char *fn) { return cg_check(c, fn, q, cap, rec, count); },
-                           [=](ddcmi_ctx *c, size_t r) { return cg_one(c, q, 0, nullptr, count + r); });
-   if (rc || !rec) return rc;
-   int64_t total = 0;
-   for (int r = 0; r < n; r++) total += count[r];
-   if (cap < total) SETERR(ctxs[0], DDCMI_EINVAL, "ddcmi_group_coarsegrain: capacity %lld < %lld entries", (long long)cap, (long long)total);
-   std::vector<int64_t> off((size_t)n, 0);
-   for (int r = 1; r < n; r++) off[r] = off[r - 1] + count[r - 1];
-   const int64_t *o = off.data();
-   return analysis_group(ctxs, n, "coarsegrain", [](ddcmi_ctx *, const char *) { return DDCMI_OK; },
-                         [=](ddcmi_ctx *c, size_t r) { return cg_one(c, q, count[r], rec + o[r], count + r); });
+   return analysis_group_records(ctxs, n, "coarsegrain", "entries", [=](ddcmi_ctx *c, const char *fn) { return cg_check(c, fn, q, cap, rec, count); },
+                                 [=](ddcmi_ctx *c, size_t r) { return cg_one(c, q, 0, nullptr, count + r); }, rec != nullptr, cap, count,
+                                 [=](ddcmi_ctx *c, size_t r, int64_t off) { return cg_one(c, q, count[r], rec + off, count + r); });
 }

@@ -131,3 +131,72 @@ extern "C" int ddcmi_debug_sort_cells(int ncell, const int *start, const int *cn
    (void)hipFree(d);
    return rc;
 }
+
+/* the census frame's stable compaction (k_compact_count, k_compact_scan, k_compact_pack of ddcmi_census_frame.inl, launched by the
+ * product's compact_count / compact_pack over census_split(n, max_wg)) on the caller's 0 / 1 flags: the kept slots' indices in slot
+ * order.  The device array of places is nrec + DDCMI_DEBUG_COMPACT_GUARD long and starts as the caller's */
+struct DebugFlagSel
+{
+   const int *flags; int *places;
+   struct Item {};
+   __device__ __forceinline__ bool selected(int i, Item &) const { return flags[i] != 0; }
+   __device__ __forceinline__ void store(int i, unsigned place, const Item &) const { places[place] = i; }
+};
+extern "C" int ddcmi_debug_compact(int n, const int *flags, int max_wg, int nrec, int *places, int *total)
+{
+   if (n < 1 || n > (1 << 24) || max_wg < 1 || max_wg > 2048 || nrec < 0 || nrec > (1 << 24) || !flags || !places || !total) return DDCMI_EINVAL;
+   int per_wg, nwg;
+   census_split(n, max_wg, &per_wg, &nwg);
+   const size_t np = (size_t)nrec + DDCMI_DEBUG_COMPACT_GUARD;
+   int *d = nullptr;
+   if (hipMalloc((void **)&d, ((size_t)n + np + 2 * (size_t)nwg + 1) * sizeof(int)) != hipSuccess) return DDCMI_ENOMEM;
+   int *d_flags = d, *d_places = d + n;
+   unsigned *d_cnt = (unsigned *)(d_places + np), *d_off = d_cnt + nwg, t = 0u;
+   const DebugFlagSel sel = {d_flags, d_places};
+   int rc = DDCMI_ENODEVICE;
+   if (hipMemcpy(d_flags, flags, (size_t)n * sizeof(int), hipMemcpyHostToDevice) == hipSuccess &&
+       hipMemcpy(d_places, places, np * sizeof(int), hipMemcpyHostToDevice) == hipSuccess)
+   {
+      compact_count((hipStream_t)0, n, per_wg, nwg, sel, d_cnt, d_off);
+      compact_pack((hipStream_t)0, n, per_wg, nwg, sel, d_off, (unsigned)nrec);
+      if (hipGetLastError() == hipSuccess && hipMemcpy(places, d_places, np * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess &&
+          hipMemcpy(&t, d_off + nwg, sizeof(unsigned), hipMemcpyDeviceToHost) == hipSuccess) { *total = (int)t; rc = DDCMI_OK; }
+   }
+   (void)hipFree(d);
+   return rc;
+}
+
+/* gid_find of ddcmi_census_frame.inl over ids[lo, hi), one thread per query: the index of the query, -1 where it is not in the range.  I: the
+ * index type of the call -- int as cholAnalysis and FORCE_AVERAGE (a sub-range: the gids behind a pivot) call it, long long as subsetWrite does */
+template <class I>
+__global__ __launch_bounds__(256) void k_debug_gid_find(I lo, I hi, const unsigned long long *__restrict__ ids, int nq, const unsigned long long *__restrict__ queries,
+                                                        int *__restrict__ index)
+{
+   const int q = blockIdx.x * 256 + threadIdx.x;
+   if (q >= nq) return;
+   I at;
+   index[q] = gid_find(ids, lo, hi, queries[q], &at) ? (int)at : -1;
+}
+extern "C" int ddcmi_debug_gid_find_in(int nids, const uint64_t *ids, int lo, int hi, int wide, int nq, const uint64_t *queries, int *index)
+{
+   if (nids < 1 || nids > (1 << 24) || lo < 0 || hi < lo || hi > nids || nq < 1 || nq > (1 << 24) || !ids || !queries || !index) return DDCMI_EINVAL;
+   for (int k = 1; k < nids; k++) if (ids[k] < ids[k - 1]) return DDCMI_EINVAL;
+   unsigned long long *d = nullptr;
+   if (hipMalloc((void **)&d, ((size_t)nids + nq) * sizeof(unsigned long long) + (size_t)nq * sizeof(int)) != hipSuccess) return DDCMI_ENOMEM;
+   unsigned long long *d_ids = d, *d_q = d + nids;
+   int *d_index = (int *)(d_q + nq);
+   int rc = DDCMI_ENODEVICE;
+   if (hipMemcpy(d_ids, ids, (size_t)nids * sizeof(uint64_t), hipMemcpyHostToDevice) == hipSuccess &&
+       hipMemcpy(d_q, queries, (size_t)nq * sizeof(uint64_t), hipMemcpyHostToDevice) == hipSuccess)
+   {
+      if (wide) hipLaunchKernelGGL(k_debug_gid_find<long long>, dim3(cdiv(nq, 256)), dim3(256), 0, 0, (long long)lo, (long long)hi, d_ids, nq, d_q, d_index);
+      else hipLaunchKernelGGL(k_debug_gid_find<int>, dim3(cdiv(nq, 256)), dim3(256), 0, 0, lo, hi, d_ids, nq, d_q, d_index);
+      if (hipGetLastError() == hipSuccess && hipMemcpy(index, d_index, (size_t)nq * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess) rc = DDCMI_OK;
+   }
+   (void)hipFree(d);
+   return rc;
+}
+extern "C" int ddcmi_debug_gid_find(int nids, const uint64_t *ids, int nq, const uint64_t *queries, int *index)
+{
+   return ddcmi_debug_gid_find_in(nids, ids, 0, nids, 0, nq, queries, index);
+}

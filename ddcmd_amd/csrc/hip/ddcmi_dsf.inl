@@ -4,8 +4,7 @@
  * and the charge ctx->d_charge_sp[species] of ddcmi_set_species.  Included from ddcmi.hip behind ddcmi_kdist.inl.  The caller adds
  * the ranks' sums and counts and divides by the global count (dsf.c:207-212).
  *
- * Per bead.  The position is the one ddcmi_download_state hands out (the slot's, shifted once by the box side where it left a
- * periodic box since the last rebuild: k_export_pos), without a further wrap.  The phase needs none: with t = r / L (one correctly
+ * Per bead.  The position is the one ddcmi_download_state hands out (census_coord), without a further wrap.  The phase needs none: with t = r / L (one correctly
  * rounded division) the turn count t - rint(t) is exact, |t| <= 1/2 from there on, and sincospi takes 2 m t without ever
  * multiplying by a rounded pi.  A bead outside the box therefore costs its own u |t| of the division and nothing more.
  *
@@ -65,13 +64,11 @@ __global__ __launch_bounds__(CENSUS_THREADS) void k_census_dsf(int n, int per_wg
          {
             const double q = charge[s];
             const double4 p4 = pos[i];
-            double r[3] = {p4.x, p4.y, p4.z};
+            const double r[3] = {p4.x, p4.y, p4.z};
 #pragma unroll
             for (int a = 0; a < 3; a++)
             {
-               const double L = dp.L[a];
-               if (dp.pbc >> a & 1) { if (r[a] > 0.5 * L) r[a] -= L; if (r[a] < -0.5 * L) r[a] += L; }      /* k_export_pos */
-               double t = r[a] / L;
+               double t = census_coord(dp, a, r[a]) / dp.L[a];
                t -= rint(t);      /* exact */
                double cs, cc, ps, pc;
                sincospi(2.0 * t, &cs, &cc);
@@ -119,17 +116,12 @@ static int census_dsf_check(ddcmi_ctx *ctx, const char *fn, int nspecies, int mm
    ARGCHK(ctx, nspecies != ctx->nspecies, "%s: nspecies = %d, the context has %d species", fn, nspecies, ctx->nspecies);
    ARGCHK(ctx, ctx->nspecies < 1, "%s needs the species (ddcmi_set_species)", fn);
    if (mmax > DDCMI_DSF_MAX_M) SETERR(ctx, DDCMI_EUNSUPPORTED, "%s: mmax = %d, at most %d", fn, mmax, DDCMI_DSF_MAX_M);
-   const int off[6] = {1, 2, 3, 5, 6, 7};
-   for (int k = 0; k < 6; k++)
-      if (fabs(ctx->h[off[k]]) > 1e-10) SETERR(ctx, DDCMI_EUNSUPPORTED, "%s: only orthorhombic boxes are supported (h[%d]=%g)", fn, off[k], ctx->h[off[k]]);
-   if (!(ctx->h[0] > 0.0) || !(ctx->h[4] > 0.0) || !(ctx->h[8] > 0.0)) SETERR(ctx, DDCMI_EINVAL, "%s needs a box (ddcmi_set_box)", fn);
-   return DDCMI_OK;
+   return census_box_check(ctx, fn, 7);
 }
 /* this rank's sums and count [sync] */
 static int census_dsf_one(ddcmi_ctx *ctx, const int *select, int mmax, double *rho, int64_t *count)
 {
    (void)hipSetDevice(ctx->device);
-   hipStream_t st = ctx->stream;
    const int n = ctx->nloc, ns = ctx->nspecies, nval = 6 * mmax;
    if (n <= 0)      /* (a domain that holds no bead) */
    {
@@ -137,28 +129,21 @@ static int census_dsf_one(ddcmi_ctx *ctx, const int *select, int mmax, double *r
       *count = 0;
       return DDCMI_OK;
    }
-   std::vector<int> sel((size_t)ns, 1);
-   if (select) for (int s = 0; s < ns; s++) sel[s] = select[s] != 0;
    DsfParms dp;
-   dp.L[0] = ctx->h[0]; dp.L[1] = ctx->h[4]; dp.L[2] = ctx->h[8];
-   dp.pbc = ctx->pbc; dp.mmax = mmax;
+   census_set_box(ctx, dp); dp.mmax = mmax;
    int per_wg, nwg;
    census_split(n, CENSUS_MAX_WG, &per_wg, &nwg);
-   /* census_part, in doubles: select | part_d | out_d | out_c | part_c */
-   const size_t o_pd = ((size_t)ns + 1) / 2, o_od = o_pd + (size_t)nwg * nval, o_oc = o_od + nval, o_pc = o_oc + 1, total = o_pc + ((size_t)nwg + 1) / 2;
-   ENSURE(ctx, ctx->census_part, total);
-   double *base = ctx->census_part.p;
-   HIPCHK(ctx, hipMemcpyAsync(base, sel.data(), (size_t)ns * sizeof(int), hipMemcpyHostToDevice, st));
+   CensusScratch cs;
+   const int s_sel = cs.seg(4, ns), s_pd = cs.seg(8, (size_t)nwg * nval), s_od = cs.seg(8, nval), s_oc = cs.seg(8, 1), s_pc = cs.seg(4, nwg);
+   int rc = cs.ensure(ctx);
+   if (rc) return rc;
+   std::vector<int> sel;
+   if ((rc = census_upload_select(ctx, select, sel, cs.at<int>(s_sel)))) return rc;
    const size_t lds = (size_t)CENSUS_WAVES * nval * sizeof(double) + sizeof(double);
-   hipLaunchKernelGGL(k_census_dsf<DSF_CHUNK>, dim3(nwg), dim3(CENSUS_THREADS), lds, st, n, per_wg, ns, dp, ctx->pos.p, ctx->species.p, ctx->d_charge_sp.p,
-                      (const int *)base, base + o_pd, (unsigned *)(base + o_pc));
-   hipLaunchKernelGGL((k_census_final<RowsSum, long long>), dim3(cdiv(nval, 64)), dim3(64), 0, st, nwg, nval, base + o_pd, base + o_od, 1,
-                      (const unsigned *)(base + o_pc), (long long *)(base + o_oc));
-   HIPCHK(ctx, hipGetLastError());
-   HIPCHK(ctx, hipMemcpyAsync(rho, base + o_od, (size_t)nval * sizeof(double), hipMemcpyDeviceToHost, st));
-   HIPCHK(ctx, hipMemcpyAsync(count, base + o_oc, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-   HIPCHK(ctx, hipStreamSynchronize(st));
-   return DDCMI_OK;
+   hipLaunchKernelGGL(k_census_dsf<DSF_CHUNK>, dim3(nwg), dim3(CENSUS_THREADS), lds, ctx->stream, n, per_wg, ns, dp, ctx->pos.p, ctx->species.p, ctx->d_charge_sp.p,
+                      cs.at<int>(s_sel), cs.at<double>(s_pd), cs.at<unsigned>(s_pc));
+   return census_finish<RowsSum, long long>(ctx, nwg, nval, cs.at<double>(s_pd), cs.at<double>(s_od), rho, 1, cs.at<unsigned>(s_pc), cs.at<long long>(s_oc),
+                                            (long long *)count);
 }
 
 extern "C" int ddcmi_charge_density_modes(ddcmi_ctx *ctx, int nspecies, const int *select, int mmax, double *rho, int64_t *count)
@@ -169,8 +154,6 @@ extern "C" int ddcmi_charge_density_modes(ddcmi_ctx *ctx, int nspecies, const in
 /* in-process group: per-rank blocks, rank after rank (rho[r * 6 mmax ...], count[r]) */
 extern "C" int ddcmi_group_charge_density_modes(ddcmi_ctx **ctxs, int n, int nspecies, const int *select, int mmax, double *rho, int64_t *count)
 {
-   if (ctxs && n >= 1 && ctxs[0] && !ctxs[0]->group_)
-      SETERR(ctxs[0], DDCMI_EINVAL, "ddcmi_group_charge_density_modes: not the contexts of an in-process group: use ddcmi_charge_density_modes");
    return analysis_group(ctxs, n, "charge_density_modes", [=](ddcmi_ctx *c, const char *fn) { return census_dsf_check(c, fn, nspecies, mmax, rho, count); },
                          [=](ddcmi_ctx *c, size_t r) { return census_dsf_one(c, select, mmax, rho + r * 6 * (size_t)mmax, count + r); });
 }

@@ -536,11 +536,8 @@ __global__ void k_export_pos(GridParams gp, int nloc, const double4 *pos, const 
    int i = blockIdx.x * blockDim.x + threadIdx.x;
    if (i >= nloc) return;
    double4 p = pos[i];
-   if (gp.pbc & 1) { if (p.x > 0.5 * gp.L[0]) p.x -= gp.L[0]; if (p.x < -0.5 * gp.L[0]) p.x += gp.L[0]; }
-   if (gp.pbc & 2) { if (p.y > 0.5 * gp.L[1]) p.y -= gp.L[1]; if (p.y < -0.5 * gp.L[1]) p.y += gp.L[1]; }
-   if (gp.pbc & 4) { if (p.z > 0.5 * gp.L[2]) p.z -= gp.L[2]; if (p.z < -0.5 * gp.L[2]) p.z += gp.L[2]; }
    int o = orig[i];
-   ox[o] = p.x; oy[o] = p.y; oz[o] = p.z;
+   ox[o] = export_coord(p.x, gp.L[0], gp.pbc & 1); oy[o] = export_coord(p.y, gp.L[1], gp.pbc & 2); oz[o] = export_coord(p.z, gp.L[2], gp.pbc & 4);
 }
 __global__ void k_export3(int nloc, const double *a, const double *b, const double *c, const int *orig, double *oa, double *ob, double *oc)
 {

@@ -480,6 +480,13 @@ struct RoctxRange
 
 
 #ifdef __HIPCC__
+/* the coordinate a download returns for a slot's x: shifted once by the box side L where the bead left a periodic box since the last
+ * rebuild (pbc: the axis's bit).  The one copy: k_export_pos, k_export_particles and every analysis pass (ddcmi_census_frame.inl) */
+__device__ __forceinline__ double export_coord(double x, double L, int pbc)
+{
+   if (pbc) { if (x > 0.5 * L) x -= L; if (x < -0.5 * L) x += L; }
+   return x;
+}
 /* double-precision 1/sqrt(x) and 1/x from the single-precision hardware seeds (the bonded kernels' versions).
  * DOMAIN: the seed instructions work on NORMAL floats -- a subnormal argument counts as 0 and a subnormal result comes back as 0:
  *   rsqrt_f64   2^-126 <= x <= FLT_MAX (2^128 - 2^104)              rcp_f64   2^-126 <= |x| <= 2^126 (above, the float 1/x is subnormal)

@@ -142,23 +142,19 @@ static int census_kdist_one(ddcmi_ctx *ctx, int ndist, const double *emin, const
    const int nslot = nbt + nd3;
    int per_wg, nwg;
    census_split(n, CENSUS_MAX_WG, &per_wg, &nwg);
-   /* census_part, in doubles: the groups' parameters | species_dist | part_d | out_d | out_c | part_c */
-   const size_t o_map = (size_t)ndist * (sizeof(KdGroup) / sizeof(double)), o_pd = o_map + ((size_t)ns + 1) / 2, o_od = o_pd + (size_t)nwg * nd3,
-                o_oc = o_od + nd3, o_pc = o_oc + nslot, total = o_pc + ((size_t)nwg * nslot + 1) / 2;
-   ENSURE(ctx, ctx->census_part, total);
-   double *base = ctx->census_part.p;
-   HIPCHK(ctx, hipMemcpyAsync(base, grp.data(), (size_t)ndist * sizeof(KdGroup), hipMemcpyHostToDevice, st));
-   HIPCHK(ctx, hipMemcpyAsync(base + o_map, species_dist, (size_t)ns * sizeof(int), hipMemcpyHostToDevice, st));
+   CensusScratch cs;
+   const int s_grp = cs.seg(sizeof(KdGroup), ndist), s_map = cs.seg(4, ns), s_pd = cs.seg(8, (size_t)nwg * nd3), s_od = cs.seg(8, nd3), s_oc = cs.seg(8, nslot),
+             s_pc = cs.seg(4, (size_t)nwg * nslot);
+   int rc = cs.ensure(ctx);
+   if (rc) return rc;
+   HIPCHK(ctx, hipMemcpyAsync(cs.at<KdGroup>(s_grp), grp.data(), (size_t)ndist * sizeof(KdGroup), hipMemcpyHostToDevice, st));
+   HIPCHK(ctx, hipMemcpyAsync(cs.at<int>(s_map), species_dist, (size_t)ns * sizeof(int), hipMemcpyHostToDevice, st));
    const size_t lds = (size_t)DDCMI_KDIST_LDS_BYTES(ndist, nbt);
    hipLaunchKernelGGL(k_census_kdist, dim3(nwg), dim3(CENSUS_THREADS), lds, st, n, per_wg, ns, ndist, nbt, ctx->vx.p, ctx->vy.p, ctx->vz.p, ctx->species.p,
-                      ctx->d_mass.p, (const KdGroup *)base, (const int *)(base + o_map), base + o_pd, (unsigned *)(base + o_pc));
-   hipLaunchKernelGGL((k_census_final<RowsSumMinMax, long long>), dim3(cdiv(nslot, 64)), dim3(64), 0, st, nwg, nd3, base + o_pd, base + o_od, nslot,
-                      (const unsigned *)(base + o_pc), (long long *)(base + o_oc));
-   HIPCHK(ctx, hipGetLastError());
-   std::vector<int64_t> hc((size_t)nslot);
-   HIPCHK(ctx, hipMemcpyAsync(stats, base + o_od, (size_t)nd3 * sizeof(double), hipMemcpyDeviceToHost, st));
-   HIPCHK(ctx, hipMemcpyAsync(hc.data(), base + o_oc, (size_t)nslot * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-   HIPCHK(ctx, hipStreamSynchronize(st));
+                      ctx->d_mass.p, cs.at<KdGroup>(s_grp), cs.at<int>(s_map), cs.at<double>(s_pd), cs.at<unsigned>(s_pc));
+   std::vector<long long> hc((size_t)nslot);      /* counts | tallies: two arrays of the caller's */
+   if ((rc = census_finish<RowsSumMinMax, long long>(ctx, nwg, nd3, cs.at<double>(s_pd), cs.at<double>(s_od), stats, nslot, cs.at<unsigned>(s_pc),
+                                                      cs.at<long long>(s_oc), hc.data()))) return rc;
    for (int k = 0; k < nbt; k++) counts[k] = hc[k];
    for (int k = 0; k < nd3; k++) tallies[k] = hc[(size_t)nbt + k];
    return DDCMI_OK;

@@ -1102,10 +1102,7 @@ __global__ void k_export_particles(GridParams gp, int n, const double4 *pos, dou
    int i = blockIdx.x * blockDim.x + threadIdx.x;
    if (i >= n) return;
    double4 p = pos[i];
-   if (gp.pbc & 1) { if (p.x > 0.5 * gp.L[0]) p.x -= gp.L[0]; if (p.x < -0.5 * gp.L[0]) p.x += gp.L[0]; }
-   if (gp.pbc & 2) { if (p.y > 0.5 * gp.L[1]) p.y -= gp.L[1]; if (p.y < -0.5 * gp.L[1]) p.y += gp.L[1]; }
-   if (gp.pbc & 4) { if (p.z > 0.5 * gp.L[2]) p.z -= gp.L[2]; if (p.z < -0.5 * gp.L[2]) p.z += gp.L[2]; }
-   x[i] = p.x; y[i] = p.y; z[i] = p.z;
+   x[i] = export_coord(p.x, gp.L[0], gp.pbc & 1); y[i] = export_coord(p.y, gp.L[1], gp.pbc & 2); z[i] = export_coord(p.z, gp.L[2], gp.pbc & 4);
    species[i] = (int)((__double_as_longlong(p.w) >> 16) & 0xffff);
 }
 extern "C" int ddcmi_download_particles(ddcmi_ctx *ctx, int cap, int *nout, uint64_t *gid, int *species,

@@ -62,7 +62,7 @@ __global__ __launch_bounds__(CENSUS_THREADS) void k_structure_modes(int n, int p
          for (int a = 0; a < 3; a++)
          {
             const double L = sp.L[a];
-            if (sp.pbc >> a & 1) { if (r[a] > 0.5 * L) r[a] -= L; if (r[a] < -0.5 * L) r[a] += L; }      /* k_export_pos */
+            r[a] = export_coord(r[a], L, sp.pbc >> a & 1);
             t[a] = r[a] / L;
             t[a] -= rint(t[a]);      /* exact */
          }
@@ -109,17 +109,12 @@ static int structure_modes_check(ddcmi_ctx *ctx, const char *fn, int nspecies, i
    for (int l = 0; l < 3 * nk; l++)
       if (kvec[l] > DDCMI_SM_MAX_N || kvec[l] < -DDCMI_SM_MAX_N)
          SETERR(ctx, DDCMI_EUNSUPPORTED, "%s: kvec[%d][%d] = %d, at most %d in magnitude", fn, l / 3, l % 3, (int)kvec[l], DDCMI_SM_MAX_N);
-   const int off[6] = {1, 2, 3, 5, 6, 7};
-   for (int k = 0; k < 6; k++)
-      if (fabs(ctx->h[off[k]]) > 1e-10) SETERR(ctx, DDCMI_EUNSUPPORTED, "%s: only orthorhombic boxes are supported (h[%d]=%g)", fn, off[k], ctx->h[off[k]]);
-   if (!(ctx->h[0] > 0.0) || !(ctx->h[4] > 0.0) || !(ctx->h[8] > 0.0)) SETERR(ctx, DDCMI_EINVAL, "%s needs a box (ddcmi_set_box)", fn);
-   return DDCMI_OK;
+   return census_box_check(ctx, fn, 7);
 }
 /* this rank's sums and count [sync] */
 static int structure_modes_one(ddcmi_ctx *ctx, const int *select, int weight, int nk, const int32_t *kvec, double *rho, int64_t *count)
 {
    (void)hipSetDevice(ctx->device);
-   hipStream_t st = ctx->stream;
    const int n = ctx->nloc, ns = ctx->nspecies, nval = 2 * nk;
    if (n <= 0)      /* (a domain that holds no bead) */
    {
@@ -127,29 +122,22 @@ static int structure_modes_one(ddcmi_ctx *ctx, const int *select, int weight, in
       *count = 0;
       return DDCMI_OK;
    }
-   std::vector<int> sel((size_t)ns, 1);
-   if (select) for (int s = 0; s < ns; s++) sel[s] = select[s] != 0;
    SmParms sp;
-   sp.L[0] = ctx->h[0]; sp.L[1] = ctx->h[4]; sp.L[2] = ctx->h[8];
-   sp.pbc = ctx->pbc; sp.weight = weight;
+   census_set_box(ctx, sp); sp.weight = weight;
    int per_wg, nwg;
    census_split(n, SM_MAX_WG, &per_wg, &nwg);
-   /* census_part, in doubles: select | kvec | part_d | out_d | out_c | part_c */
-   const size_t o_kv = ((size_t)ns + 1) / 2, o_pd = o_kv + (3 * (size_t)nk + 1) / 2, o_od = o_pd + (size_t)nwg * nval, o_oc = o_od + nval, o_pc = o_oc + 1,
-                total = o_pc + ((size_t)nwg + 1) / 2;
-   ENSURE(ctx, ctx->census_part, total);
-   double *base = ctx->census_part.p;
-   HIPCHK(ctx, hipMemcpyAsync(base, sel.data(), (size_t)ns * sizeof(int), hipMemcpyHostToDevice, st));
-   HIPCHK(ctx, hipMemcpyAsync(base + o_kv, kvec, 3 * (size_t)nk * sizeof(int32_t), hipMemcpyHostToDevice, st));
-   hipLaunchKernelGGL(k_structure_modes, dim3(nwg, cdiv(nk, CENSUS_THREADS)), dim3(CENSUS_THREADS), 0, st, n, per_wg, ns, nk, sp, ctx->pos.p, ctx->species.p,
-                      ctx->d_charge_sp.p, (const int *)base, (const int *)(base + o_kv), base + o_pd, (unsigned *)(base + o_pc));
-   hipLaunchKernelGGL((k_census_final<RowsSum, long long>), dim3(cdiv(nval, 64)), dim3(64), 0, st, nwg, nval, base + o_pd, base + o_od, 1,
-                      (const unsigned *)(base + o_pc), (long long *)(base + o_oc));
-   HIPCHK(ctx, hipGetLastError());
-   HIPCHK(ctx, hipMemcpyAsync(rho, base + o_od, (size_t)nval * sizeof(double), hipMemcpyDeviceToHost, st));
-   HIPCHK(ctx, hipMemcpyAsync(count, base + o_oc, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-   HIPCHK(ctx, hipStreamSynchronize(st));
-   return DDCMI_OK;
+   CensusScratch cs;
+   const int s_sel = cs.seg(4, ns), s_kv = cs.seg(4, 3 * (size_t)nk), s_pd = cs.seg(8, (size_t)nwg * nval), s_od = cs.seg(8, nval), s_oc = cs.seg(8, 1),
+             s_pc = cs.seg(4, nwg);
+   int rc = cs.ensure(ctx);
+   if (rc) return rc;
+   std::vector<int> sel;
+   if ((rc = census_upload_select(ctx, select, sel, cs.at<int>(s_sel)))) return rc;
+   HIPCHK(ctx, hipMemcpyAsync(cs.at<int>(s_kv), kvec, 3 * (size_t)nk * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+   hipLaunchKernelGGL(k_structure_modes, dim3(nwg, cdiv(nk, CENSUS_THREADS)), dim3(CENSUS_THREADS), 0, ctx->stream, n, per_wg, ns, nk, sp, ctx->pos.p, ctx->species.p,
+                      ctx->d_charge_sp.p, cs.at<int>(s_sel), cs.at<int>(s_kv), cs.at<double>(s_pd), cs.at<unsigned>(s_pc));
+   return census_finish<RowsSum, long long>(ctx, nwg, nval, cs.at<double>(s_pd), cs.at<double>(s_od), rho, 1, cs.at<unsigned>(s_pc), cs.at<long long>(s_oc),
+                                            (long long *)count);
 }
 
 extern "C" int ddcmi_structure_modes(ddcmi_ctx *ctx, int nspecies, const int *select, int weight, int nk, const int32_t *kvec, double *rho, int64_t *count)
@@ -163,8 +151,6 @@ extern "C" int ddcmi_structure_modes(ddcmi_ctx *ctx, int nspecies, const int *se
 extern "C" int ddcmi_group_structure_modes(ddcmi_ctx **ctxs, int n, int nspecies, const int *select, int weight, int nk, const int32_t *kvec, double *rho,
                                            int64_t *count)
 {
-   if (ctxs && n >= 1 && ctxs[0] && !ctxs[0]->group_)
-      SETERR(ctxs[0], DDCMI_EINVAL, "ddcmi_group_structure_modes: not the contexts of an in-process group: use ddcmi_structure_modes");
    return analysis_group(ctxs, n, "structure_modes",
                          [=](ddcmi_ctx *c, const char *fn) { return structure_modes_check(c, fn, nspecies, weight, nk, kvec, rho, count); },
                          [=](ddcmi_ctx *c, size_t r) { return structure_modes_one(c, select, weight, nk, kvec, rho + r * 2 * (size_t)nk, count + r); });

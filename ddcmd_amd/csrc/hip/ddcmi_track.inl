@@ -16,14 +16,14 @@
  *                   sum[3 u .. 3 u + 2] += value, hits[u] += 1: a gid is owned by one bead of one rank, so slot u has one writer
  *                   in the launch, and launches on one stream are ordered -- a plain load, add and store.
  * The value is what a download returns at this point: the force arrays as they stand, the stored velocity, the slot's position
- * shifted once by the box side where it left a periodic box (k_export_pos's comparisons and subtraction).
+ * shifted once by the box side where it left a periodic box (census_position).
  * The accumulators belong to the rank, not to the bead: a tracked bead that migrates adds to its new owner's sums, and the window's
  * value is the sum of the ranks' partial sums.  Nothing travels in the migration records. */
 
 #define TRACK_LDS_IDS 1024      /* pivots staged per workgroup: 8 KB of LDS */
 #define TRACK_MAX_WG 512        /* two workgroups per CU: each stages the pivots once */
 
-struct TrackBeads { const double4 *pos; const double *ax, *ay, *az; double L[3]; int pbc; };
+struct TrackBeads { const double4 *pos; const double *ax, *ay, *az; CensusBox box; };
 
 template <int WHAT>      /* 0 force, 1 velocity (both: the arrays ax, ay, az), 2 position */
 __global__ __launch_bounds__(CENSUS_THREADS) void k_track_accumulate(int n, int per_wg, unsigned long long gmin, unsigned long long gmax, int nu, int lstride,
@@ -38,7 +38,7 @@ __global__ __launch_bounds__(CENSUS_THREADS) void k_track_accumulate(int n, int 
    for (int i = beg + (int)threadIdx.x; i < end; i += CENSUS_THREADS)
    {
       const unsigned long long g = gid[i];
-      if (g < gmin || g > gmax) continue;
+      if (!gid_in_range(g, gmin, gmax)) continue;
       int lo = 0, hi = npiv;      /* the first pivot > g; g >= gmin = piv_s[0], so it is not the first one */
       while (lo < hi)
       {
@@ -50,24 +50,14 @@ __global__ __launch_bounds__(CENSUS_THREADS) void k_track_accumulate(int n, int 
       if (lstride == 0) { if (piv_s[u] != g) continue; }
       else
       {
-         int a = u << lstride, e = min(nu, a + stride);      /* the first entry >= g among ids[a, e) */
-         while (a < e)
-         {
-            const int mid = a + ((e - a) >> 1);
-            if (ids[mid] < g) a = mid + 1; else e = mid;
-         }
-         if (a >= nu || ids[a] != g) continue;
-         u = a;
+         /* g is among the gids ids[a, e) behind its pivot, or not listed: where e < nu, ids[e] is the next pivot, and that is > g (the
+          * pivot search), so "the first entry >= g lies in [a, e) and is g" says what "it lies in [a, nu) and is g" said.  (u is
+          * written on a miss too: the bead is done then.) */
+         const int a = u << lstride;
+         if (!gid_find(ids, a, min(nu, a + stride), g, &u)) continue;
       }
       double v[3];
-      if (WHAT == 2)
-      {
-         const double4 p4 = b.pos[i];
-         v[0] = p4.x; v[1] = p4.y; v[2] = p4.z;
-#pragma unroll
-         for (int c = 0; c < 3; c++)
-            if (b.pbc >> c & 1) { if (v[c] > 0.5 * b.L[c]) v[c] -= b.L[c]; if (v[c] < -0.5 * b.L[c]) v[c] += b.L[c]; }      /* k_export_pos */
-      }
+      if (WHAT == 2) census_position(b.box, b.pos[i], v);
       else { v[0] = b.ax[i]; v[1] = b.ay[i]; v[2] = b.az[i]; }
       double *s = sum + 3 * (size_t)u;
       s[0] += v[0]; s[1] += v[1]; s[2] += v[2];
@@ -137,8 +127,7 @@ extern "C" int ddcmi_track_accumulate(ddcmi_ctx *ctx, int what)
    int per_wg, nwg;
    census_split(n, TRACK_MAX_WG, &per_wg, &nwg);
    TrackBeads b;
-   b.pos = ctx->pos.p; b.pbc = ctx->pbc;
-   for (int a = 0; a < 3; a++) b.L[a] = ctx->h[4 * a];
+   b.pos = ctx->pos.p; census_set_box(ctx, b.box);
    if (what == 0) { b.ax = ctx->fx.p; b.ay = ctx->fy.p; b.az = ctx->fz.p; }
    else { b.ax = ctx->vx.p; b.ay = ctx->vy.p; b.az = ctx->vz.p; }
    const auto k = what == 2 ? k_track_accumulate<2> : what == 1 ? k_track_accumulate<1> : k_track_accumulate<0>;

@@ -152,6 +152,18 @@ int ddcmi_debug_scan(ddcmi_ctx *ctx, int n, const int *in, int *out, int *total,
  * (unsigned) and key2[norder] (may be NULL), ascending (key, key2, entry); an entry of a cell outside [0, norder): DDCMI_EINVAL.  What lies
  * between the cells is left alone.  ncell <= 2^20, norder <= 2^24. */
 int ddcmi_debug_sort_cells(int ncell, const int *start, const int *cnt, int norder, int *order, const uint64_t *key, const int *key2);
+/* ddcmi_debug_compact: the stable compaction the record-writing analyses share (count, scan, pack over the ranges of census_split(n, max_wg),
+ * max_wg <= 2048) on flags[n]: places[k] = the index of the k-th non-zero flag for k < nrec, *total = their number.  places has room for nrec +
+ * DDCMI_DEBUG_COMPACT_GUARD ints: the device array is that long, starts as the caller's and comes back whole, so that places[] shows what the
+ * pack left alone -- with nrec below the total, everything from nrec on.  1 <= n <= 2^24, 0 <= nrec <= 2^24. */
+#define DDCMI_DEBUG_COMPACT_GUARD 64
+int ddcmi_debug_compact(int n, const int *flags, int max_wg, int nrec, int *places, int *total);
+/* ddcmi_debug_gid_find: the search of an ascending gid list that subsetWrite's idList, cholAnalysis and FORCE_AVERAGE share, over ids[nids]
+ * (not ascending: DDCMI_EINVAL): index[q] = where queries[q] stands in ids, -1 where it is not listed.  nids, nq <= 2^24. */
+int ddcmi_debug_gid_find(int nids, const uint64_t *ids, int nq, const uint64_t *queries, int *index);
+/* ddcmi_debug_gid_find_in: the same search over the sub-range ids[lo, hi), 0 <= lo <= hi <= nids, as FORCE_AVERAGE searches the gids behind a
+ * pivot: index[q] is still the place in ids[], -1 where queries[q] is not in the range.  wide != 0: the instantiation with 64-bit indices, subsetWrite's. */
+int ddcmi_debug_gid_find_in(int nids, const uint64_t *ids, int lo, int hi, int wide, int nq, const uint64_t *queries, int *index);
 
 /* the cross-workgroup reductions, each on the caller's rows and on the current device (tests/test_gpu_reductions.py; tests/reductions.py restates
  * their orders).  The very kernels of the product with the product's launch shapes.  Arguments out of range: DDCMI_EINVAL.  Every output array

@@ -12,7 +12,11 @@ The reciprocals.  Inputs: 262 values in each binade 2^-20 ... 2^40 and four in e
 The wave operations equal numpy on every lane of every set, row_sum_dpp and lean_effective bit for bit.  The scan equals the shifted cumsum
 at every size around its tile (2048) and around the 256 tiles at which its second kernel's loop makes a second trip, out of place and in
 place, with and without the total, one context shrinking and growing through all of them.  The in-cell sorts equal Python's sort by
-(gid as unsigned, shift code, index) on cells of 0 ... 300 entries with ties and gids at and above 2^63.
+(gid as unsigned, shift code, index) on cells of 0 ... 300 entries with ties and gids at and above 2^63.  The census frame's
+compaction equals numpy.flatnonzero at every size around a wave, a block and a workgroup's range, and leaves what lies behind nrec alone;
+its gid search equals numpy.searchsorted over whole lists of the lengths at which FORCE_AVERAGE's pivot stride changes (the call with int
+indices over [0, n): cholAnalysis'), over the sub-ranges behind a pivot as k_track_accumulate forms them, and with 64-bit indices as subsetWrite
+calls it.  The pivot search of k_track_accumulate itself, an upper bound in LDS, is not run by these hooks: tests/test_gpu_track.py has it.
 
 docs/primitive_variants.md lists the one-line mutations of the device code that these tests were run against."""
 import ctypes
@@ -41,10 +45,14 @@ def lib(built):
     lib.ddcmi_debug_wave_ops.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     lib.ddcmi_debug_scan.argtypes = [ctypes.c_void_p, ctypes.c_int, c_int_p, c_int_p, c_int_p, ctypes.c_int]
     lib.ddcmi_debug_sort_cells.argtypes = [ctypes.c_int, c_int_p, c_int_p, ctypes.c_int, c_int_p, c_u64_p, c_int_p]
+    lib.ddcmi_debug_compact.argtypes = [ctypes.c_int, c_int_p, ctypes.c_int, ctypes.c_int, c_int_p, c_int_p]
+    lib.ddcmi_debug_gid_find.argtypes = [ctypes.c_int, c_u64_p, ctypes.c_int, c_u64_p, c_int_p]
+    lib.ddcmi_debug_gid_find_in.argtypes = [ctypes.c_int, c_u64_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_u64_p, c_int_p]
     lib.ddcmi_create.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int]
     lib.ddcmi_destroy.argtypes = [ctypes.c_void_p]
     lib.ddcmi_destroy.restype = None
-    for f in (lib.ddcmi_debug_recip, lib.ddcmi_debug_wave_ops, lib.ddcmi_debug_scan, lib.ddcmi_debug_sort_cells, lib.ddcmi_create):
+    for f in (lib.ddcmi_debug_recip, lib.ddcmi_debug_wave_ops, lib.ddcmi_debug_scan, lib.ddcmi_debug_sort_cells, lib.ddcmi_debug_compact, lib.ddcmi_debug_gid_find, lib.ddcmi_debug_gid_find_in,
+              lib.ddcmi_create):
         f.restype = ctypes.c_int
     return lib
 
@@ -314,3 +322,144 @@ def test_bad_arguments(lib, ctx):
     assert f(2, sp, cp, 12, o2.ctypes.data_as(c_int_p), kp, None) == EINVAL
     assert np.array_equal(order, np.arange(12)[::-1])                                 # refused calls wrote nothing
     assert f(2, sp, cp, 12, op, kp, None) == 0 and list(order) == [8, 9, 10, 11, 7, 6, 5, 4, 0, 1, 2, 3]
+
+
+# ---- the census frame's compaction and gid search (ddcmi_census_frame.inl) ---------------------------------------------------
+COMPACT_GUARD = 64           # DDCMI_DEBUG_COMPACT_GUARD
+COMPACT_MAX_WG = 2048        # census_split(n, 2048) gives ranges of 256 slots up to n = 2^19: the last size spans four workgroups
+COMPACT_SIZES = (1, 63, 64, 65, 255, 256, 257, 511, 512, 513, 3 * 256 + 1)
+COMPACT_PATTERNS = ("zeros", "ones", "first", "last", "every64", "half")
+POISON = -559038737
+
+
+def compact_flags(pattern, n):
+    f = np.zeros(n, np.int32)
+    if pattern == "ones":
+        f[:] = 1
+    elif pattern == "first":
+        f[0] = 1
+    elif pattern == "last":
+        f[-1] = 1
+    elif pattern == "every64":
+        f[::64] = 1
+    elif pattern == "half":
+        f[:] = np.random.RandomState(20261021 + n).randint(0, 2, n)
+    return f
+
+
+def compact(lib, flags, nrec, max_wg=COMPACT_MAX_WG):
+    places = np.full(nrec + COMPACT_GUARD, POISON, np.int32)
+    total = ctypes.c_int(-1)
+    assert lib.ddcmi_debug_compact(len(flags), flags.ctypes.data_as(c_int_p), max_wg, nrec, places.ctypes.data_as(c_int_p), ctypes.byref(total)) == 0
+    return places, total.value
+
+
+@pytest.mark.parametrize("pattern", COMPACT_PATTERNS)
+def test_compact_equals_flatnonzero(lib, pattern):
+    for n in COMPACT_SIZES:
+        flags = compact_flags(pattern, n)
+        want = np.flatnonzero(flags).astype(np.int32)
+        places, total = compact(lib, flags, len(want))
+        assert total == len(want), (pattern, n)
+        assert np.array_equal(places[:len(want)], want), (pattern, n)
+        assert np.all(places[len(want):] == POISON), (pattern, n)
+
+
+@pytest.mark.parametrize("max_wg,n", [(1, 3 * 256 + 1), (2, 3 * 256 + 1), (1, 8 * 256), (3, 7 * 256 + 65)])
+def test_compact_workgroups_of_several_blocks(lib, max_wg, n):
+    """few workgroups, so that each walks several blocks of 256 slots (census_split(769, 1): one workgroup of four blocks, the last with one
+    slot; (769, 2): two of two; (2048, 1): eight full blocks; (1857, 3): three of three, the last short): the pack kernel's two alternating rows
+    of wave counts and the carry of a block's total into the next block's places"""
+    for pattern in COMPACT_PATTERNS:
+        flags = compact_flags(pattern, n)
+        want = np.flatnonzero(flags).astype(np.int32)
+        places, total = compact(lib, flags, len(want), max_wg)
+        assert total == len(want), (pattern, n)
+        assert np.array_equal(places[:len(want)], want) and np.all(places[len(want):] == POISON), (pattern, n)
+    flags = compact_flags("half", n)
+    want = np.flatnonzero(flags).astype(np.int32)
+    places, total = compact(lib, flags, len(want) - 1, max_wg)      # nrec one below the total
+    assert total == len(want) and np.array_equal(places[:len(want) - 1], want[:-1]) and np.all(places[len(want) - 1:] == POISON)
+
+
+def test_compact_stops_at_nrec(lib):
+    """nrec one below the total: the last kept slot has no place, and the guard behind nrec stays as it was"""
+    for pattern in ("ones", "half", "every64"):
+        flags = compact_flags(pattern, 3 * 256 + 1)
+        want = np.flatnonzero(flags).astype(np.int32)
+        places, total = compact(lib, flags, len(want) - 1)
+        assert total == len(want)
+        assert np.array_equal(places[:len(want) - 1], want[:-1]) and np.all(places[len(want) - 1:] == POISON), pattern
+
+
+def gid_lists():
+    """ascending 64-bit ids of the lengths around FORCE_AVERAGE's pivot strides, with ids above 2^32 and the largest value"""
+    for n in (1, 2, 1024, 1025, 2049):
+        rng = np.random.RandomState(n)
+        gaps = rng.randint(2, 1 << 20, n).astype(np.uint64)      # at least 2: a value strictly between any two neighbours
+        ids = np.cumsum(gaps, dtype=np.uint64) + np.uint64(5)
+        ids[n // 2:] += np.uint64(1) << np.uint64(33)            # the upper half above 2^32 (n = 1: the one id)
+        ids[-1] = np.uint64(2 ** 64 - 1)
+        yield ids
+
+
+def test_gid_find_equals_searchsorted(lib):
+    for ids in gid_lists():
+        n = len(ids)
+        between = ids[:-1] + np.uint64(1)
+        q = np.concatenate([[ids[0] - np.uint64(1), np.uint64(0)], [ids[-1]], [ids[0]], between, ids, ids[:1] + np.uint64(1)]).astype(np.uint64)
+        if n > 1:
+            q = np.concatenate([q, [ids[-2] + np.uint64(1)]]).astype(np.uint64)      # above every id but the largest value itself
+        at = np.searchsorted(ids, q, side="left")
+        hit = (at < n) & (ids[np.minimum(at, n - 1)] == q)
+        want = np.where(hit, at, -1).astype(np.int32)
+        assert hit.sum() >= n + 2 and (~hit).sum() >= 2
+        got = np.full(len(q), 12345, np.int32)
+        assert lib.ddcmi_debug_gid_find(n, ids.ctypes.data_as(c_u64_p), len(q), q.ctypes.data_as(c_u64_p), got.ctypes.data_as(c_int_p)) == 0
+        assert np.array_equal(got, want), n
+    # a list whose greatest id is not the largest value: a query above it
+    ids = np.array([7, 1 << 40, (1 << 63) + 5], np.uint64)
+    q = np.array([(1 << 63) + 6, 2 ** 64 - 1, 6, 7, 1 << 40], np.uint64)
+    got = np.full(len(q), 12345, np.int32)
+    assert lib.ddcmi_debug_gid_find(3, ids.ctypes.data_as(c_u64_p), len(q), q.ctypes.data_as(c_u64_p), got.ctypes.data_as(c_int_p)) == 0
+    assert got.tolist() == [-1, -1, -1, 0, 1]
+
+
+@pytest.mark.parametrize("wide", [0, 1])
+def test_gid_find_in_a_sub_range(lib, wide):
+    """the ranges k_track_accumulate searches, ids[u << l, min(n, (u + 1) << l)) behind pivot u for the strides 2 and 4 of lists of 1025 and
+    2049 gids, and a few others (empty, one entry, the tail): the queries are the range's gids, their neighbours in the list on either side
+    (listed, but outside the range: a miss), values between entries, below and above everything.  int and 64-bit indices."""
+    for ids in gid_lists():
+        n = len(ids)
+        ranges = [(0, 0), (n, n), (0, 1), (n - 1, n), (n // 3, n), (0, n)]
+        for l in (1, 2):
+            ranges += [(u << l, min(n, (u + 1) << l)) for u in (0, 1, (n - 1) >> l, ((n - 1) >> l) - 1) if u >= 0 and (u << l) < n]
+        for lo, hi in ranges:
+            around = ids[max(lo - 2, 0):min(hi + 2, n)]
+            q = np.concatenate([around, around + np.uint64(1), [np.uint64(0), np.uint64(2 ** 64 - 1)]]).astype(np.uint64)
+            at = lo + np.searchsorted(ids[lo:hi], q, side="left")
+            hit = (at < hi) & (ids[np.minimum(at, n - 1)] == q)
+            want = np.where(hit, at, -1).astype(np.int32)
+            got = np.full(len(q), 12345, np.int32)
+            assert lib.ddcmi_debug_gid_find_in(n, ids.ctypes.data_as(c_u64_p), lo, hi, wide, len(q), q.ctypes.data_as(c_u64_p), got.ctypes.data_as(c_int_p)) == 0
+            assert np.array_equal(got, want), (n, lo, hi, wide)
+    ids = np.arange(8, dtype=np.uint64)
+    q, got = ids.copy(), np.zeros(8, np.int32)
+    for lo, hi in ((-1, 4), (5, 4), (0, 9)):
+        assert lib.ddcmi_debug_gid_find_in(8, ids.ctypes.data_as(c_u64_p), lo, hi, wide, 8, q.ctypes.data_as(c_u64_p), got.ctypes.data_as(c_int_p)) == EINVAL
+
+
+def test_compact_and_gid_find_bad_arguments(lib):
+    f = np.ones(8, np.int32)
+    p = np.zeros(8 + COMPACT_GUARD, np.int32)
+    t = ctypes.c_int(0)
+    fp, pp = f.ctypes.data_as(c_int_p), p.ctypes.data_as(c_int_p)
+    for n, a, wg, nrec, b, c in ((0, fp, 4, 8, pp, ctypes.byref(t)), (8, None, 4, 8, pp, ctypes.byref(t)), (8, fp, 0, 8, pp, ctypes.byref(t)),
+                                 (8, fp, 2049, 8, pp, ctypes.byref(t)), (8, fp, 4, -1, pp, ctypes.byref(t)), (8, fp, 4, 8, None, ctypes.byref(t)), (8, fp, 4, 8, pp, None)):
+        assert lib.ddcmi_debug_compact(n, a, wg, nrec, b, c) == EINVAL
+    ids, q, idx = np.array([3, 2], np.uint64), np.array([2], np.uint64), np.zeros(1, np.int32)
+    ip, qp, xp = ids.ctypes.data_as(c_u64_p), q.ctypes.data_as(c_u64_p), idx.ctypes.data_as(c_int_p)
+    assert lib.ddcmi_debug_gid_find(2, ip, 1, qp, xp) == EINVAL      # not ascending
+    assert lib.ddcmi_debug_gid_find(0, ip, 1, qp, xp) == EINVAL and lib.ddcmi_debug_gid_find(1, None, 1, qp, xp) == EINVAL
+    assert lib.ddcmi_debug_gid_find(1, ip, 0, qp, xp) == EINVAL and lib.ddcmi_debug_gid_find(1, ip, 1, None, xp) == EINVAL and lib.ddcmi_debug_gid_find(1, ip, 1, qp, None) == EINVAL

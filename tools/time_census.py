@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""ANALYSIS vcmWrite, zdensity, KINETICENERGYDISTN, (chol:<lattice>, default 63: 1.0 M beads, 10^5 molecules) cholAnalysis and (track:<lattice>, 64: 1.05 M beads) FORCE_AVERAGE on the headline boxes: what one call of each entry point costs, beside one ddcmi_vaf_sample and
+"""ANALYSIS vcmWrite, zdensity, KINETICENERGYDISTN, DSF, subsetWrite, COARSEGRAIN, (chol:<lattice>, default 63: 1.0 M beads, 10^5 molecules) cholAnalysis and (track:<lattice>, 64: 1.05 M beads) FORCE_AVERAGE on the headline boxes: what one call of each entry point costs, beside one ddcmi_vaf_sample and
 one plain step of the same box in the same process.
    python3 tools/time_census.py [water:<lattice> | lipid:<x,y,z>] ...   (default: water:102 lipid:12,12,6 -- 4.24 M and 2.04 M beads)
 Every call is timed by HIP events recorded on the context's stream around it (the kernels and the copy of the result; median of
@@ -158,7 +158,13 @@ for spec in (sys.argv[1:] or ["water:102", "lipid:12,12,6", "chol:63", "track:64
             ("kinetic_energy_distn all x 100", 24 + 4, lambda: m.kinetic_energy_distn(kd_lo, kd_hi, [100] * s.nspecies, np.arange(s.nspecies))),
             ("kinetic_energy_distn 16357 bins", 24 + 4, lambda: m.kinetic_energy_distn(kd_lo[:1], kd_hi[:1], [16357], kd_one)),
             ("charge_density_modes mmax=8", 32 + 4, lambda: m.charge_density_modes(8)),      # one chunk of modes: one pass over the positions
-            ("charge_density_modes mmax=64", 8 * (32 + 4), lambda: m.charge_density_modes(64))]
+            ("charge_density_modes mmax=64", 8 * (32 + 4), lambda: m.charge_density_modes(64)),
+            # the record-writing passes (count, scan, pack; two waits): every 16th gid's record; every bead's (the copy of 24 B each in the time);
+            # a 32^3 grid one cell per bead, and smeared over eight (a sort of eight contributions per bead)
+            ("subset_records modulus 16", 2 * (32 + 24 + 8 + 4), lambda: m.subset_records(modulus=16)),
+            ("subset_records all", 2 * (32 + 24 + 8 + 4), lambda: m.subset_records()),
+            ("coarsegrain 32^3", 32 + 24 + 4, lambda: m.coarsegrain(32, 32, 32)),
+            ("coarsegrain 32^3 hat 1 A", 32 + 24 + 4, lambda: m.coarsegrain(32, 32, 32, smear, "hat"))]
     print("%s: %d beads, %d groups, %d species; one plain step %.4f ms" % (name, s.natoms, max(1, s.ngroup), s.nspecies, step_ms), flush=True)
     for label, bpb, call in rows:
         med, lo, host = timed(m, call, e0, e1)
